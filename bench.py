@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — `mul!` hot-path throughput on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is ONE 5-arg `mul!(res, H, v, α, β)` of `opHouseholder(h)` at n = 10^8 fp64 per GPU
 (BASELINE.json configs[1]) with all operands resident in HBM. For N > 1 the vectors are
@@ -14,17 +14,26 @@ are visible; it exits non-zero with a message when they are not, when any rank f
 all-reduce hook (libmxlo_rccl.so: ncclAllReduce issued from C on the ctx stream) cannot be installed on the `nccl`
 backend — a run never degrades silently to one rank or to Python-issued collectives. Under
 `python -m torch.distributed.run …` (WORLD_SIZE set) the ranks are used as launched.
-A second leg in the same line (`extras.single_process_shard_abi`) drives the same N devices from ONE host process
+With --full, a second leg in the same line (`extras.single_process_shard_abi`) drives the same N devices from ONE host process
 through `mxlo_shard_ctx_create` + the `_sharded` entry points (the Julia deployment shape, include/mxlo_rccl.h); it
 runs in a child process with a timeout so that it can never cost the headline line.
 
-One JSON line is printed by rank 0 with, besides the driver contract fields:
+A plain run sets up, warms up, times the K steps, writes the outputs when --dump-outputs is given and prints the line
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...). Everything else is measured only with --full; the
+single-process shard leg and the transport preflight at N = 1 are --full too (at N > 1 the preflight always runs).
+
+With --full, rank 0's JSON line carries, besides the driver contract fields:
   roofline      dominant kernel (the Householder update pass, 24 B/elt) timed with HIP events
                 on the launch stream, against the 8 TB/s HBM3E peak
   cpu_baseline  the oracle (C restatement of the reference `mulHouseholder!`) on the host cores,
                 1 thread, on a bounded sample of the same workload (rank 0, N == 1 only)
   extras        opDiagonal GB/s and (when built) InverseLBFGS / LBFGS apply/s — the other
                 figures the metric string names
+
+--dump-outputs DIR writes `res` of the last timed step (what a caller of mul! receives) as DIR/res.npy (float64; at N > 1
+every rank writes its own rows, DIR/res_rank<k>.npy): the whole vector up to DUMP_MAX_ELEMS elements, beyond that a fixed
+stratified sample (one element from each of the strata that tile the vector, offsets from numpy seed 0). The
+operands are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -39,6 +48,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md): 8.0 TB/s
+DUMP_MAX_ELEMS = 1 << 22  # --dump-outputs: float64 elements over all ranks (32 MiB)
 
 
 def parse(argv=None):
@@ -51,10 +61,15 @@ def parse(argv=None):
     ap.add_argument("--clock-spin-s", type=float, default=0.5,
                     help="untimed seconds of the same kernels before the warm-up steps, to reach steady GPU clocks")
     ap.add_argument("--nelem", dest="n", type=int, default=100_000_000, help="vector length per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure everything else: per-kernel roofline, quasi-Newton / cfg4 / misc legs, "
+                         "CPU baseline and parity, PMC traffic, transports, the single-process shard leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra legs")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="do not measure roofline.traffic in this run (two rocprofv3 --pmc passes over a child process, ~25 s); "
+                    help="with --full: do not measure roofline.traffic in this run (two rocprofv3 --pmc passes over a child process, ~25 s); "
                          "the profile-derived figure of profiles/traffic_householder.json is reported instead, labelled as such")
     ap.add_argument("--cpu-sample", type=int, default=100_000_000)   # the GPU workload's own n
     ap.add_argument("--qn-nelem", type=int, default=50_000_000,
@@ -67,7 +82,7 @@ def parse(argv=None):
                     help="N = 1 only: run the N-rank code path at world 1 — nccl process group of one rank, the NATIVE RCCL hook, "
                          "transport preflight, the peer transport, every collective of the timed legs — so that the code the "
                          "driver's multi-GPU run depends on has executed on a one-GPU box (the numbers are those of one GPU)")
-    # the N-device leg through the single-process shard ABI (runs in a child process with a timeout)
+    # the N-device leg through the single-process shard ABI (runs in a child process with a timeout; --full only)
     ap.add_argument("--no-shard-leg", action="store_true")
     ap.add_argument("--shard-leg-timeout", type=float, default=420.0)
     ap.add_argument("--launch-timeout", type=float, default=1200.0,
@@ -149,7 +164,7 @@ def die(msg: str, code: int = 2):
 # stderr and exits with status 7; the launcher then stops the other ranks and reports every rank's last phase.
 PHASE_LIMITS_S = {
     "import + library load": 300, "init_process_group": 300, "communicator creation": 240, "transport preflight": 240,
-    "operand set-up": 300, "clock spin-up": 300, "warm-up steps": 300, "timed loop": 300, "per-kernel timing": 300,
+    "operand set-up": 300, "clock spin-up": 300, "warm-up steps": 300, "timed loop": 300, "dump outputs": 300, "per-kernel timing": 300,
     "quasi-Newton legs": 900, "cfg4 legs": 300, "misc legs": 600, "cpu baseline": 300, "pmc traffic": 400, "second transport (optional)": 150, "teardown": 120,
 }
 
@@ -349,6 +364,8 @@ def run_shard_leg(args) -> dict:
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse(argv)
+    if args.steps < 1:
+        die("--steps must be >= 1")
     claim_stdout()
     if args.role == "shard-leg":
         emit_json(shard_leg(args))
@@ -362,7 +379,7 @@ def main(argv=None):
         return
     # the shard-ABI leg runs ONCE, after the process-per-GPU ranks are gone: in the launcher when this script started the
     # ranks itself (its rank-0 child skips it), in rank 0 under an external launcher
-    if not args.no_shard_leg and not args.worker_cmd and (self_launch or os.environ.get("MXLO_BENCH_SELF_LAUNCHED") != "1"):
+    if args.full and not args.no_shard_leg and not args.worker_cmd and (self_launch or os.environ.get("MXLO_BENCH_SELF_LAUNCHED") != "1"):
         out.setdefault("extras", {})["single_process_shard_abi"] = run_shard_leg(args)
     out.setdefault("complete", "abandoned" not in out)   # false: printed by a rescue (see `abandon`); every leg ran otherwise
     emit_json(out)
@@ -427,28 +444,29 @@ def worker(args):
     # ---- the transport proves itself BEFORE anything is timed: every rank all-reduces known 8 B /
     # 320 B / 6912 B payloads through the hook the applies use, checks the sums, checks that all ranks hold identical bits,
     # agrees on the verdict, and records what the communicator reports about itself. A failure ends the run non-zero,
-    # naming phase and rank; every wait is bounded.
+    # naming phase and rank; every wait is bounded. At N = 1 it is informational and runs with --full only.
     transports = {}
     peer_hook = None
-    with wd.phase("transport preflight"):
-        try:
-            transports = transport_preflight(args, lo, torch, dist, ctx, dev, rank, world, hook if native else None)
-        except Exception as e:
-            if distributed:
-                die(f"rank {rank}: transport preflight failed: {e}", 6)
-            transports = {"error": repr(e)[:300]}       # N = 1: informational only (no collective is on the timed path)
-        if distributed and native and (not args.no_extras or args.rehearse_distributed):
-            try:   # the second transport: peer-mapped one-shot exchange (csrc/peer.hip), measured below next to RCCL
-                peer_hook = lo.sharded.PeerShmHook(rank, world, timeout_ms=args.preflight_timeout_ms)
-                transports["peer_shm"] = {"latency_us": peer_hook.preflight(ctx.stream, 50, args.preflight_timeout_ms),
-                                          "mailboxes": "POSIX shm segment registered with every rank's HIP runtime; one kernel per collective"}
+    if distributed or args.full:
+        with wd.phase("transport preflight"):
+            try:
+                transports = transport_preflight(args, lo, torch, dist, ctx, dev, rank, world, hook if native else None)
             except Exception as e:
-                transports["peer_shm"] = {"error": repr(e)[:300]}
-                peer_hook = None
-            ok = torch.tensor([1 if peer_hook is not None else 0], dtype=torch.int32, device=dev)
-            dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-            if int(ok.item()) == 0:
-                peer_hook = None                        # never a mix of transports
+                if distributed:
+                    die(f"rank {rank}: transport preflight failed: {e}", 6)
+                transports = {"error": repr(e)[:300]}       # N = 1: informational only (no collective is on the timed path)
+            if args.full and distributed and native and (not args.no_extras or args.rehearse_distributed):
+                try:   # the second transport: peer-mapped one-shot exchange (csrc/peer.hip), measured below next to RCCL
+                    peer_hook = lo.sharded.PeerShmHook(rank, world, timeout_ms=args.preflight_timeout_ms)
+                    transports["peer_shm"] = {"latency_us": peer_hook.preflight(ctx.stream, 50, args.preflight_timeout_ms),
+                                              "mailboxes": "POSIX shm segment registered with every rank's HIP runtime; one kernel per collective"}
+                except Exception as e:
+                    transports["peer_shm"] = {"error": repr(e)[:300]}
+                    peer_hook = None
+                ok = torch.tensor([1 if peer_hook is not None else 0], dtype=torch.int32, device=dev)
+                dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+                if int(ok.item()) == 0:
+                    peer_hook = None                        # never a mix of transports
 
     n = args.n
     ph = wd.phase("operand set-up")
@@ -521,60 +539,65 @@ def worker(args):
     ms_per_step = dt / args.steps * 1e3
     bytes_per_step = 40.0 * n * world                   # 16 B/elt dot pass + 24 B/elt update pass
     value = bytes_per_step / (dt / args.steps) / 1e9
+    if args.dump_outputs:                                # before anything below writes into res again
+        with wd.phase("dump outputs"):
+            dump_outputs(args.dump_outputs, torch, res, rank, world)
 
-    # ---- per-kernel timing with HIP events on the launch stream (rank-local)
-    wd_k = wd.phase("per-kernel timing")
-    wd_k.__enter__()
-    tm = Timer(ctx)
-    f64 = dtype_code(torch.float64)
-    K = max(10, min(args.steps, 50))
-    dot_dev = torch.zeros(1, dtype=torch.float64, device=dev)
-    if distributed:                                      # time the kernels, not the collective
-        ctx.set_allreduce(None)
-    tm.start()
-    for _ in range(K):
-        _lib.call("mxlo_dot", ctx.handle, f64, ptr(h), ptr(v), n, ptr(dot_dev))
-    tm.stop()
-    ms_dot = tm.elapsed_ms() / K
-    tm.start()
-    for _ in range(K):
-        _lib.call("mxlo_householder_apply", ctx.handle, f64, ptr(res), ptr(h), ptr(v), n, alpha, beta, 0, ptr(dot_dev))
-    tm.stop()
-    ms_upd = tm.elapsed_ms() / K
-    D = lo.opDiagonal(h)
-    for _ in range(3):
-        lo.mul(res, D, v, alpha, beta)
-    tm.start()
-    for _ in range(K):
-        lo.mul(res, D, v, alpha, beta)
-    tm.stop()
-    ms_diag = tm.elapsed_ms() / K
-    install_hook()
-    wd_k.__exit__(None, None, None)
+    # ---- --full: per-kernel timing with HIP events on the launch stream (rank-local)
+    roofline = None
+    extras = {"householder_mul_frac_hbm_peak_per_gpu": round(value / world / HBM_PEAK_GBS, 4)}
+    if args.full:
+        wd_k = wd.phase("per-kernel timing")
+        wd_k.__enter__()
+        tm = Timer(ctx)
+        f64 = dtype_code(torch.float64)
+        K = max(10, min(args.steps, 50))
+        dot_dev = torch.zeros(1, dtype=torch.float64, device=dev)
+        if distributed:                                      # time the kernels, not the collective
+            ctx.set_allreduce(None)
+        tm.start()
+        for _ in range(K):
+            _lib.call("mxlo_dot", ctx.handle, f64, ptr(h), ptr(v), n, ptr(dot_dev))
+        tm.stop()
+        ms_dot = tm.elapsed_ms() / K
+        tm.start()
+        for _ in range(K):
+            _lib.call("mxlo_householder_apply", ctx.handle, f64, ptr(res), ptr(h), ptr(v), n, alpha, beta, 0, ptr(dot_dev))
+        tm.stop()
+        ms_upd = tm.elapsed_ms() / K
+        D = lo.opDiagonal(h)
+        for _ in range(3):
+            lo.mul(res, D, v, alpha, beta)
+        tm.start()
+        for _ in range(K):
+            lo.mul(res, D, v, alpha, beta)
+        tm.stop()
+        ms_diag = tm.elapsed_ms() / K
+        install_hook()
+        wd_k.__exit__(None, None, None)
 
-    upd_gbs = 24.0 * n / (ms_upd * 1e-3) / 1e9
-    traffic = None
-    tpath = os.path.join(ROOT, "profiles", "traffic_householder.json")
-    if os.path.exists(tpath):
-        try:
-            traffic = json.load(open(tpath)).get("householder_update_bytes_per_launch")
-        except Exception:
-            traffic = None
-    roofline = {"bound": "hbm", "kernel": "map_kernel<HouseholderOp> (update pass res = α(v - c·h), 24 B/elt)",
-                "achieved": round(upd_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(upd_gbs / HBM_PEAK_GBS, 4), "traffic": traffic,
-                "traffic_source": ("profile-derived, NOT measured in this run: HBM bytes per launch from separate rocprofv3 --pmc "
-                                   "FETCH_SIZE / WRITE_SIZE passes over the same kernel and size (tools/profile_gpu.sh -> "
-                                   "profiles/traffic_householder.json, gfx950 unit corrections applied there)") if traffic else None,
-                "avg_launch_ms": round(ms_upd, 4), "algorithmic_bytes_per_launch": 24.0 * n}
-    extras = {
-        "householder_dot_pass": {"ms": round(ms_dot, 4), "GB/s": round(16.0 * n / (ms_dot * 1e-3) / 1e9, 1),
-                                 "frac_hbm_peak": round(16.0 * n / (ms_dot * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
-        "householder_mul_frac_hbm_peak_per_gpu": round(value / world / HBM_PEAK_GBS, 4),
-        "opDiagonal_mul": {"ms": round(ms_diag, 4), "GB/s": round(24.0 * n / (ms_diag * 1e-3) / 1e9, 1),
-                           "frac_hbm_peak": round(24.0 * n / (ms_diag * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
-    }
-    del D
+        upd_gbs = 24.0 * n / (ms_upd * 1e-3) / 1e9
+        traffic = None
+        tpath = os.path.join(ROOT, "profiles", "traffic_householder.json")
+        if os.path.exists(tpath):
+            try:
+                traffic = json.load(open(tpath)).get("householder_update_bytes_per_launch")
+            except Exception:
+                traffic = None
+        roofline = {"bound": "hbm", "kernel": "map_kernel<HouseholderOp> (update pass res = α(v - c·h), 24 B/elt)",
+                    "achieved": round(upd_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(upd_gbs / HBM_PEAK_GBS, 4), "traffic": traffic,
+                    "traffic_source": ("profile-derived, NOT measured in this run: HBM bytes per launch from separate rocprofv3 --pmc "
+                                       "FETCH_SIZE / WRITE_SIZE passes over the same kernel and size (tools/profile_gpu.sh -> "
+                                       "profiles/traffic_householder.json, gfx950 unit corrections applied there)") if traffic else None,
+                    "avg_launch_ms": round(ms_upd, 4), "algorithmic_bytes_per_launch": 24.0 * n}
+        extras.update({
+            "householder_dot_pass": {"ms": round(ms_dot, 4), "GB/s": round(16.0 * n / (ms_dot * 1e-3) / 1e9, 1),
+                                     "frac_hbm_peak": round(16.0 * n / (ms_dot * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
+            "opDiagonal_mul": {"ms": round(ms_diag, 4), "GB/s": round(24.0 * n / (ms_diag * 1e-3) / 1e9, 1),
+                               "frac_hbm_peak": round(24.0 * n / (ms_diag * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
+        })
+        del D
 
     out = None
     if rank == 0:
@@ -584,7 +607,7 @@ def worker(args):
             "metric": "mul! GB/s (frac HBM peak) at n=10^8 fp64; L-BFGS apply/s, 1/2/4/8 GPU",
             "value": round(value, 1), "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
+            "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": "opHouseholder(h) 5-arg mul!(res,H,v,1,0), n=%d fp64 per GPU (configs[1])" % n,
                        "n_per_gpu": n, "algorithmic_bytes_per_elt": 40,
                        "sharding": ("row ranges over %d ranks (one process per GPU), 1-double all-reduce per apply: %s" % (world, transport)) if distributed else "none",
@@ -596,6 +619,8 @@ def worker(args):
                           if args.rehearse_distributed else None),
             "phases_s": {k: v for k, v in wd.history},
         }
+        if args.dump_outputs:
+            out["outputs_dir"] = os.path.abspath(args.dump_outputs)
 
     # From here on the headline is measured. Every later leg is an extra: if one of them stalls (a collective a rank never
     # joins, a transport that dies) the watchdog calls `abandon` instead of ending the run with status 7 — rank 0 prints
@@ -621,8 +646,9 @@ def worker(args):
     if distributed:
         wd.rescue = abandon
 
-    # ---- quasi-Newton apply/s (the second figure of the metric string)
-    if not args.no_extras and hasattr(lo, "InverseLBFGSOperator"):
+    # ---- --full: quasi-Newton apply/s (the second figure of the metric string) and the other legs
+    legs = args.full and not args.no_extras
+    if legs and hasattr(lo, "InverseLBFGSOperator"):
         with wd.phase("quasi-Newton legs"):
             if os.environ.get("MXLO_BENCH_FAULT") == "extras-stall" and rank == world - 1 and world > 1:
                 time.sleep(1e6)                          # TEST HOOK: the last rank never joins the extras' collectives
@@ -632,21 +658,21 @@ def worker(args):
                 extras["lbfgs_error"] = repr(e)
             install_hook()                                   # rank 0 cleared it for the single-GPU cfg5 leg
 
-    if not args.no_extras:
+    if legs:
         with wd.phase("cfg4 legs"):
             try:
                 extras.update(bench_cfg4(lo, torch, dev, ctx))
             except Exception as e:
                 extras["cfg4_error"] = repr(e)
 
-    if not args.no_extras and rank == 0 and world == 1:
+    if legs and rank == 0 and world == 1:
         with wd.phase("misc legs"):
             try:
                 extras.update(bench_misc(lo, torch, dev, ctx))
             except Exception as e:
                 extras["misc_error"] = repr(e)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         with wd.phase("cpu baseline"):
             # parity AT THE BENCHMARK'S OWN SIZE beside the throughput: the CPU legs run the oracle on the
             # device's operands, so what they compute is compared with the device result instead of being thrown away
@@ -670,7 +696,7 @@ def worker(args):
                 except Exception as e:
                     extras["cpu_legs_error"] = repr(e)[:200]
 
-    if rank == 0 and world == 1 and not args.no_traffic and not args.no_extras:
+    if legs and rank == 0 and world == 1 and not args.no_traffic:
         with wd.phase("pmc traffic"):
             t_meas, how = measure_traffic(n)
             if t_meas is not None:
@@ -729,6 +755,22 @@ def worker(args):
             if rank == 0:
                 out["teardown_error"] = repr(e)[:300]
     return out
+
+
+def dump_outputs(path, torch, res, rank, world):
+    """--dump-outputs: `res` as float64 .npy — whole up to DUMP_MAX_ELEMS / world elements, else one element from each of k
+    strata that tile [0, n) at offsets drawn from numpy seed 0 (fixed for a given n and world: runs compare element for element)."""
+    import numpy as np
+    n, k = res.numel(), DUMP_MAX_ELEMS // world
+    torch.cuda.synchronize()
+    if n <= k:
+        sample = res.cpu().numpy()
+    else:
+        edges = np.arange(k + 1, dtype=np.int64) * n // k
+        idx = edges[:-1] + (np.random.default_rng(0).random(k) * np.diff(edges)).astype(np.int64)
+        sample = res[torch.from_numpy(idx).to(res.device)].cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "res.npy" if world == 1 else "res_rank%d.npy" % rank), sample.astype(np.float64, copy=False))
 
 
 def transport_preflight(args, lo, torch, dist, ctx, dev, rank, world, native_hook):

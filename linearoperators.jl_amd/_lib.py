@@ -52,7 +52,8 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_voi
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile every HIP translation unit for gfx950 and link ``libmxlo.so`` in-tree."""
-    cmd = ["make", "-C", CSRC, "-j", str(max(2, (os.cpu_count() or 4))), "all"]
+    jobs = int(os.environ.get("MAX_JOBS") or min(16, os.cpu_count() or 4))   # a shared host's cpu_count is not our share
+    cmd = ["make", "-C", CSRC, "-j", str(max(2, jobs)), "all"]
     if force:
         cmd.insert(1, "-B")
     out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

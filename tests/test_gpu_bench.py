@@ -17,7 +17,7 @@ def test_rehearsal_of_the_n_rank_path_at_world_1():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rehearse-distributed", "--steps", "5", "--warmup", "2",
-                        "--nelem", "4000000", "--no-cpu-baseline", "--no-shard-leg", "--clock-spin-s", "0.05"],
+                        "--nelem", "4000000", "--full", "--no-cpu-baseline", "--no-shard-leg", "--clock-spin-s", "0.05"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -45,7 +45,7 @@ def test_a_failing_or_stalled_second_transport_leg_cannot_sink_the_headline(faul
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", MXLO_BENCH_FAULT=fault, MXLO_BENCH_OPTIONAL_LIMIT_S="3")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rehearse-distributed", "--steps", "5", "--warmup", "2",
-                        "--nelem", "4000000", "--no-extras", "--no-cpu-baseline", "--no-shard-leg", "--clock-spin-s", "0.05"],
+                        "--nelem", "4000000", "--full", "--no-extras", "--no-cpu-baseline", "--no-shard-leg", "--clock-spin-s", "0.05"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -69,7 +69,7 @@ def test_n_ranks_on_one_device_over_the_debug_transport(n):
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--single-device", "--backend", "gloo", "--steps", "5",
                         "--warmup", "2", "--nelem", "4000000" if n == 2 else "1000000", "--qn-nelem", "50000000" if n == 2 else "400000",
-                        "--no-cpu-baseline", "--no-shard-leg", "--clock-spin-s", "0.05"],
+                        "--full", "--no-cpu-baseline", "--no-shard-leg", "--clock-spin-s", "0.05"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -90,7 +90,7 @@ def test_a_rank_that_never_joins_an_extra_leg_cannot_sink_the_headline():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", MXLO_BENCH_FAULT="extras-stall")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--single-device", "--backend", "gloo", "--steps", "5",
-                        "--warmup", "2", "--nelem", "4000000", "--no-cpu-baseline", "--no-shard-leg", "--clock-spin-s", "0.05",
+                        "--warmup", "2", "--nelem", "4000000", "--full", "--no-cpu-baseline", "--no-shard-leg", "--clock-spin-s", "0.05",
                         "--phase-timeout-scale", "0.03"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -99,3 +99,35 @@ def test_a_rank_that_never_joins_an_extra_leg_cannot_sink_the_headline():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["roofline"]["frac"] > 0
     assert "abandoned" in d or "lbfgs_error" in d["extras"] or "teardown_error" in d
+
+
+def test_a_plain_run_times_only_the_headline_and_dumps_what_the_last_step_computed(tmp_path, dev):
+    """Without --full: set-up, warm-up, exactly --steps timed steps, the line — no extra leg. --dump-outputs writes `res`
+    of the last step, which the oracle's mulHouseholder! reproduces from the same seeded operands."""
+    import numpy as np
+    import torch
+
+    import oracle
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    n = 1_000_000
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                        "--nelem", str(n), "--clock-spin-s", "0.05", "--dump-outputs", str(tmp_path / "out")],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), p.stdout[-500:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["complete"] is True
+    assert d["unit"] == "GB/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and d["full"] is False
+    assert set(d["phases_s"]) == {"import + library load", "communicator creation", "operand set-up", "clock spin-up",
+                                  "warm-up steps", "timed loop", "dump outputs"}
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["transports"] == {}
+    assert set(d["extras"]) == {"householder_mul_frac_hbm_peak_per_gpu"}
+    got = np.load(tmp_path / "out" / "res.npy")
+    assert got.dtype == np.float64 and got.shape == (n,)
+    gen = torch.Generator(device=dev).manual_seed(1234)             # bench.py's operands at rank 0
+    h = torch.rand(n, dtype=torch.float64, device=dev, generator=gen) - 0.5
+    h /= (h * h).sum().sqrt()
+    v = torch.rand(n, dtype=torch.float64, device=dev, generator=gen) * 2 - 1
+    ref = oracle.householder_mul(np.zeros(n), h.cpu().numpy(), v.cpu().numpy(), 1.0, 0.0)
+    assert np.linalg.norm(got - ref) / np.linalg.norm(ref) <= 1e-12

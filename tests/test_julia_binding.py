@@ -198,7 +198,16 @@ def test_kernel_function_methods_are_defined_for_device_vectors():
 # extension adds to a reference function must have an arity the reference itself defines or calls — a renamed kernel
 # function or a changed argument list upstream would otherwise only fail on a Julia-equipped host.
 REF = pathlib.Path("/root/reference")
-needs_ref = pytest.mark.skipif(not (REF / "src").is_dir(), reason="/root/reference is only present in the build container")
+
+
+def _ref_has(p: pathlib.Path, is_dir: bool = False) -> bool:
+    try:
+        return p.is_dir() if is_dir else p.exists()
+    except OSError:                     # a parent directory this user may not enter: the reference is not available
+        return False
+
+
+needs_ref = pytest.mark.skipif(not _ref_has(REF / "src", is_dir=True), reason="needs the reference checkout, which is not readable here")
 
 
 def _ref_sources() -> str:
@@ -280,7 +289,7 @@ def test_runtests_mirrors_the_reference_gpu_tests_line_by_line():
     for frag in ("BlockDiagonalOperator(A, B, C)", "y isa MXVector{Float32}", "storage_type(adjoint(A))", "storage_type(transpose(A))",
                  "storage_type(Diagonal(v)) == typeof(v)", "@allocated mul!(res, B, x)", "@allocated push!(HD, x, y, 1.0, x, tmpd)"):
         assert frag in rt, frag
-    if (REF / "test" / "gpu" / "test_S_kwarg.jl").exists():       # what the include relies on still exists upstream
+    if _ref_has(REF / "test" / "gpu" / "test_S_kwarg.jl"):       # what the include relies on still exists upstream
         up = (REF / "test" / "gpu" / "test_S_kwarg.jl").read_text()
         assert "function test_S_kwarg(; arrayType" in up
         for frag in ("LinearOperator(mat; S = vecTother)", "opRestriction([1, 2, 3], 32; S = vecT)", "arrayType(rand(Float32, 32, 32))",

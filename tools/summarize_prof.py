@@ -25,7 +25,7 @@ def short(name):
     return name[:70]
 
 
-print("== kernel stats (rocprofv3 --kernel-trace --stats, bench.py --steps 20 --warmup 5) ==")
+print("== kernel stats (rocprofv3 --kernel-trace --stats, bench.py --steps 20 --warmup 5 --full) ==")
 for f in glob.glob(os.path.join(out, "stats", "**", "*kernel_stats.csv"), recursive=True):
     rows = list(csv.DictReader(open(f)))
     rows.sort(key=lambda r: -float(r.get("TotalDurationNs", 0) or 0))
