@@ -138,6 +138,32 @@ int32_t fused_fault_check(mxlo_ctx *ctx) {
             code == kFaultHouseholder ? "opHouseholder" : (code == kFaultHermitian ? "opHermitian" : (code == kFaultKron ? "kron" : "quasi-Newton")), ctx->tune.fused_timeout_ms);
   return MXLO_EHIP;
 }
+
+int32_t stage_alias(mxlo_ctx *ctx, const void *res, int64_t res_bytes, const void **v, int64_t v_bytes, bool same_ok,
+                    const char *what) {
+  if (!ctx->tune.alias_guard || !bytes_overlap(res, res_bytes, *v, v_bytes) || (same_ok && res == *v)) return MXLO_OK;
+  const size_t phase = (uintptr_t)*v & 255u, need = (size_t)v_bytes + 256;
+  if (ctx->stage_bytes < need) {
+    MXLO_REQUIRE(!ctx->capturing, MXLO_ESTATE,
+                 "%s: res overlaps v inside a graph capture and the ctx's staging buffer (%zu bytes) is smaller than v "
+                 "(%lld bytes) — run the aliased call once before the capture", what, ctx->stage_bytes, (long long)v_bytes);
+    if (ctx->stage) {                          // stream-ordered users only: drain before the buffer is replaced
+      MXLO_HIP(hipStreamSynchronize(ctx->stream));
+      MXLO_HIP(hipFree(ctx->stage));
+    }
+    ctx->stage = nullptr;
+    ctx->stage_bytes = 0;
+    hipError_t e = hipMalloc(&ctx->stage, need);
+    MXLO_REQUIRE(e == hipSuccess, MXLO_ENOMEM, "%s staging buffer: %s", what, hipGetErrorString(e));
+    ctx->stage_bytes = need;
+    ++ctx->scratch_generation;                 // graphs that recorded the old buffer are stale now
+  }
+  if (ctx->capturing) ctx->scratch_used_in_capture = true;
+  void *dst = (char *)ctx->stage + phase;
+  MXLO_HIP(hipMemcpyAsync(dst, *v, (size_t)v_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  *v = dst;
+  return MXLO_OK;
+}
 }  // namespace mxlo
 
 MXLO_API int32_t mxlo_ctx_destroy(mxlo_ctx *ctx) {
@@ -153,6 +179,7 @@ MXLO_API int32_t mxlo_ctx_destroy(mxlo_ctx *ctx) {
   if (ctx->kron_cnt) (void)hipFree(ctx->kron_cnt);
   if (ctx->fault_host) (void)hipHostFree(ctx->fault_host);
   if (ctx->scratch) (void)hipFree(ctx->scratch);
+  if (ctx->stage) (void)hipFree(ctx->stage);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   if (ctx->switch_event) (void)hipEventDestroy(ctx->switch_event);
   delete ctx;
@@ -301,7 +328,7 @@ MXLO_API int32_t mxlo_graph_launch(mxlo_graph *g) {
                  "after the capture: slot order, scaling factor and kernel choice are baked into the graph — recapture");
   }
   MXLO_REQUIRE(g->scratch_generation < 0 || g->scratch_generation == g->ctx->scratch_generation, MXLO_ESTATE,
-               "mxlo_graph_launch: the opHermitian workspace recorded in this graph was reallocated (a larger n arrived) "
+               "mxlo_graph_launch: the opHermitian workspace or the aliasing staging buffer recorded in this graph was reallocated (a larger n arrived) "
                "— recapture");
   // A graph replays on the stream it was captured from. If the ctx has moved to another stream since, order the two:
   // the workspaces, the scalar buffer and the exchange slots of the single-launch kernels belong to the ctx, not to a
@@ -457,7 +484,14 @@ MXLO_API int32_t mxlo_ctx_tune(mxlo_ctx *ctx, const char *key, int64_t value) {
     ctx->tune.qn_persist_lds_pad = (int)value;
   } else if (!strcmp(key, "kron_fuse")) {
     MXLO_REQUIRE(value >= 0 && value <= 2, MXLO_EINVAL, "kron_fuse must be 0, 1 (or 2: timing experiment without the wait, wrong results)");
+    // mode 2 does not wait, so its last consumer can zero a row block's counter before late producers add to it: leaving or
+    // entering it re-arms the counters, or the next waiting apply could consume a row block early
+    if ((ctx->tune.kron_fuse == 2 || value == 2) && ctx->tune.kron_fuse != (int)value && ctx->kron_cnt)
+      MXLO_HIP(hipMemsetAsync(ctx->kron_cnt, 0, sizeof(unsigned) * ctx->kron_cnt_n, ctx->stream));
     ctx->tune.kron_fuse = (int)value;
+  } else if (!strcmp(key, "alias_guard")) {
+    MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "alias_guard must be 1 or 0 (test hook: overlapping res / v unguarded)");
+    ctx->tune.alias_guard = (int)value;
   } else if (!strcmp(key, "herm_order")) {
     MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "herm_order must be 0 or 1");
     ctx->tune.herm_order = (int)value;

@@ -251,6 +251,7 @@ struct mxlo_blockdiag {
   Tile *d_tiles_n = nullptr, *d_tiles_t = nullptr;
   int64_t ntiles_n = 0, ntiles_t = 0;
   size_t lds_bytes = 0;     // dynamic LDS of a launch: the product buffer of the sparse tiles, 0 without sparse blocks
+  bool elementwise = true;  // square diagonal / identity / zero blocks only: res[i] comes from v[i] in the same lane
 };
 
 MXLO_API int32_t mxlo_blockdiag_create(mxlo_ctx *ctx, int32_t dtype, const mxlo_block_desc *blocks,
@@ -262,7 +263,7 @@ MXLO_API int32_t mxlo_blockdiag_create(mxlo_ctx *ctx, int32_t dtype, const mxlo_
   std::vector<DevBlock> hb((size_t)nblocks);
   std::vector<Tile> tn, tt;
   int64_t nrow = 0, ncol = 0;
-  bool has_sparse = false;
+  bool has_sparse = false, elementwise = true;
   for (int64_t k = 0; k < nblocks; ++k) {
     const mxlo_block_desc &b = blocks[k];
     MXLO_REQUIRE(b.kind >= MXLO_BLK_DIAG && b.kind <= MXLO_BLK_CSC, MXLO_EINVAL, "block %lld: bad kind", (long long)k);
@@ -294,6 +295,7 @@ MXLO_API int32_t mxlo_blockdiag_create(mxlo_ctx *ctx, int32_t dtype, const mxlo_
     }
     nrow += b.m;
     ncol += b.n;
+    elementwise = elementwise && b.kind != MXLO_BLK_DENSE && b.kind != MXLO_BLK_CSC && b.m == b.n;
     auto cut = [&](std::vector<Tile> &out, int64_t off, int64_t len, int64_t step) {
       if (b.kind == MXLO_BLK_CSC) {                      // one tile per chunk of the sweep (step = number of chunks)
         for (int64_t c = 0; c < step; ++c) out.push_back(Tile{hb[k], c, 0});
@@ -324,6 +326,7 @@ MXLO_API int32_t mxlo_blockdiag_create(mxlo_ctx *ctx, int32_t dtype, const mxlo_
   bd->ncol = ncol;
   bd->ntiles_n = (int64_t)tn.size();
   bd->ntiles_t = (int64_t)tt.size();
+  bd->elementwise = elementwise;
   bd->lds_bytes = has_sparse ? sp_lds_bytes<double>() : 0;   // (the Float32 instantiation uses 16 of the 24 KiB)
   hipError_t e = hipSuccess;
   auto up = [&](void **dst, const void *src, size_t bytes) {
@@ -392,6 +395,9 @@ MXLO_API int32_t mxlo_blockdiag_mul(mxlo_blockdiag *bd, void *res, const void *v
   const int64_t nres = op_mode == MXLO_OP_N ? bd->nrow : bd->ncol;
   if (nres == 0) return MXLO_OK;
   MXLO_REQUIRE(res && v, MXLO_EINVAL, "mxlo_blockdiag_mul: NULL operand");
+  const int64_t es = bd->dtype == MXLO_F64 ? 8 : 4;
+  MXLO_TRY(stage_alias(bd->ctx, res, nres * es, &v, (op_mode == MXLO_OP_N ? bd->ncol : bd->nrow) * es, bd->elementwise,
+                       "mxlo_blockdiag_mul"));
   eff_scalars(bd->dtype == MXLO_F64 ? 8 : 4, flags, alpha, beta);
   if (bd->dtype == MXLO_F64) return blockdiag_mul_t<double>(bd, (double *)res, (const double *)v, alpha, beta, op_mode, flags);
   return blockdiag_mul_t<float>(bd, (float *)res, (const float *)v, alpha, beta, op_mode, flags);

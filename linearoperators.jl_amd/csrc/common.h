@@ -187,6 +187,8 @@ struct Tune {
                                  // before it gives up, raises the ctx fault flag and stores NaN (a launch that is not fully
                                  // co-resident — GPU shared with other processes, CU masking — ends instead of hanging)
   int fused_debug_drop = -1;     // TEST HOOK: this workgroup of a single-launch kernel never publishes its partial
+  int alias_guard = 1;           // res overlapping v: stage v / leave the one-launch kron (stage_alias below); 0 = TEST HOOK,
+                                 // overlapping operands go to the kernels as they are (wrong results where a kernel races)
 };
 
 }  // namespace mxlo
@@ -222,6 +224,8 @@ struct mxlo_ctx {
   std::vector<std::pair<mxlo_qn *, int64_t>> captured_qn;   // quasi-Newton handles (and their generation) applied inside the open capture
   int64_t scratch_generation = 0;   // bumped whenever `scratch` is reallocated (captured opHermitian applies go stale)
   bool scratch_used_in_capture = false;
+  void *stage = nullptr;       // copy of a v that overlaps res (stage_alias); grow-on-demand, owned by the ctx
+  size_t stage_bytes = 0;
   mxlo::Tune tune;
 };
 
@@ -242,6 +246,21 @@ struct DeviceGuard {
   DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
 #define MXLO_DEVICE_GUARD(ctxexpr) mxlo::DeviceGuard dev_guard__((ctxexpr)->device)
+
+// ---- res aliasing v: mul!(x, op, x), or two overlapping windows of one buffer -------------------------------------------
+// The reference defines these calls for the operators whose closures read (or copy) all of v before they write res.
+// Our kernels take both pointers __restrict__, so the entry points decide: `same_ok` entry points (every element of res
+// written by the lane that read the same element of v, after it read it) accept res == v as it is; any other overlap is
+// STAGED — v is copied into the ctx's staging buffer with one D2D copy on the ctx stream (a memcpy node inside a graph
+// capture) and the kernels read the copy, placed at v's own address modulo 256 so every alignment-dependent path (and
+// its bits) is the one the unstaged call takes. A staging buffer that would have to grow inside a capture is MXLO_ESTATE,
+// before anything is enqueued. Calls whose operands do not overlap pay one comparison.
+inline bool bytes_overlap(const void *a, int64_t na, const void *b, int64_t nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return na > 0 && nb > 0 && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
+}
+int32_t stage_alias(mxlo_ctx *ctx, const void *res, int64_t res_bytes, const void **v, int64_t v_bytes, bool same_ok,
+                    const char *what);   // api_ctx.hip
 
 // ---- single-launch (grid-exchange) kernels: bounded wait + fault flag -----------------------------------------------
 // The workgroups of householder_fused_kernel / qn_apply_fused_kernel wait for each other's partials, so the whole grid

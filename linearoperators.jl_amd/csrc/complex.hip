@@ -1169,6 +1169,8 @@ MXLO_API int32_t mxlo_diag_mul_c(mxlo_ctx *ctx, int32_t dtype, void *res, const 
   MXLO_REQUIRE(n_min >= 0 && nrow >= n_min, MXLO_ESHAPE, "mxlo_diag_mul_c: n_min=%lld nrow=%lld", (long long)n_min,
                (long long)nrow);
   MXLO_REQUIRE(nrow == 0 || (res && (n_min == 0 || (d && v))), MXLO_EINVAL, "mxlo_diag_mul_c: NULL operand");
+  const int64_t es = dtype == MXLO_C64 ? 16 : 8;
+  MXLO_TRY(stage_alias(ctx, res, nrow * es, &v, n_min * es, true, "mxlo_diag_mul_c"));
   const bool cj = (flags & MXLO_CONJ_D) != 0;
   if (dtype == MXLO_C64)
     return cdiag<double>(ctx, (C<double> *)res, (const C<double> *)d, (const C<double> *)v, n_min, nrow,
@@ -1183,6 +1185,8 @@ MXLO_API int32_t mxlo_eye_mul_c(mxlo_ctx *ctx, int32_t dtype, void *res, const v
   MXLO_REQUIRE(n_min >= 0 && nrow >= n_min, MXLO_ESHAPE, "mxlo_eye_mul_c: n_min=%lld nrow=%lld", (long long)n_min,
                (long long)nrow);
   MXLO_REQUIRE(nrow == 0 || (res && (n_min == 0 || v)), MXLO_EINVAL, "mxlo_eye_mul_c: NULL operand");
+  const int64_t es = dtype == MXLO_C64 ? 16 : 8;
+  MXLO_TRY(stage_alias(ctx, res, nrow * es, &v, n_min * es, true, "mxlo_eye_mul_c"));
   if (dtype == MXLO_C64)
     return ceye<double>(ctx, (C<double> *)res, (const C<double> *)v, n_min, nrow,
                         scal_args(8, alpha_re, alpha_im, beta_re, beta_im, flags), flags);
@@ -1215,6 +1219,8 @@ MXLO_API int32_t mxlo_scale_c(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t n
 MXLO_API int32_t mxlo_conj_c(mxlo_ctx *ctx, int32_t dtype, void *res, const void *v, int64_t n) {
   CHECK_C("mxlo_conj_c");
   MXLO_REQUIRE(n >= 0 && (n == 0 || (res && v)), MXLO_EINVAL, "mxlo_conj_c: bad argument");
+  const int64_t es = dtype == MXLO_C64 ? 16 : 8;
+  MXLO_TRY(stage_alias(ctx, res, n * es, &v, n * es, true, "mxlo_conj_c"));   // conj!(res): res == v runs in place
   if (dtype == MXLO_C64)
     return launch_map<C<double>, 1, false, false>(ctx, (C<double> *)res, (const C<double> *)v, (const C<double> *)nullptr,
                                                   n, CConjOp<double>{});
@@ -1234,6 +1240,8 @@ MXLO_API int32_t mxlo_householder_mul_c(mxlo_ctx *ctx, int32_t dtype, void *res,
                                         int32_t flags) {
   CHECK_C("mxlo_householder_mul_c");
   MXLO_REQUIRE(n >= 0 && (n == 0 || (res && h && v)), MXLO_EINVAL, "mxlo_householder_mul_c: bad argument");
+  const int64_t es = dtype == MXLO_C64 ? 16 : 8;
+  MXLO_TRY(stage_alias(ctx, res, n * es, &v, n * es, true, "mxlo_householder_mul_c"));
   if (dtype == MXLO_C64)
     return chouse<double>(ctx, (C<double> *)res, (const C<double> *)h, (const C<double> *)v, n,
                           scal_args(8, alpha_re, alpha_im, beta_re, beta_im, flags));
@@ -1262,6 +1270,8 @@ MXLO_API int32_t mxlo_hermitian_mul_c(mxlo_ctx *ctx, int32_t dtype, void *res, c
   CHECK_C("mxlo_hermitian_mul_c");
   MXLO_REQUIRE(n >= 0 && lda >= (n > 1 ? n : 1), MXLO_ESHAPE, "mxlo_hermitian_mul_c: bad shape");
   MXLO_REQUIRE(n == 0 || (res && d && A && v), MXLO_EINVAL, "mxlo_hermitian_mul_c: NULL operand");
+  const int64_t es = dtype == MXLO_C64 ? 16 : 8;
+  MXLO_TRY(stage_alias(ctx, res, n * es, &v, n * es, false, "mxlo_hermitian_mul_c"));   // every row reads all of v
   const bool d_real = (flags & MXLO_D_REAL) != 0;
   if (dtype == MXLO_C64)
     return chermitian<double>(ctx, (C<double> *)res, d, d_real, (const C<double> *)A, lda, (const C<double> *)v, n,

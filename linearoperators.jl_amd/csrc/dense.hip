@@ -1818,7 +1818,11 @@ int32_t kron_t(mxlo_ctx *ctx, T *res, const T *A, int64_t am, int64_t an, int64_
   // same tile class for both (the one gemm() would pick for each), the same A layout, every tile of both products on its
   // own CU (grid <= #CU and co-resident), DMA preconditions as gemm().
   // (inside a graph capture only once a warm-up apply has probed the XCD map and allocated the counters: neither can happen there)
-  if (ctx->tune.kron_fuse && trans_a == trans_b && ctx->fault_dev && (!ctx->capturing || (ctx->xcd_map == 1 && ctx->kron_cnt_n > 0)) && m > 0 && n > 0 && p > 0 && q > 0 &&
+  // Not when res overlaps x (mul!(x, K, x) of a square kron, src/kron.jl:14-40 materialises B*X*A' before res .=): the
+  // second product's workgroups store res while other row blocks' first-product workgroups still read x. The two
+  // launches are alias-safe as they are — the first has read all of x before the second stores.
+  const bool res_x = ctx->tune.alias_guard && bytes_overlap(res, p * m * (int64_t)sizeof(T), x, q * n * (int64_t)sizeof(T));
+  if (ctx->tune.kron_fuse && !res_x && trans_a == trans_b && ctx->fault_dev && (!ctx->capturing || (ctx->xcd_map == 1 && ctx->kron_cnt_n > 0)) && m > 0 && n > 0 && p > 0 && q > 0 &&
       m < (1LL << 31) && n < (1LL << 31) && p < (1LL << 31) && q < (1LL << 31) && lda < (1LL << 22) && ldb < (1LL << 22) &&
       m < (1LL << 22) && q < (1LL << 22) && gemm_glds_ok<T>(A, lda, trans_a, x, q, m, q, n) &&
       gemm_glds_ok<T>(B, ldb, trans_b, work, m, p, m, q)) {
@@ -2142,6 +2146,8 @@ MXLO_API int32_t mxlo_hermitian_mul(mxlo_ctx *ctx, int32_t dtype, void *res, con
   MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "bad dtype");
   MXLO_REQUIRE(n >= 0 && lda >= (n > 1 ? n : 1), MXLO_ESHAPE, "mxlo_hermitian_mul: bad shape");
   MXLO_REQUIRE(n == 0 || (res && d && A && v), MXLO_EINVAL, "mxlo_hermitian_mul: NULL operand");
+  MXLO_TRY(stage_alias(ctx, res, n * (dtype == MXLO_F64 ? 8 : 4), &v, n * (dtype == MXLO_F64 ? 8 : 4), false,
+                       "mxlo_hermitian_mul"));   // every row reads all of v
   eff_ab(dtype, flags, alpha, beta);
   if (dtype == MXLO_F64)
     return hermitian_t<double>(ctx, (double *)res, (const double *)d, (const double *)A, lda, (const double *)v, n, alpha, beta, flags);

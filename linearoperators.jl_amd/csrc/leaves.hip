@@ -55,6 +55,8 @@ MXLO_API int32_t mxlo_diag_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const vo
                (long long)n_min, (long long)nrow);
   MXLO_REQUIRE(nrow == 0 || (res && (n_min == 0 || (d && v))), MXLO_EINVAL,
                "mxlo_diag_mul: NULL operand");
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4;
+  MXLO_TRY(stage_alias(ctx, res, nrow * es, &v, n_min * es, true, "mxlo_diag_mul"));
   alpha = eff_alpha(dtype, flags, alpha);
   beta = eff_beta(dtype, flags, beta);
   if (dtype == MXLO_F64)
@@ -93,6 +95,8 @@ MXLO_API int32_t mxlo_eye_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const voi
   MXLO_REQUIRE(n_min >= 0 && nrow >= n_min, MXLO_ESHAPE, "mxlo_eye_mul: n_min=%lld nrow=%lld",
                (long long)n_min, (long long)nrow);
   MXLO_REQUIRE(nrow == 0 || (res && (n_min == 0 || v)), MXLO_EINVAL, "mxlo_eye_mul: NULL operand");
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4;
+  MXLO_TRY(stage_alias(ctx, res, nrow * es, &v, n_min * es, true, "mxlo_eye_mul"));
   alpha = eff_alpha(dtype, flags, alpha);
   beta = eff_beta(dtype, flags, beta);
   if (dtype == MXLO_F64)
@@ -418,6 +422,8 @@ MXLO_API int32_t mxlo_householder_apply(mxlo_ctx *ctx, int32_t dtype, void *res,
   MXLO_DEVICE_GUARD(ctx);
   MXLO_REQUIRE(n >= 0 && dot_dev && (n == 0 || (res && h && v)), MXLO_EINVAL,
                "mxlo_householder_apply: bad argument");
+  MXLO_TRY(stage_alias(ctx, res, n * (dtype == MXLO_F64 ? 8 : 4), &v, n * (dtype == MXLO_F64 ? 8 : 4), true,
+                       "mxlo_householder_apply"));
   alpha = eff_alpha(dtype, flags, alpha);
   beta = eff_beta(dtype, flags, beta);
   if (dtype == MXLO_F64)
@@ -434,6 +440,8 @@ MXLO_API int32_t mxlo_householder_mul(mxlo_ctx *ctx, int32_t dtype, void *res, c
   MXLO_DEVICE_GUARD(ctx);
   MXLO_REQUIRE(n >= 0 && (n == 0 || (res && h && v)), MXLO_EINVAL,
                "mxlo_householder_mul: bad argument");
+  MXLO_TRY(stage_alias(ctx, res, n * (dtype == MXLO_F64 ? 8 : 4), &v, n * (dtype == MXLO_F64 ? 8 : 4), true,
+                       "mxlo_householder_mul"));
   alpha = eff_alpha(dtype, flags, alpha);
   beta = eff_beta(dtype, flags, beta);
   if (dtype == MXLO_F64)
@@ -692,6 +700,8 @@ MXLO_API int32_t mxlo_gather(mxlo_ctx *ctx, int32_t elem_size, void *res, const 
   MXLO_REQUIRE(nidx >= 0 && nv >= 0, MXLO_ESHAPE, "mxlo_gather: negative size");
   if (nidx == 0) return MXLO_OK;
   MXLO_REQUIRE(res && v && idx, MXLO_EINVAL, "mxlo_gather: NULL operand");
+  MXLO_REQUIRE(elem_size == 4 || elem_size == 8 || elem_size == 16, MXLO_EINVAL, "element size %d not in {4,8,16}", elem_size);
+  MXLO_TRY(stage_alias(ctx, res, nidx * elem_size, &v, nv * elem_size, false, "mxlo_gather"));
   return by_elem_size(elem_size, [&]<typename E>() -> int32_t {
     constexpr int KPT = sizeof(E) >= 16 ? 1 : 16 / (int)sizeof(E);
     const int grid = grid_for(ctx, (nidx + KPT - 1) / KPT, kBlock * 4, ctx->tune.blocks_per_cu);
@@ -717,6 +727,8 @@ MXLO_API int32_t mxlo_gather_range(mxlo_ctx *ctx, int32_t elem_size, void *res, 
   MXLO_REQUIRE(step != 0 && start >= 1 && start <= nv && last >= 1 && last <= nv, MXLO_ESHAPE,
                "mxlo_gather_range: %lld:%lld:%lld outside 1..%lld", (long long)start,
                (long long)step, (long long)last, (long long)nv);
+  MXLO_REQUIRE(elem_size == 4 || elem_size == 8 || elem_size == 16, MXLO_EINVAL, "element size %d not in {4,8,16}", elem_size);
+  MXLO_TRY(stage_alias(ctx, res, len * elem_size, &v, nv * elem_size, false, "mxlo_gather_range"));
   if (step == 1) {  // UnitRange: a contiguous copy through the streaming kernel (16-byte, nontemporal
                     // when large: ~1.8x the rate of hipMemcpyAsync D2D measured at 5e7 doubles);
                     // plain register moves, so every bit pattern (NaN payloads) survives
@@ -1002,6 +1014,8 @@ MXLO_API int32_t mxlo_gather_plan(mxlo_ctx *ctx, int32_t elem_size, void *res, c
   MXLO_REQUIRE(nv == plan->n, MXLO_ESHAPE, "mxlo_gather_plan: v has %lld elements, the plan was built for %lld", (long long)nv, (long long)plan->n);
   if (plan->nidx == 0) return MXLO_OK;
   MXLO_REQUIRE(res && v, MXLO_EINVAL, "mxlo_gather_plan: NULL operand");
+  MXLO_REQUIRE(elem_size == 4 || elem_size == 8 || elem_size == 16, MXLO_EINVAL, "element size %d not in {4,8,16}", elem_size);
+  MXLO_TRY(stage_alias(ctx, res, plan->nidx * elem_size, &v, nv * elem_size, false, "mxlo_gather_plan"));
   return by_elem_size(elem_size, [&]<typename E>() -> int32_t {
     constexpr int VEC = sizeof(E) >= 16 ? 1 : 16 / (int)sizeof(E);
     const int grid = grid_for(ctx, (nv + VEC - 1) / VEC, kBlock * 4, ctx->tune.blocks_per_cu);
@@ -1148,6 +1162,8 @@ MXLO_API int32_t mxlo_kron_diag_mul(mxlo_ctx *ctx, int32_t dtype, void *res, con
   MXLO_REQUIRE(m >= 0 && p >= 0, MXLO_ESHAPE, "mxlo_kron_diag_mul: negative size");
   if (m == 0 || p == 0) return MXLO_OK;
   MXLO_REQUIRE(res && x, MXLO_EINVAL, "mxlo_kron_diag_mul: NULL operand");
+  MXLO_TRY(stage_alias(ctx, res, m * p * (dtype == MXLO_F64 ? 8 : 4), &x, m * p * (dtype == MXLO_F64 ? 8 : 4), true,
+                       "mxlo_kron_diag_mul"));
   alpha = eff_alpha(dtype, flags, alpha);
   beta = eff_beta(dtype, flags, beta);
   if (dtype == MXLO_F64)

@@ -3103,6 +3103,8 @@ MXLO_API int32_t mxlo_qn_mul(mxlo_qn *h, void *res, const void *x, double alpha,
                              int32_t flags) {
   MXLO_REQUIRE(h && (h->n == 0 || (res && x)), MXLO_EINVAL, "mxlo_qn_mul: NULL argument");
   MXLO_DEVICE_GUARD(h->ctx);
+  const int64_t es = h->dtype == MXLO_F64 ? 8 : 4;   // every form reads x in passes that other lanes' stores can overtake
+  MXLO_TRY(stage_alias(h->ctx, res, h->n * es, &x, h->n * es, false, "mxlo_qn_mul"));
   note_capture(h);
   if (h->dtype == MXLO_F64) return qn_mul_t<double>(h, (double *)res, (const double *)x, alpha, beta, flags);
   return qn_mul_t<float>(h, (float *)res, (const float *)x, alpha, beta, flags);
@@ -3112,6 +3114,8 @@ MXLO_API int32_t mxlo_qn_mul_shifted(mxlo_qn *h, void *res, const void *x, doubl
                                      double sigma, int32_t flags) {
   MXLO_REQUIRE(h && (h->n == 0 || (res && x)), MXLO_EINVAL, "mxlo_qn_mul_shifted: NULL argument");
   MXLO_DEVICE_GUARD(h->ctx);
+  const int64_t es = h->dtype == MXLO_F64 ? 8 : 4;
+  MXLO_TRY(stage_alias(h->ctx, res, h->n * es, &x, h->n * es, false, "mxlo_qn_mul_shifted"));
   note_capture(h);
   // shifted_prod! (src/shifted_operators.jl:16-25): mul!(y, H, x, α, β); iszero(σ) || iszero(α) || axpy!(α*σ, x, y).
   // α*σ is formed in the callers' types (σ is a T; α a T or a Float64), then axpy! converts it to T.

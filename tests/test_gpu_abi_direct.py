@@ -154,3 +154,84 @@ def test_shard_stage_pack_unpack_bit_exact(lo, dev, n, world, dtype):
     assert torch.equal(back.view(torch.uint8) if dtype != torch.complex128 else torch.view_as_real(back),
                        full.view(torch.uint8) if dtype != torch.complex128 else torch.view_as_real(full))
     assert lo._lib.lib().mxlo_shard_stage(ctx.handle, es, ptr(back), ptr(wire), n, world, -1, 5) == lo._lib.EINVAL
+
+
+def test_aliased_res_and_v_through_raw_pointers(lo, dev):
+    """mul!(x, op, x) the way a foreign glue calls it: one device pointer passed as res and as v (include/mxlo.h: per entry
+    point, whether res may alias v or v is staged). mxlo_kron_mul on a square kron whose separate-buffer apply is the
+    one-launch form, and mxlo_gather_range reversing a vector in place (n:-1:1) and shifted by one element."""
+    L = lo._lib.lib()
+    ctx = lo.get_ctx(dev).handle
+    P = lambda t: C.c_void_p(t.data_ptr())
+    rng = np.random.default_rng(23)
+    for m in (64, 512):
+        A, B = rng.uniform(-1, 1, (m, m)), rng.uniform(-1, 1, (m, m))
+        dA, dB = (torch.from_numpy(np.asfortranarray(M).T.copy()).to(dev) for M in (A, B))   # column-major storage
+        work = torch.empty(m * m, dtype=torch.float64, device=dev)
+        for rep in range(3):
+            xh = rng.uniform(-1, 1, m * m)
+            for op_mode, tr in ((lo._lib.OP_N, False), (lo._lib.OP_T, True)):
+                for alpha, beta in ((1.0, 0.0), (0.75, -1.25)):
+                    sep, x = torch.from_numpy(xh.copy()).to(dev), torch.from_numpy(xh.copy()).to(dev)
+                    assert L.mxlo_kron_mul(ctx, lo._lib.F64, P(sep), P(dA), m, m, m, P(dB), m, m, m, P(x), P(work),
+                                           C.c_double(alpha), C.c_double(beta), op_mode, 0) == 0
+                    assert L.mxlo_kron_mul(ctx, lo._lib.F64, P(x), P(dA), m, m, m, P(dB), m, m, m, P(x), P(work),
+                                           C.c_double(alpha), C.c_double(beta), op_mode, 0) == 0
+                    torch.cuda.synchronize()
+                    assert torch.equal(x, sep), (m, op_mode, alpha)
+                    want = oracle.kron_mul(xh.copy(), A, B, xh, alpha, beta, trans=tr)
+                    assert np.linalg.norm(sep.cpu().numpy() - want) <= 1e-12 * np.linalg.norm(want)
+    n = 1_000_003
+    for es, dt in ((8, torch.float64), (4, torch.float32), (16, torch.complex128)):
+        for rep in range(3):
+            vh = rng.uniform(-1, 1, n).astype(np.float64)
+            v = torch.from_numpy(vh).to(dev).to(dt)
+            want = v.flip(0).clone()
+            x = v.clone()
+            assert L.mxlo_gather_range(ctx, es, P(x), P(x), n, n, -1, n) == 0          # res .= view(x, n:-1:1)
+            torch.cuda.synchronize()
+            assert torch.equal(x, want), (es, int((x != want).nonzero()[0]))
+            buf = torch.cat([v, v[:1]])                                                  # res = buf[1:], v = buf[:n]
+            assert L.mxlo_gather_range(ctx, es, C.c_void_p(buf.data_ptr() + es), P(buf), n, 1, 1, n) == 0
+            torch.cuda.synchronize()
+            assert torch.equal(buf[1:], v)
+
+
+def test_staging_buffer_cannot_grow_inside_a_graph_capture(lo, dev):
+    """An overlapping res / v inside a capture needs the ctx's staging buffer at its size: growing it there would
+    synchronise, so the call is MXLO_ESTATE and enqueues nothing. After one aliased call outside the capture the same
+    call captures (as a memcpy node + the gather) and the replay is right."""
+    L = lo._lib.lib()
+    ctx, s = C.c_void_p(), C.c_void_p()
+    assert L.mxlo_ctx_create(0, None, C.byref(ctx)) == 0
+    try:
+        assert L.mxlo_ctx_create_stream(ctx, C.byref(s)) == 0 and L.mxlo_ctx_set_stream(ctx, s) == 0
+        n = 100_000
+        vh = np.random.default_rng(4).uniform(-1, 1, n)
+        x = torch.from_numpy(vh).to(dev)
+        px = C.c_void_p(x.data_ptr())
+        torch.cuda.synchronize()
+        assert L.mxlo_graph_begin(ctx) == 0
+        assert L.mxlo_gather_range(ctx, 8, px, px, n, n, -1, n) == lo._lib.ESTATE
+        assert b"staging" in L.mxlo_last_error()
+        g = C.c_void_p()
+        L.mxlo_graph_end(ctx, C.byref(g))
+        if g:
+            assert L.mxlo_graph_destroy(g) == 0
+        assert L.mxlo_ctx_sync(ctx) == 0
+        assert np.array_equal(x.cpu().numpy(), vh)                                       # nothing ran
+        assert L.mxlo_gather_range(ctx, 8, px, px, n, n, -1, n) == 0 and L.mxlo_ctx_sync(ctx) == 0
+        assert np.array_equal(x.cpu().numpy(), vh[::-1])
+        assert L.mxlo_graph_begin(ctx) == 0
+        assert L.mxlo_gather_range(ctx, 8, px, px, n, n, -1, n) == 0
+        g = C.c_void_p()
+        assert L.mxlo_graph_end(ctx, C.byref(g)) == 0
+        try:
+            x.copy_(torch.from_numpy(vh).to(dev))
+            torch.cuda.synchronize()
+            assert L.mxlo_graph_launch(g) == 0 and L.mxlo_ctx_sync(ctx) == 0
+            assert np.array_equal(x.cpu().numpy(), vh[::-1])
+        finally:
+            L.mxlo_graph_destroy(g)
+    finally:
+        assert L.mxlo_ctx_destroy(ctx) == 0

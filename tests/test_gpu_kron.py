@@ -488,3 +488,145 @@ def test_one_launch_kron_timeout_is_an_error_not_a_hang(lo, dev):
         ctx.tune("fused_timeout_ms", 2000)
         for key in ("kron_fuse", "house_fused", "qn_fused_small", "qn_persist", "herm_single"):
             ctx.tune(key, 1)
+
+
+# ---- the one-launch form: where it runs, and its edge shapes ------------------------------------------------------------
+def _launches(lo):
+    import ctypes as C
+    a = (C.c_int64 * 12)()
+    lo._lib.call("mxlo_debug_counters", a)
+    return a[10]
+
+
+def _kron_launches(lo, res, K, x, *ab):
+    """kernel launches of one (warmed) apply"""
+    lo.mul(res, K, x, *ab)
+    l0 = _launches(lo)
+    lo.mul(res, K, x, *ab)
+    return _launches(lo) - l0
+
+
+def _one_launch_canary(lo, dev):
+    """512^2 f64 with kron_fuse = 1: True when the one-time XCD-map probe (dense.hip: xcd_map_ok) accepted this device."""
+    rng = np.random.default_rng(1)
+    K = lo.kron(colmajor(rng.uniform(-1, 1, (512, 512)), dev), colmajor(rng.uniform(-1, 1, (512, 512)), dev))
+    x = T(rng.uniform(-1, 1, 512 * 512), dev)
+    return _kron_launches(lo, torch.empty_like(x), K, x) == 1
+
+
+def _fused_gate(shape, dtype, num_cu):
+    """kron_t's one-launch gate (dense.hip) restated for kron(A, B) * x with column-major A (m x n), B (p x q), no
+    transposition, 16-byte aligned device buffers: the DMA preconditions of both GEMMs, one tile class below 128 for
+    both products (tile_of), every tile on its own CU (grid <= num_cu), at most 64 row blocks."""
+    (m, n), (p, q) = shape
+    vec = 16 // (8 if dtype == torch.float64 else 4)
+    if min(m, q, p) < vec or m % vec or q % vec or p % vec:
+        return False
+
+    def tile_of(M, N):
+        tiles = lambda t: -(-M // t) * -(-N // t)
+        if tiles(128) >= num_cu:
+            return 128
+        return 64 if tiles(64) * 5 >= num_cu * 3 else 32
+    t1, t2 = tile_of(m, q), tile_of(p, m)
+    if t1 != t2 or t1 == 128:
+        return False
+    nrb, gy1, gx2 = -(-m // t1), -(-q // t1), -(-p // t1)
+    grid = 8 * (-(-nrb // 8) * max(gy1, gx2))
+    return grid <= num_cu and nrb <= 64
+
+
+GATE_SHAPES = [((64, 64), (64, 64)), ((128, 96), (200, 160)), ((256, 256), (256, 256)), ((300, 260), (180, 340)),
+               ((512, 512), (512, 512)), ((1024, 1024), (1024, 1024)), ((520, 1000), (1000, 520)),
+               ((264, 512), (512, 512)), ((20, 512), (512, 512))]
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_kron_one_launch_form_runs_wherever_the_gate_admits_it(lo, dev, dtype):
+    """The bit-identity test above compares kron_fuse 0 with 1 and would pass with nothing checked if the one-launch form
+    never ran. Here the launches are counted: one wherever the gate admits the shape, two with kron_fuse = 0 and two for
+    an aliased call (res == x), which must leave the one-launch form."""
+    if not _one_launch_canary(lo, dev):
+        pytest.skip("the XCD-map probe (dense.hip: xcd_map_ok) rejected this device: kron never runs as one launch here")
+    ctx = lo.get_ctx(dev)
+    num_cu = ctx.info()["num_cu"]
+    npd = NP[dtype]
+    admitted = 0
+    try:
+        for shape in GATE_SHAPES:
+            (am, an), (bp, bq) = shape
+            rng = np.random.default_rng(am * bq)
+            K = lo.kron(colmajor(rng.uniform(-1, 1, (am, an)).astype(npd), dev), colmajor(rng.uniform(-1, 1, (bp, bq)).astype(npd), dev))
+            x = T(rng.uniform(-1, 1, an * bq).astype(npd), dev)
+            res = torch.empty(am * bp, dtype=dtype, device=dev)
+            gate = _fused_gate(shape, dtype, num_cu)
+            admitted += gate
+            ctx.tune("kron_fuse", 1)
+            got = _kron_launches(lo, res, K, x)
+            assert got == 1 if gate else got >= 2, (shape, gate, got)
+            if gate:
+                assert _kron_launches(lo, res, K, x, 0.75, -1.25) == 1, shape
+                ctx.tune("kron_fuse", 0)
+                assert _kron_launches(lo, res, K, x) == 2, shape
+                ctx.tune("kron_fuse", 1)
+                if am * bp == an * bq:                                # square: mul!(x, K, x)
+                    l0 = _launches(lo)
+                    lo.mul(x, K, x)
+                    assert _launches(lo) - l0 == 2, shape
+    finally:
+        ctx.tune("kron_fuse", 1)
+    assert admitted >= 4
+
+
+@pytest.mark.parametrize("dtype,tol", [(torch.float64, 1e-12), (torch.float32, 3e-5)])
+@pytest.mark.parametrize("shape", [((264, 512), (512, 512)), ((20, 512), (512, 512)), ((20, 64), (64, 20))])
+def test_kron_one_launch_form_on_row_blocks_that_share_a_cache_line(lo, dev, dtype, tol, shape):
+    """m * sizeof(T) % 128 != 0: a 128-byte line of Ut straddles two row blocks — with nrb = 9 (== 1 mod 8) the last row
+    block of one column and block 0 of the next sit on the same XCD — and m = 20, a single row block. Every element is
+    checked against the oracle and against the two-launch bits, with fresh x three times."""
+    (am, an), (bp, bq) = shape
+    npd = NP[dtype]
+    ctx = lo.get_ctx(dev)
+    rng = np.random.default_rng(am + bp)
+    A, B = rng.uniform(-1, 1, (am, an)).astype(npd), rng.uniform(-1, 1, (bp, bq)).astype(npd)
+    K = lo.kron(colmajor(A, dev), colmajor(B, dev))
+    try:
+        for rep in range(3):
+            xh = rng.uniform(-1, 1, an * bq).astype(npd)
+            x = T(xh, dev)
+            got = {}
+            for fuse in (1, 0):
+                ctx.tune("kron_fuse", fuse)
+                got[fuse] = torch.full((am * bp,), float("nan"), dtype=dtype, device=dev)
+                lo.mul(got[fuse], K, x)
+            ctx.tune("kron_fuse", 1)
+            assert torch.equal(got[1], got[0]), (rep, int((got[1] != got[0]).nonzero()[0]))
+            want = oracle.kron_mul(np.empty(am * bp), A.astype(np.float64), B.astype(np.float64), xh.astype(np.float64), 1.0, 0.0)
+            err = np.abs(got[1].cpu().numpy().astype(np.float64) - want) / (np.abs(want) + np.abs(want).max() * 1e-3)
+            assert err.max() <= tol * 100, (rep, int(err.argmax()), float(err.max()))
+            assert rel(got[1].cpu().numpy(), want) <= tol
+    finally:
+        ctx.tune("kron_fuse", 1)
+
+
+def test_kron_after_the_no_wait_mode_matches_the_oracle(lo, dev):
+    """kron_fuse = 2 (timing experiment, documented wrong results) can leave the row-block counters non-zero; setting
+    kron_fuse back to 1 re-arms them, so the next apply is right again."""
+    ctx = lo.get_ctx(dev)
+    rng = np.random.default_rng(3)
+    A, B = rng.uniform(-1, 1, (512, 512)), rng.uniform(-1, 1, (512, 512))
+    K = lo.kron(colmajor(A, dev), colmajor(B, dev))
+    xh = rng.uniform(-1, 1, 512 * 512)
+    x, res = T(xh, dev), torch.empty(512 * 512, dtype=torch.float64, device=dev)
+    want = oracle.kron_mul(np.empty(512 * 512), A, B, xh, 1.0, 0.0)
+    try:
+        ctx.tune("kron_fuse", 2)
+        for _ in range(3):
+            lo.mul(res, K, x)
+        torch.cuda.synchronize()
+    finally:
+        ctx.tune("kron_fuse", 1)
+    for _ in range(3):
+        res.fill_(float("nan"))
+        lo.mul(res, K, x)
+        assert rel(res.cpu().numpy(), want) <= 1e-12
