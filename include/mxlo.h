@@ -457,7 +457,9 @@ int32_t mxlo_kron_mul_c(mxlo_ctx *ctx, int32_t dtype, void *res, const void *Ar,
  *   (a + ib)(c + id):  k1 = (a + b) c,  k2 = a (d - c),  k3 = b (c + d);  re = k1 - k3,  im = k1 + k2.
  * Same arguments and semantics as mxlo_kron_mul_c (a real factor still costs its two plain GEMMs); results agree with
  * it to rounding (normwise: the three-multiplication form is not componentwise stable, which the reference's
- * 1e-12 * ||K||_1 criterion, test/test_kron.jl:35, does not ask for). As / Bs: the factor-sum planes a + s*b of A / B
+ * 1e-12 * ||K||_1 criterion, test/test_kron.jl:35, does not ask for). Non-finite operands: mxlo_kron_mul_c puts NaN, +Inf
+ * and -Inf where the reference puts them; this form does so for NaN operands, but with an Inf in x its re / im are
+ * differences of Inf products: non-finite wherever the reference is, NaN where it may hold +-Inf and the reverse. As / Bs: the factor-sum planes a + s*b of A / B
  * (s = -1 when bit 1 of the factor's mode conjugates it, else +1; CONTIGUOUS, leading dimension = rows; form them with
  * mxlo_plane_sum) as the glue caches them per factor state and sign — or NULL: formed per call in `work` (the library
  * keeps no factor state). `work` must be 16-byte aligned and hold mxlo_kron_c3_work_size(am, an, mode_a, bp, bq, mode_b)
@@ -646,7 +648,10 @@ int32_t mxlo_qn_reset(mxlo_qn *h);
 int32_t mxlo_qn_get_scalars(mxlo_qn *h, double scalars[5], double *ys, double *aux);
 /* Device pointer of one panel column, k 0-based: which = 0:s 1:y 2:a 3:b. */
 int32_t mxlo_qn_column(mxlo_qn *h, int32_t which, int64_t k, void **out);
-/* Evaluation strategy for the inverse two-loop (MXLO_INV_*). */
+/* Evaluation strategy for the inverse two-loop (MXLO_INV_*). Non-finite operands: MXLO_INV_REFORDER (and, below,
+ * MXLO_PUSH_REFORDER) put NaN, +Inf and -Inf where the reference's recursion puts them; MXLO_INV_TWOPASS and the
+ * MXLO_PUSH_GRAM / MXLO_PUSH_COMPACT forms are non-finite wherever the reference is, but may hold NaN where it holds
+ * +-Inf and the reverse (their coefficients come from Gram matrices). A NaN in x gives all NaN in every form. */
 int32_t mxlo_qn_set_mode(mxlo_qn *h, int32_t mode);
 /* Forward L-BFGS push!: how the a_k panel is rebuilt (src/lbfgs.jl:236-250).
  *   MXLO_PUSH_GRAM     (default) coefficient-space recurrence on the Gram matrices S'S, Y'S kept up

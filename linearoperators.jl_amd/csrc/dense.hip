@@ -1194,6 +1194,7 @@ herm_strip_body(const T *__restrict__ A, int64_t lda, const T *__restrict__ v, i
     slot = (int64_t)qint * G + t % DT;
   }
   const int64_t i0 = G * HR;
+  const bool diag_tile = DSEL || (EDGE && mode == 2);             // the tile straddles the diagonal
   const int tid = threadIdx.x, lane = tid & 63, rp = tid & 127;   // rows RPL*rp .. RPL*rp+RPL-1 of the row group
   const int cg = __builtin_amdgcn_readfirstlane(tid >> 7);          // columns cg + 2k, k < 16, of each tile
   const int half = __builtin_amdgcn_readfirstlane((tid >> 6) & 1);  // which 64*RPL rows this wave covers
@@ -1267,13 +1268,29 @@ herm_strip_body(const T *__restrict__ A, int64_t lda, const T *__restrict__ v, i
       const int64_t ca = j0 + cg + 2 * q, cb = ca + 16;
       const double vca = (!EDGE || ca < n) ? (double)vk[ca] : 0.0, vcb = (!EDGE || cb < n) ? (double)vk[cb] : 0.0;
       double pa = 0.0, pb = 0.0;
+      int below = 0;                            // row - column of this lane's element (r = 0) of column k = 0 of the tile
+      if constexpr (DSEL || (EDGE && C == 1)) {   // (the masked diagonal tiles are C = 1 bodies)
+        below = (int)(gr - (j0 + cg));
+        // (opaque to the optimiser: shared with load_tile's compares, the 16 x RPL lane masks of the tile are computed once
+        //  and stay live across it, which costs registers; tools/kernel_resources.py shows the counts of a build)
+        asm volatile("" : "+v"(below));
+      }
 #pragma unroll
       for (int r = 0; r < RPL; ++r) {
         const double a = (double)e[q][r], b = (double)e[q + 8][r];
-        prow[kk][r] = fma(a, vca, prow[kk][r]);
-        prow[kk][r] = fma(b, vcb, prow[kk][r]);
-        pa = r == 0 ? a * vr[kk][0] : fma(a, vr[kk][r], pa);
-        pb = r == 0 ? b * vr[kk][0] : fma(b, vr[kk][r], pb);
+        double va = vca, vb = vcb, ra = vr[kk][r], rb = vr[kk][r];
+        if constexpr (DSEL || (EDGE && C == 1)) {   // (the masked diagonal tiles are C = 1 bodies)
+          // A tile of a diagonal block: an element at or above the diagonal takes no part — its (zeroed) value must not
+          // meet v either, or an Inf / NaN in v would come back as 0 * Inf = NaN in rows the triangle never touches. The
+          // vector operands of those products are zeroed too: 0 * 0 adds nothing, finite results keep their bits.
+          const bool ka = !diag_tile || below + r > 2 * q, kb = !diag_tile || below + r > 2 * (q + 8);
+          va = ka ? vca : 0.0, ra = ka ? ra : 0.0;
+          vb = kb ? vcb : 0.0, rb = kb ? rb : 0.0;
+        }
+        prow[kk][r] = fma(a, va, prow[kk][r]);
+        prow[kk][r] = fma(b, vb, prow[kk][r]);
+        pa = r == 0 ? a * ra : fma(a, ra, pa);
+        pb = r == 0 ? b * rb : fma(b, rb, pb);
       }
       w8[q] = halve_step32(pa, pb);           // lanes < 32: column q, rows of lanes l and l + 32; lanes >= 32: column q + 8
       __builtin_amdgcn_sched_barrier(0);

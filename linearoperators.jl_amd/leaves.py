@@ -983,7 +983,9 @@ def _kron_complex(A, B, fA, fB, T, complex_form=None):
     pA, pB = Planes(fA), Planes(fB)
     # Gauss form (3 real GEMMs per complex product, `mxlo_kron_mul_c3`, normwise stable) by default; the 4-GEMM form
     # (`mxlo_kron_mul_c`, componentwise) by `complex_form="4gemm"` or MXLO_KRON_GAUSS=0 — the tests use it as the
-    # independent device implementation. The workspace covers the forward and the transposed shapes of both forms.
+    # independent device implementation. Non-finite operands: the 4-GEMM form keeps the reference's positions of NaN / ±Inf;
+    # the Gauss form is non-finite wherever the reference is, not necessarily of the same kind.
+    # The workspace covers the forward and the transposed shapes of both forms.
     if complex_form is None:
         complex_form = "gauss" if os.environ.get("MXLO_KRON_GAUSS", "1") != "0" else "4gemm"
     if complex_form not in ("gauss", "4gemm"):
