@@ -666,6 +666,34 @@ int32_t mxlo_qn_set_mode(mxlo_qn *h, int32_t mode);
 #define MXLO_PUSH_COMPACT 2
 int32_t mxlo_qn_set_push_mode(mxlo_qn *h, int32_t mode);
 
+/* ======================================================================== */
+/*  Krylov building blocks (estimate_opnorm)                                 */
+/* ======================================================================== */
+/* estimate_opnorm — declared at src/utilities.jl:319, implemented by ext/LinearOperatorsOpNormExt.jl:39-136 with ARPACK's
+ * eigs / svds. What those spend between two operator applies (dsaitr's Gram–Schmidt of the new Lanczos vector against the
+ * basis with one DGKS re-orthogonalisation, and the Ritz-vector combination at a restart) are these two calls; the
+ * operator applies are the ordinary mul!. Real f32 / f64 only. Both are stream-ordered on the ctx stream: kernel
+ * launches and nothing else (no allocation, no copy, no synchronisation), f64 accumulators also for f32 data, fixed-order
+ * partial sums (bit-reproducible). Row-sharded bases are not supported: with an all-reduce hook installed on the ctx
+ * both return MXLO_ESTATE (the hook is never called).
+ *
+ * mxlo_krylov_orth: V is n x k column-major with orthonormal columns (ldv >= n, 1 <= k <= 128), w has n elements and
+ * must not overlap them — normally it is column k of the same allocation, V + k*ldv; any 16-byte phase and any n work
+ * (16-byte accesses need ldv to be a multiple of 16 bytes). Classical Gram–Schmidt, twice:
+ *     h = V'w;  w -= V h;      h2 = V'w;  w -= V h2;      beta = |w|;  w ./= beta
+ * coef (device, k + 1 doubles): coef[0..k) = h + h2, coef[k] = beta (before the division). beta == 0 or not finite: w
+ * is left undivided — a breakdown is the caller's decision. MXLO_KRYLOV_DGKS: the second round is skipped when
+ * |w after the first| >= |w before it| / sqrt(2); the test is evaluated on the device and read by the second round's
+ * kernels there (the host never sees it). */
+#define MXLO_KRYLOV_DGKS 0x1
+int32_t mxlo_krylov_orth(mxlo_ctx *ctx, int32_t dtype, const void *V, int64_t ldv, int64_t n, int32_t k, void *w,
+                         double *coef, int32_t flags);
+/* out = V[:, 0..k) * y with y k device doubles (the Ritz vector of an explicit restart), then out ./= |out|;
+ * coef[0] (device) = |out| before the division (0 or not finite: undivided). ONE pass over the basis. out may be a
+ * column of V — column 0 when the restart vector overwrites the basis —; any other overlap is MXLO_EINVAL. */
+int32_t mxlo_krylov_combine(mxlo_ctx *ctx, int32_t dtype, const void *V, int64_t ldv, int64_t n, int32_t k,
+                            const double *y_dev, void *out, double *coef);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,7 @@ except ImportError:  # pragma: no cover - during bring-up only
 from .diagqn import DiagonalAndrei, DiagonalBFGS, DiagonalPSB, SpectralGradient
 from .graph import CapturedSequence, capture_mul
 from .utilities import check_ctranspose, check_hermitian, check_positive_definite, normest
+from .opnorm import estimate_opnorm
 
 try:
     from . import sharded

@@ -32,6 +32,7 @@ BLK_DIAG, BLK_DENSE, BLK_EYE, BLK_ZEROS, BLK_CSC = 0, 1, 2, 3, 4
 QN_LBFGS_INV, QN_LBFGS_FWD, QN_LSR1 = 0, 1, 2
 INV_TWOPASS, INV_REFORDER = 0, 1
 PUSH_GRAM, PUSH_REFORDER, PUSH_COMPACT = 0, 1, 2
+KRYLOV_DGKS = 0x1
 DQN_PSB, DQN_ANDREI, DQN_BFGS, DQN_SPECTRAL = 0, 1, 2, 3
 
 
@@ -173,6 +174,8 @@ _PROTOS = {
     "mxlo_qn_column": [_vp, _i32, _i64, C.POINTER(_vp)],
     "mxlo_qn_set_mode": [_vp, _i32],
     "mxlo_qn_set_push_mode": [_vp, _i32],
+    "mxlo_krylov_orth": [_vp, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _i32],
+    "mxlo_krylov_combine": [_vp, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp],
 }
 
 

@@ -388,6 +388,34 @@ __device__ __forceinline__ double wave_allsum(double v) {
 #endif
 }
 
+// Sum over the wave in LANE 0 (other lanes: unspecified), on the tree of the shuffle-down loop this replaces —
+//   v[l] += v[l + 32]; v[l] += v[l + 16]; ... ; v[l] += v[l + 1]
+// — so every reduction of the library keeps its bits. A 64-bit __shfl_down is two ds_bpermute_b32 with an LDS round trip
+// each and six dependent levels per sum: the 2 NC + 4 sums at the end of a push pass cost 1.8 us (5 columns) to 5.5 us (20)
+// at launch-bound sizes. Here the upper half arrives with v_permlane32_swap, the odd rows with v_permlane16_swap (gfx950),
+// the rest with DPP row shifts: register-speed VALU work that independent sums overlap freely.
+__device__ __forceinline__ double wave_sum(double v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    const auto slo = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);   // [1]: lanes 0..31 hold lanes 32..63
+    const auto shi = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    v += __hiloint2double((int)shi[1], (int)slo[1]);
+  }
+  {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    const auto slo = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);   // [1]: rows 0, 2 hold rows 1, 3
+    const auto shi = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    v += __hiloint2double((int)shi[1], (int)slo[1]);
+  }
+  v += dpp_shift_or_zero<0x108, 0xf>(v);   // row_shl:8: lane l reads lane l + 8 of its row
+  v += dpp_shift_or_zero<0x104, 0xf>(v);   // row_shl:4
+  v += dpp_shift_or_zero<0x102, 0xf>(v);   // row_shl:2
+  v += dpp_shift_or_zero<0x101, 0xf>(v);   // row_shl:1
+#endif
+  return v;
+}
+
 // ---- halving butterfly steps without LDS ---------------------------------------------------------------------------
 // One step of a halving reduction over the lanes: every lane holds TWO partial sums x, y; lanes whose bit B is clear keep
 // x and hand y to lane l ^ B, the others keep y and hand x over — afterwards each lane holds ONE sum over twice the lanes:
