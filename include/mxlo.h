@@ -128,10 +128,78 @@ int32_t mxlo_ctx_set_stream(mxlo_ctx *ctx, void *stream);
 int32_t mxlo_ctx_sync(mxlo_ctx *ctx);
 /* info[0]=device id, [1]=CU count, [2]=workspace bytes, [3]=max reduction columns */
 int32_t mxlo_ctx_info(mxlo_ctx *ctx, int64_t info[4]);
-/* Launch-geometry / algorithm-variant knobs for sweeps and for tests that compare two device implementations. Keys:
- * "blocks_per_cu", "nt_min_bytes", "red_blocks_per_cu", "graph_direct_max", "house_fused", "house_reverse", "house_inline_n" (two-pass opHouseholder up to this n: the update pass adds up the dots pass's partial sums itself, no finalize launch; 0: never),
- * "cherm_two_pass", "lbfgs_inv_mode", "gemm_tile", "extend_tiles_per_block", "fuse_finalize", "combine_blocks_per_cu",
- * "dots_max_nc", "sp_xcds" (sparse apply: number of L2 domains the chunk order is banded over — 8 = one contiguous part of the chunk table per XCD of an MI355X; default 1 = plain order), "fused_timeout_ms", "fused_debug_drop" (both below), "qn_fused_small" (1: dots + finalize + coefficients of a small quasi-Newton apply in one launch), "qn_fused_max_grid" (most workgroups of that launch, 1..256, default 256: vectors up to 2^19 doubles with 4 vectors per lane; 64 was the round-3 limit), "qn_fused_batch12" (1: with 9 .. 12 panel columns on a short vector that launch takes all columns in one batch — one memory round trip less in each of its two phases), "push_wide", "push_posted" (1: push!'s few doubles of decision state are posted into mapped pinned host memory of the handle by a one-wave kernel and the host polls a sequence word behind them — falling back to a stream synchronisation after 200 us of polling, and to a plain copy from device memory (posting off for that handle from then on) should the posted words not be there after it; 0: hipMemcpyAsync + hipStreamSynchronize; 2: debug — every posting is treated as lost), "qn_persist" (1, default: a quasi-Newton apply at cache-resident sizes — n >= "qn_persist_min_n" (2^19), "qn_persist_min_bytes" (32 MiB) <= panel bytes <= "qn_persist_max_bytes" (448 MiB) — is ONE persistent launch: one 512-thread workgroup per CU owning a contiguous run of the vectors, dots -> grid exchange -> coefficients -> combine; "qn_persist_reverse" (1): its combine phase walks back to front; "qn_persist_prefetch" (0; measured slower at n <= 2^20): x and the first column batch of the first combine chunk are requested before the exchange; "qn_persist_lds" (1, default; round 6): the dots phase parks x of every chunk and the first columns of the combine order in the CU's LDS (18 tiles of 8 KiB) and the combine phase reads them from there — bit-identical to 0; "qn_persist_lds_pad": bytes of unused dynamic LDS per workgroup (a placement experiment, default 0)), "herm_order" (interior strips of opHermitian walked 0: row group by row group, 1: column block by column block — same partial layout, same results), "herm_nt" (-1, default: the strip loads of opHermitian carry the nontemporal hint except for triangles of "herm_dp_min_bytes" (96 MiB) <= bytes < "herm_nt_min_bytes" (384 MiB) — about the size of the Infinity Cache, where the next apply finds part of a default-policy stream still cached; 0 / 1: never / always nontemporal), "house_fused_per_cu" (2, default; round 6: the single-launch Householder may use two co-resident workgroups per CU — vectors up to 2^22 doubles keep their slices of h and v in registers, 24 instead of 40 B/elt; 1: one per CU, up to 2^21), "herm_poll_sleep" (4: the finishers of the single-launch opHermitian look at their last partials every 64 x this many clocks while the strips stream), "herm_strip" (0, default: tiles per strip of opHermitian by size; 1 / 2 / 8 force it — a sweep knob, results do not depend on it beyond rounding of the row partials' grouping), "herm_lds_pad" (0; occupancy experiment: bytes of unused dynamic LDS per workgroup of the opHermitian pass launch, 0..49152), "herm_single" (1, default: opHermitian on full row groups of an aligned matrix whose strict lower triangle has at most "herm_single_max_bytes" (112 MiB: f64 n <= 5120, f32 n <= 7424; "herm_single_max_n" > 0 replaces the rule by n <= that value) is ONE launch — strip workgroups publish their partial sums as self-validating slots, finisher workgroups of the same launch wait for the slots of their rows, add them in the order of the separate finish launch (bit-identical) and re-arm them), "gemv_n_rows" (1, default: dense M*v on an aligned matrix with >= 8 x 16 B of rows per CU runs as ONE launch of row bands — a workgroup owns 16 ... 128 rows across all columns, the column sum never leaves it; 0: the two-launch column-chunk schedule; 8/16/32 x (16 / sizeof(T)): that band height, for sweeps), "kron_fuse" (1, default: both GEMMs of a kron apply whose tiles fit one per CU run in ONE launch — a row block of the first product is produced and consumed by workgroups of one XCD, published through a counter in that XCD's L2, no device-wide barrier; bounded wait + fault word like every single-launch form; 0: two launches; 2: timing experiment without the wait, wrong results — entering or leaving 2 re-arms the row-block counters), "alias_guard" (1, default: res overlapping v is staged or leaves the one-launch kron, see Conventions; 0: TEST HOOK, overlapping operands reach the kernels unguarded), "gemvb_n_rows" (1, default: the block apply M*V of a dense operator runs where M*v takes its 512- / 256-byte row bands as ONE launch of those bands with the block of vectors staged in LDS once per workgroup — no partial workspace, every column bit-identical to M*v on that column; 0: the column-chunk schedule + finish launch), "gemvb_t_lds" (1, default: the transposed block apply of a dense operator with >= 4 columns stages the block of vectors in LDS once per workgroup), "combine_reverse" (0, default: the combine pass of a four-launch apply walks front to back; 1 measured no gain), "push_fused" (1: streaming push! schedules — L-BFGS: new pair held per lane, in-pass inserts; L-SR1: panels once, y - B s never stored, inserts ride in the rebuild; 0: the copies + dots schedules they replaced). Unknown key or out-of-range value -> MXLO_EINVAL.
+/* Launch-geometry / algorithm-variant knobs for sweeps and for tests that compare two device implementations.
+ * mxlo_ctx_tune sets one, mxlo_ctx_tune_get reads it back (set, run, restore what was there), and mxlo_tune_key
+ * enumerates them: index 0, 1, ... until it returns MXLO_EINVAL; it needs no ctx and no GPU; any out-pointer may be
+ * NULL. An unknown key or a value that is not accepted -> MXLO_EINVAL, the value left as it was. `lo` .. `hi` is the
+ * accepted range; for the keys that accept a list of values it is the smallest and largest of them, and for
+ * "red_blocks_per_cu" `hi` is the static bound (a ctx accepts value x its CU count <= that bound).
+ * The keys, as  "key" (default; accepted values): what it selects
+ *  streaming kernels and reductions
+ *   "blocks_per_cu" (0; 0..64): 0 = one chunk per workgroup, k = a persistent grid of k workgroups per CU
+ *   "nt_min_bytes" (256 MiB; >= 0): streamed footprint from which nontemporal accesses are used
+ *   "red_blocks_per_cu" (4; >= 1): workgroups per CU of the reduction kernels
+ *   "fuse_finalize" (1; 0/1): reductions of <= 4 columns are finalized by the last-arriving workgroup of the dots kernel
+ *   "dots_max_nc" (20; 1..20): columns per dots launch
+ *   "extend_tiles_per_block" (0; 0..1024): sorted extension, consecutive output tiles per workgroup (0 = auto)
+ *   "graph_direct_max" (16; 0..4096): captured chains of at most this many nodes replay as direct launches (0: never)
+ *   "alias_guard" (1; 0/1): res overlapping v is staged or leaves the one-launch kron, see Conventions; 0: TEST HOOK,
+ *     overlapping operands reach the kernels unguarded
+ *  opHouseholder
+ *   "house_fused" (1; any value, stored as value != 0): the single-launch form (dot, grid exchange, update)
+ *   "house_fused_per_cu" (2; 1..2): workgroups per CU that launch may use: 2 takes vectors up to 2^22 doubles, 1 up to 2^21
+ *   "house_reverse" (1; any value, stored as value != 0): the update phase walks the vectors back to front
+ *   "house_inline_n" (2^23; >= 0): two-pass form up to this n: the update pass adds up the dots pass's partial sums
+ *     itself, no finalize launch (0: never)
+ *  quasi-Newton operators
+ *   "lbfgs_inv_mode" (MXLO_INV_TWOPASS; or MXLO_INV_REFORDER): schedule of the inverse L-BFGS apply
+ *   "combine_blocks_per_cu" (0; 0..64): combine pass, 0 = one vector per thread, k = persistent grid
+ *   "combine_reverse" (0; 0/1): the combine pass of a four-launch apply walks back to front (measured: no gain)
+ *   "qn_fused_small" (1; 0/1): dots + finalize + coefficients of a small apply in one launch
+ *   "qn_fused_max_grid" (256; 1..256): most workgroups of that launch (256: vectors up to 2^19 doubles)
+ *   "qn_fused_batch12" (1; 0/1): with 9 .. 12 panel columns on a short vector that launch takes all columns in one batch
+ *   "qn_persist" (1; 0/1): an apply at cache-resident sizes is ONE persistent launch, one 512-thread workgroup per CU
+ *     owning a contiguous run of the vectors: dots -> grid exchange -> coefficients -> combine
+ *   "qn_persist_min_n" (2^19; >= 1), "qn_persist_min_bytes" (32 MiB; >= 0), "qn_persist_max_bytes" (448 MiB; >= 0):
+ *     ... for n and panel bytes within these limits
+ *   "qn_persist_reverse" (1; 0/1): ... its combine phase walks back to front
+ *   "qn_persist_prefetch" (0; 0/1): ... x and the first column batch of the first combine chunk are requested before
+ *     the exchange (measured slower at n <= 2^20)
+ *   "qn_persist_lds" (1; 0/1): ... the dots phase parks x and the first columns of the combine order in the CU's LDS;
+ *     bit-identical to 0
+ *   "qn_persist_lds_pad" (0; 0..114688): ... bytes of unused dynamic LDS per workgroup (placement experiment)
+ *   "push_fused" (1; 0/1): streaming push! schedules; 0: the copies + dots schedules they replaced
+ *   "push_wide" (1; 0/1): one-pass push! takes 20 columns per pass while >= 20 remain (0: always <= 10)
+ *   "push_posted" (1; 0..2): push!'s few doubles of decision state are posted into mapped pinned host memory by a
+ *     one-wave kernel and polled by the host (falling back to a stream synchronisation, then to a plain copy);
+ *     0: hipMemcpyAsync + hipStreamSynchronize; 2: debug, every posting is treated as lost
+ *  dense operators, opHermitian, kron, sparse
+ *   "gemv_n_rows" (1; 0..128): dense M*v as ONE launch of row bands, the column sum never leaves a workgroup; 0: the
+ *     two-launch column-chunk schedule; 8/16/32 x (16 / sizeof(T)): that band height, for sweeps
+ *   "gemvb_n_rows" (1; 0/1): the block apply M*V as one launch of those bands, V staged in LDS once per workgroup,
+ *     every column bit-identical to M*v on it; 0: the column-chunk schedule + finish launch
+ *   "gemvb_t_lds" (1; 0/1): the transposed block apply with >= 4 columns stages the block in LDS once per workgroup
+ *   "herm_single" (1; 0/1): opHermitian on full row groups of an aligned matrix is ONE launch: strip workgroups publish
+ *     partial sums as self-validating slots, finishers of the same launch add them in the order of the separate
+ *     finish launch (bit-identical)
+ *   "herm_single_max_bytes" (112 MiB; >= 0), "herm_single_max_n" (0; >= 0): ... for strict lower triangles of at most
+ *     that many bytes (f64 n <= 5120, f32 n <= 7424); a max_n > 0 replaces the rule by n <= max_n
+ *   "herm_poll_sleep" (4; 1..1024): ... its finishers look at their last partials every 64 x this many clocks
+ *   "herm_order" (1; 0/1): interior strips walked 0: row group by row group, 1: column block by column block; same results
+ *   "herm_strip" (0; 0, 1, 2, 8): tiles per strip, 0 = by size; results differ only by the grouping of the row partials
+ *   "herm_nt" (-1; -1..1): -1: strip loads are nontemporal except for triangles of "herm_dp_min_bytes" (96 MiB; >= 0)
+ *     <= bytes < "herm_nt_min_bytes" (384 MiB; >= 0), about the size of the Infinity Cache; 0 / 1: never / always
+ *   "herm_lds_pad" (0; 0..49152): bytes of unused dynamic LDS per workgroup of the pass launch (occupancy experiment)
+ *   "cherm_two_pass" (0; any value, stored as value != 0): complex opHermitian in the two-pass (rows, then columns) form
+ *   "kron_fuse" (1; 0..2): both GEMMs of a kron apply whose tiles fit one per CU run in ONE launch, a row block of the
+ *     first product produced and consumed inside one XCD; 0: two launches; 2: timing experiment without the wait,
+ *     wrong results (entering or leaving 2 re-arms the row-block counters)
+ *   "gemm_tile" (0; -1, 0, 32, 64, 128): kron GEMM tile edge, 0 = auto, -1 = the generic kernel only
+ *   "sp_xcds" (1; 1..64): sparse apply: number of L2 domains the chunk order is banded over (8 = one contiguous part of
+ *     the chunk table per XCD of an MI355X; 1 = plain order)
+ *  the bounded wait of the single-launch forms (below)
+ *   "fused_timeout_ms" (2000; 1..600000), "fused_debug_drop" (-1; -1..4095)
+ *
  * "house_fused" / "qn_fused_small" = 0 is also the setting for MORE than two processes sharing one GPU: the workgroups of a
  * single-launch apply wait for each other, so a launch must be resident as a whole; two of the largest Householder launches
  * (256 workgroups of 179-209 VGPRs: 2^20 < n <= 2^21 doubles; four of those up to 2^20 — since round 6 a launch for 2^21 < n <= 2^22 doubles takes the WHOLE chip itself, two workgroups per CU, "house_fused_per_cu"; and the persistent quasi-Newton apply with LDS parking, "qn_persist_lds", owns every CU's LDS: ONE of either at a time) or two quasi-Newton ones (up to 256
@@ -146,6 +214,8 @@ int32_t mxlo_ctx_info(mxlo_ctx *ctx, int64_t info[4]);
  * the multi-launch form otherwise. "fused_debug_drop" (default -1) is a TEST HOOK: that workgroup index never publishes
  * its partial, which is how tests/test_gpu_leaves.py provokes the timeout. */
 int32_t mxlo_ctx_tune(mxlo_ctx *ctx, const char *key, int64_t value);
+int32_t mxlo_ctx_tune_get(mxlo_ctx *ctx, const char *key, int64_t *value);
+int32_t mxlo_tune_key(int32_t index, const char **key, int64_t *def, int64_t *lo, int64_t *hi);
 
 /* Row-sharding hook. When set, EVERY global reduction this ctx performs
  * (Householder h'v, L-BFGS/L-SR1 panel dots, push! dots, shifted-solve dots)

@@ -92,6 +92,8 @@ _PROTOS = {
     "mxlo_ctx_sync": [_vp],
     "mxlo_ctx_info": [_vp, C.POINTER(_i64)],
     "mxlo_ctx_tune": [_vp, C.c_char_p, _i64],
+    "mxlo_ctx_tune_get": [_vp, C.c_char_p, C.POINTER(_i64)],
+    "mxlo_tune_key": [_i32, C.POINTER(C.c_char_p), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
     "mxlo_ctx_set_allreduce": [_vp, ALLREDUCE_FN, _vp],
     "mxlo_malloc": [_vp, _i64, C.POINTER(_vp)],
     "mxlo_free": [_vp, _vp],
@@ -210,6 +212,15 @@ def lib() -> C.CDLL:
         f.restype = _i64 if name == "mxlo_kron_c3_work_size" else _i32
     _lib = L
     return L
+
+
+def tune_keys() -> list[tuple[str, int, int, int]]:
+    """(key, default, lowest, highest) of every ``mxlo_ctx_tune`` key, as ``mxlo_tune_key`` enumerates them (no GPU needed)."""
+    f, out = lib().mxlo_tune_key, []
+    key, d, lo, hi = C.c_char_p(), _i64(), _i64(), _i64()
+    while f(len(out), C.byref(key), C.byref(d), C.byref(lo), C.byref(hi)) == OK:
+        out.append((key.value.decode(), d.value, lo.value, hi.value))
+    return out
 
 
 _rccl = None

@@ -408,160 +408,87 @@ MXLO_API int32_t mxlo_ctx_info(mxlo_ctx *ctx, int64_t info[4]) {
   return MXLO_OK;
 }
 
+// ---- tuning keys: one descriptor per line of tune_keys.def -------------------------------------------------------
+namespace {
+struct TuneKey {
+  const char *name, *doc;
+  int64_t def, lo, hi;
+  int32_t (*rule)(mxlo_ctx *ctx, const TuneKey &k, int64_t *value);   // accepts (and may normalise) *value, or MXLO_EINVAL
+  int64_t (*get)(const Tune &t);
+  void (*set)(Tune &t, int64_t value);
+};
+
+int32_t tune_range(mxlo_ctx *, const TuneKey &k, int64_t *value) {
+  MXLO_REQUIRE(*value >= k.lo && *value <= k.hi, MXLO_EINVAL, "%s must be in %lld..%lld (%s)", k.name, (long long)k.lo,
+               (long long)k.hi, k.doc);
+  return MXLO_OK;
+}
+template <int64_t... Allowed>
+int32_t tune_one_of(const TuneKey &k, int64_t value) {
+  MXLO_REQUIRE(((value == Allowed) || ...), MXLO_EINVAL, "%s: %lld is not an accepted value (%s)", k.name,
+               (long long)value, k.doc);
+  return MXLO_OK;
+}
+int32_t tune_nonzero(mxlo_ctx *, const TuneKey &, int64_t *value) {   // any value: stored as value != 0
+  *value = *value != 0;
+  return MXLO_OK;
+}
+int32_t tune_gemm_tile(mxlo_ctx *, const TuneKey &k, int64_t *value) { return tune_one_of<-1, 0, 32, 64, 128>(k, *value); }
+int32_t tune_herm_strip(mxlo_ctx *, const TuneKey &k, int64_t *value) { return tune_one_of<0, 1, 2, 8>(k, *value); }
+int32_t tune_red_blocks(mxlo_ctx *ctx, const TuneKey &k, int64_t *value) {   // the partial slots of a column hold one per workgroup
+  MXLO_REQUIRE(*value >= k.lo && *value <= k.hi / ctx->num_cu, MXLO_EINVAL, "%s x %d CUs must be in %lld..%lld (%s)",
+               k.name, ctx->num_cu, (long long)k.lo, (long long)k.hi, k.doc);
+  return MXLO_OK;
+}
+int32_t tune_kron_fuse(mxlo_ctx *ctx, const TuneKey &k, int64_t *value) {
+  MXLO_TRY(tune_range(ctx, k, value));
+  // mode 2 does not wait, so its last consumer can zero a row block's counter before late producers add to it: leaving or
+  // entering it re-arms the counters, or the next waiting apply could consume a row block early
+  if ((ctx->tune.kron_fuse == 2 || *value == 2) && ctx->tune.kron_fuse != (int)*value && ctx->kron_cnt)
+    MXLO_HIP(hipMemsetAsync(ctx->kron_cnt, 0, sizeof(unsigned) * ctx->kron_cnt_n, ctx->stream));
+  return MXLO_OK;
+}
+
+static_assert(MXLO_INV_REFORDER == MXLO_INV_TWOPASS + 1, "lbfgs_inv_mode is described as the range TWOPASS..REFORDER");
+const TuneKey kTuneKeys[] = {
+#define MXLO_TUNE_KEY(type, name, def, lo, hi, rule, doc) \
+  {#name, doc, def, lo, hi, rule, [](const Tune &t) -> int64_t { return t.name; }, [](Tune &t, int64_t v) { t.name = (type)v; }},
+#include "tune_keys.def"
+};
+
+const TuneKey *find_tune_key(const char *key) {
+  for (const TuneKey &k : kTuneKeys)
+    if (!strcmp(key, k.name)) return &k;
+  set_error("unknown tuning key '%s'", key);
+  return nullptr;
+}
+}  // namespace
+
 MXLO_API int32_t mxlo_ctx_tune(mxlo_ctx *ctx, const char *key, int64_t value) {
   MXLO_REQUIRE(ctx && key, MXLO_EINVAL, "ctx/key is NULL");
-  if (!strcmp(key, "blocks_per_cu")) {
-    MXLO_REQUIRE(value >= 0 && value <= 64, MXLO_EINVAL, "blocks_per_cu out of range");
-    ctx->tune.blocks_per_cu = (int)value;
-  } else if (!strcmp(key, "nt_min_bytes")) {
-    MXLO_REQUIRE(value >= 0, MXLO_EINVAL, "nt_min_bytes out of range");
-    ctx->tune.nt_min_bytes = value;
-  } else if (!strcmp(key, "red_blocks_per_cu")) {
-    MXLO_REQUIRE(value >= 1 && value * ctx->num_cu <= kMaxRedBlocks, MXLO_EINVAL,
-                 "red_blocks_per_cu out of range");
-    ctx->tune.red_blocks_per_cu = (int)value;
-  } else if (!strcmp(key, "graph_direct_max")) {
-    MXLO_REQUIRE(value >= 0 && value <= 4096, MXLO_EINVAL, "graph_direct_max must be in 0..4096 (0: always hipGraphLaunch)");
-    ctx->tune.graph_direct_max = (int)value;
-  } else if (!strcmp(key, "house_fused")) {
-    ctx->tune.house_fused = value != 0;
-  } else if (!strcmp(key, "cherm_two_pass")) {
-    ctx->tune.cherm_two_pass = value != 0;
-  } else if (!strcmp(key, "house_inline_n")) {
-    MXLO_REQUIRE(value >= 0, MXLO_EINVAL, "house_inline_n out of range");
-    ctx->tune.house_inline_n = value;
-  } else if (!strcmp(key, "house_reverse")) {
-    ctx->tune.house_reverse = value != 0;
-  } else if (!strcmp(key, "lbfgs_inv_mode")) {
-    MXLO_REQUIRE(value == MXLO_INV_TWOPASS || value == MXLO_INV_REFORDER, MXLO_EINVAL,
-                 "lbfgs_inv_mode must be MXLO_INV_TWOPASS or MXLO_INV_REFORDER");
-    ctx->tune.lbfgs_inv_mode = (int)value;
-  } else if (!strcmp(key, "gemm_tile")) {
-    MXLO_REQUIRE(value == 0 || value == 32 || value == 64 || value == 128 || value == -1, MXLO_EINVAL,
-                 "gemm_tile must be 0 (auto), 32, 64, 128 or -1 (generic kernel)");
-    ctx->tune.gemm_tile = (int)value;
-  } else if (!strcmp(key, "extend_tiles_per_block")) {
-    MXLO_REQUIRE(value >= 0 && value <= 1024, MXLO_EINVAL, "extend_tiles_per_block must be in 0..1024 (0 = auto)");
-    ctx->tune.extend_tiles_per_block = (int)value;
-  } else if (!strcmp(key, "fuse_finalize")) {
-    MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "fuse_finalize must be 0 or 1");
-    ctx->tune.fuse_finalize = (int)value;
-  } else if (!strcmp(key, "combine_blocks_per_cu")) {
-    MXLO_REQUIRE(value >= 0 && value <= 64, MXLO_EINVAL, "combine_blocks_per_cu out of range");
-    ctx->tune.combine_blocks_per_cu = (int)value;
-  } else if (!strcmp(key, "qn_fused_max_grid")) {
-    MXLO_REQUIRE(value >= 1 && value <= kQnfMaxGrid, MXLO_EINVAL, "qn_fused_max_grid must be in 1..256");
-    ctx->tune.qn_fused_max_grid = (int)value;
-  } else if (!strcmp(key, "qn_fused_batch12")) {
-    MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "qn_fused_batch12 must be 0 or 1");
-    ctx->tune.qn_fused_batch12 = (int)value;
-  } else if (!strcmp(key, "qn_fused_small")) {
-    MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "qn_fused_small must be 0 or 1");
-    ctx->tune.qn_fused_small = (int)value;
-  } else if (!strcmp(key, "qn_persist")) {
-    MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "qn_persist must be 0 or 1");
-    ctx->tune.qn_persist = (int)value;
-  } else if (!strcmp(key, "qn_persist_min_n")) {
-    MXLO_REQUIRE(value >= 1, MXLO_EINVAL, "qn_persist_min_n must be >= 1");
-    ctx->tune.qn_persist_min_n = value;
-  } else if (!strcmp(key, "qn_persist_max_bytes")) {
-    MXLO_REQUIRE(value >= 0, MXLO_EINVAL, "qn_persist_max_bytes must be >= 0");
-    ctx->tune.qn_persist_max_bytes = value;
-  } else if (!strcmp(key, "qn_persist_min_bytes")) {
-    MXLO_REQUIRE(value >= 0, MXLO_EINVAL, "qn_persist_min_bytes must be >= 0");
-    ctx->tune.qn_persist_min_bytes = value;
-  } else if (!strcmp(key, "qn_persist_reverse")) {
-    MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "qn_persist_reverse must be 0 or 1");
-    ctx->tune.qn_persist_reverse = (int)value;
-  } else if (!strcmp(key, "qn_persist_prefetch")) {
-    MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "qn_persist_prefetch must be 0 or 1");
-    ctx->tune.qn_persist_prefetch = (int)value;
-  } else if (!strcmp(key, "qn_persist_lds")) {
-    MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "qn_persist_lds must be 0 or 1");
-    ctx->tune.qn_persist_lds = (int)value;
-  } else if (!strcmp(key, "qn_persist_lds_pad")) {
-    MXLO_REQUIRE(value >= 0 && value <= 112 * 1024, MXLO_EINVAL, "qn_persist_lds_pad must be in 0..114688 bytes");
-    ctx->tune.qn_persist_lds_pad = (int)value;
-  } else if (!strcmp(key, "kron_fuse")) {
-    MXLO_REQUIRE(value >= 0 && value <= 2, MXLO_EINVAL, "kron_fuse must be 0, 1 (or 2: timing experiment without the wait, wrong results)");
-    // mode 2 does not wait, so its last consumer can zero a row block's counter before late producers add to it: leaving or
-    // entering it re-arms the counters, or the next waiting apply could consume a row block early
-    if ((ctx->tune.kron_fuse == 2 || value == 2) && ctx->tune.kron_fuse != (int)value && ctx->kron_cnt)
-      MXLO_HIP(hipMemsetAsync(ctx->kron_cnt, 0, sizeof(unsigned) * ctx->kron_cnt_n, ctx->stream));
-    ctx->tune.kron_fuse = (int)value;
-  } else if (!strcmp(key, "alias_guard")) {
-    MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "alias_guard must be 1 or 0 (test hook: overlapping res / v unguarded)");
-    ctx->tune.alias_guard = (int)value;
-  } else if (!strcmp(key, "herm_order")) {
-    MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "herm_order must be 0 or 1");
-    ctx->tune.herm_order = (int)value;
-  } else if (!strcmp(key, "herm_nt")) {
-    MXLO_REQUIRE(value >= -1 && value <= 1, MXLO_EINVAL, "herm_nt must be -1 (by size), 0 or 1");
-    ctx->tune.herm_nt = (int)value;
-  } else if (!strcmp(key, "herm_dp_min_bytes")) {
-    MXLO_REQUIRE(value >= 0, MXLO_EINVAL, "herm_dp_min_bytes must be >= 0");
-    ctx->tune.herm_dp_min_bytes = value;
-  } else if (!strcmp(key, "herm_nt_min_bytes")) {
-    MXLO_REQUIRE(value >= 0, MXLO_EINVAL, "herm_nt_min_bytes must be >= 0");
-    ctx->tune.herm_nt_min_bytes = value;
-  } else if (!strcmp(key, "house_fused_per_cu")) {
-    MXLO_REQUIRE(value == 1 || value == 2, MXLO_EINVAL, "house_fused_per_cu must be 1 or 2");
-    ctx->tune.house_fused_per_cu = (int)value;
-  } else if (!strcmp(key, "herm_poll_sleep")) {
-    MXLO_REQUIRE(value >= 1 && value <= 1024, MXLO_EINVAL, "herm_poll_sleep must be in 1..1024");
-    ctx->tune.herm_poll_sleep = (int)value;
-  } else if (!strcmp(key, "herm_strip")) {
-    MXLO_REQUIRE(value == 0 || value == 1 || value == 2 || value == 8, MXLO_EINVAL, "herm_strip must be 0 (by size), 1, 2 or 8");
-    ctx->tune.herm_strip = (int)value;
-  } else if (!strcmp(key, "herm_lds_pad")) {
-    MXLO_REQUIRE(value >= 0 && value <= 48 * 1024, MXLO_EINVAL, "herm_lds_pad must be in 0..49152 bytes");
-    ctx->tune.herm_lds_pad = (int)value;
-  } else if (!strcmp(key, "herm_single")) {
-    MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "herm_single must be 0 or 1");
-    ctx->tune.herm_single = (int)value;
-  } else if (!strcmp(key, "herm_single_max_bytes")) {
-    MXLO_REQUIRE(value >= 0, MXLO_EINVAL, "herm_single_max_bytes must be >= 0");
-    ctx->tune.herm_single_max_bytes = value;
-  } else if (!strcmp(key, "herm_single_max_n")) {
-    MXLO_REQUIRE(value >= 0, MXLO_EINVAL, "herm_single_max_n must be >= 0");
-    ctx->tune.herm_single_max_n = value;
-  } else if (!strcmp(key, "gemv_n_rows")) {
-    MXLO_REQUIRE(value >= 0 && value <= 128, MXLO_EINVAL, "gemv_n_rows must be 0 (off), 1 (auto) or a band height");
-    ctx->tune.gemv_n_rows = (int)value;
-  } else if (!strcmp(key, "gemvb_n_rows")) {
-    MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "gemvb_n_rows must be 0 or 1");
-    ctx->tune.gemvb_n_rows = (int)value;
-  } else if (!strcmp(key, "gemvb_t_lds")) {
-    MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "gemvb_t_lds must be 0 or 1");
-    ctx->tune.gemvb_t_lds = (int)value;
-  } else if (!strcmp(key, "combine_reverse")) {
-    MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "combine_reverse must be 0 or 1");
-    ctx->tune.combine_reverse = (int)value;
-  } else if (!strcmp(key, "sp_xcds")) {
-    MXLO_REQUIRE(value >= 1 && value <= 64, MXLO_EINVAL, "sp_xcds must be in 1..64");
-    ctx->tune.sp_xcds = (int)value;
-  } else if (!strcmp(key, "fused_timeout_ms")) {
-    MXLO_REQUIRE(value >= 1 && value <= 600000, MXLO_EINVAL, "fused_timeout_ms must be in 1..600000");
-    ctx->tune.fused_timeout_ms = (int)value;
-  } else if (!strcmp(key, "fused_debug_drop")) {
-    MXLO_REQUIRE(value >= -1 && value < 4096, MXLO_EINVAL, "fused_debug_drop must be -1 (off) or a workgroup index");
-    ctx->tune.fused_debug_drop = (int)value;
-  } else if (!strcmp(key, "push_wide")) {
-    MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "push_wide must be 0 or 1");
-    ctx->tune.push_wide = (int)value;
-  } else if (!strcmp(key, "push_posted")) {
-    MXLO_REQUIRE(value >= 0 && value <= 2, MXLO_EINVAL, "push_posted must be 0, 1 or 2 (2: debug, the posting is treated as lost)");
-    ctx->tune.push_posted = (int)value;
-  } else if (!strcmp(key, "push_fused")) {
-    MXLO_REQUIRE(value == 0 || value == 1, MXLO_EINVAL, "push_fused must be 0 or 1");
-    ctx->tune.push_fused = (int)value;
-  } else if (!strcmp(key, "dots_max_nc")) {
-    MXLO_REQUIRE(value >= 1 && value <= 20, MXLO_EINVAL, "dots_max_nc out of range");
-    ctx->tune.dots_max_nc = (int)value;
-  } else {
-    set_error("mxlo_ctx_tune: unknown key '%s'", key);
-    return MXLO_EINVAL;
-  }
+  const TuneKey *k = find_tune_key(key);
+  if (!k) return MXLO_EINVAL;
+  MXLO_TRY(k->rule(ctx, *k, &value));
+  k->set(ctx->tune, value);
+  return MXLO_OK;
+}
+
+MXLO_API int32_t mxlo_ctx_tune_get(mxlo_ctx *ctx, const char *key, int64_t *value) {
+  MXLO_REQUIRE(ctx && key && value, MXLO_EINVAL, "mxlo_ctx_tune_get: NULL argument");
+  const TuneKey *k = find_tune_key(key);
+  if (!k) return MXLO_EINVAL;
+  *value = k->get(ctx->tune);
+  return MXLO_OK;
+}
+
+MXLO_API int32_t mxlo_tune_key(int32_t index, const char **key, int64_t *def, int64_t *lo, int64_t *hi) {
+  constexpr int32_t n = (int32_t)(sizeof(kTuneKeys) / sizeof(kTuneKeys[0]));
+  MXLO_REQUIRE(index >= 0 && index < n, MXLO_EINVAL, "mxlo_tune_key: index %d not in [0,%d)", index, n);
+  const TuneKey &k = kTuneKeys[index];
+  if (key) *key = k.name;
+  if (def) *def = k.def;
+  if (lo) *lo = k.lo;
+  if (hi) *hi = k.hi;
   return MXLO_OK;
 }
 

@@ -117,78 +117,9 @@ inline bool mxlo_trace_on() {
     }                                                                                            \
   } while (0)
 
-struct Tune {
-  int blocks_per_cu = 0;   // streaming kernels: 0 = one chunk per workgroup; k = persistent grid CUs*k
-  int extend_tiles_per_block = 0;     // sorted extension: consecutive output tiles per workgroup (0 = auto)
-  int64_t nt_min_bytes = 256ll << 20;  // streamed footprint from which nontemporal accesses are used: the size of the
-                                       // Infinity Cache — below it the second pass of a two-pass apply finds the first
-                                       // pass's lines there (profiles/r03_sweep_nt_mid.txt: -5 ... -8 % at n = 2^21 .. 2^23)
-  int red_blocks_per_cu = 4;  // reduction kernels
-  int graph_direct_max = 16; // captured chains of at most this many kernel/memset nodes replay as direct launches
-  int house_fused_per_cu = 2;   // single-launch Householder: workgroups per CU it may use (2, round 6: vectors up to 2^22 doubles; 1: up to 2^21)
-  int house_fused = 1;     // single-launch Householder (dot, grid exchange, update) while the vectors fit one wave of workgroups
-  int cherm_two_pass = 0;  // complex opHermitian: 1 = the two-pass (rows, then columns) form instead of the strip kernel
-  int house_reverse = 1;   // Householder phase B walks the vectors back-to-front (MALL tail reuse)
-  int64_t house_inline_n = 1ll << 23;   // two-pass Householder up to this n: the update pass sums the dots pass's partials
-                                        // itself (no finalize launch); above, one finalize launch is cheaper than every
-                                        // update workgroup re-reading the partials
-  int lbfgs_inv_mode = MXLO_INV_TWOPASS;
-  int dots_max_nc = 20;    // columns per panel_dots launch (<= 20)
-  int gemm_tile = 0;       // kron GEMM tile edge: 0 = auto (largest of 128/64/32 that still gives every CU a
-                           // workgroup), 32 / 64 / 128 force one, -1 = generic fallback kernel only
-  int fuse_finalize = 1;   // reductions of <= 4 columns: last-arriving workgroup finalizes in the dots kernel
-  int combine_blocks_per_cu = 0;   // panel_combine: 0 = one vector per thread (best measured), k = persistent grid
-  int qn_fused_max_grid = 256;  // single-launch quasi-Newton apply: most workgroups it may use (<= 256; 64 = the round-3 limit)
-  int qn_fused_batch12 = 1;   // single-launch quasi-Newton apply with 9 .. 12 columns on short vectors: all columns in one batch
-  int qn_fused_small = 1;  // quasi-Newton applies with <= 64 workgroups of dots: dots + finalize + coefficients in one launch
-  int qn_persist = 1;      // quasi-Newton applies at cache-resident sizes: ONE persistent launch (one workgroup per CU, grid
-                           // exchange between the dots and the combine phase; qn.hip: qn_apply_persist_kernel)
-  int64_t qn_persist_min_n = 1ll << 19;          // ... from this vector length on (below: the single-launch slice form)
-  int64_t qn_persist_max_bytes = 448ll << 20;    // ... while the panel (columns x n x element size) is at most this many bytes
-                                                 // (profiles/r05_tune_persist.txt: ahead of four launches up to ~340 MB panels)
-  int qn_persist_reverse = 1;   // ... its combine phase walks the workgroup's chunks back to front
-  int qn_persist_prefetch = 0;  // ... x and the first column batch of its first combine chunk are requested before the exchange.
-                                // Measured (profiles/r05_bench_mid_apply.txt, last block): 1.5 us SLOWER at n = 2^19 .. 2^20 (the polls of
-                                // the exchange return in order behind the 11 prefetch loads), neutral above — off
-  int qn_persist_lds = 1;       // ... x and the first columns of the combine order parked in the CU's LDS by the dots phase (round 6)
-  int qn_persist_lds_pad = 0;   // ... bytes of (unused) dynamic LDS requested per workgroup: > 80 KiB forces one workgroup per CU
-  int64_t qn_persist_min_bytes = 32ll << 20;     // ... and at least this many (an L-SR1 m = 5 apply at n = 2^19 — 21 MB — is
-                                                 // faster in the single-launch slice form: 10.7 vs 12.1 us)
-  int herm_order = 1;      // opHermitian interior strips: 0 = row group by row group, 1 (default, round 6) = column block by column block (dense.hip)
-  int herm_nt = -1;        // opHermitian strip loads: -1 = nontemporal except for triangles of [herm_dp_min_bytes, herm_nt_min_bytes)
-                           // (about the size of the Infinity Cache; round 6, dense.hip: herm_nt_policy), 0 / 1 force
-  int64_t herm_dp_min_bytes = 96ll << 20;
-  int64_t herm_nt_min_bytes = 384ll << 20;
-  int herm_poll_sleep = 4;    // single-launch opHermitian: the finishers' first wait looks every 64 x this many clocks (round 5: 32;
-                              // sweep 1 ... 64 in profiles/r06_herm_policy.txt: 2 ... 8 are 0 ... 5 % ahead of 32 at n = 2048 / 3072 / f32 6144, equal elsewhere)
-  int herm_strip = 0;      // opHermitian: tiles per strip, 0 = by size (8 once there are two 8-tile strips per CU, else 2, else 1); 1 / 2 / 8 force (sweeps)
-  int herm_lds_pad = 0;    // opHermitian pass launch: bytes of unused dynamic LDS per workgroup (occupancy experiment, <= 48 KiB)
-  int herm_single = 1;     // opHermitian (full row groups, aligned A, n <= herm_single_max_n): strips and finishers in ONE launch
-  int64_t herm_single_max_n = 0;      // 0 (default): by size — triangles of at most herm_single_max_bytes; > 0: n <= this value
-  int64_t herm_single_max_bytes = 112ll << 20;   // measured (profiles/r06_herm_policy.txt, round 6): f64 gains up to n = 5120
-                                      // (4096: 15.2 -> 14.8 us, 5120: 20.4 -> 19.8), equal at 3072, LOSES at 6144 (28.3 -> 28.8); f32 gains up
-                                      // to 6144 (5120: 15.5 -> 14.1, 6144: 18.5 -> 17.6), equal at 8192. Round 5 measured no gain above
-                                      // 2048: that was with the row-group order and the three-round finish.
-  int kron_fuse = 1;       // kron: both GEMMs in ONE launch when every tile has its own CU, the dependency kept XCD-local
-                           // (gemm_glds.h: kron_fused_kernel; 2: timing experiment without the wait — wrong results)
-  int gemv_n_rows = 1;     // dense M*v: row bands, the column sum stays inside a workgroup — one launch, no partials (dense.hip)
-  int gemvb_n_rows = 1;    // block apply M*V of a dense operator: row bands, V staged in LDS per workgroup — one launch, no partials (dense.hip)
-  int gemvb_t_lds = 1;     // transposed block apply of a dense operator (k >= 4): U staged in LDS per workgroup (dense.hip)
-  int combine_reverse = 0; // four-launch applies: the combine pass walks the vectors back to front. Measured (round 5,
-                           // profiles/r05_bench_mid_apply.txt): -3.6 … +2.8 %, no gain on average — the grid-stride dots pass
-                           // leaves no usable tail behind; the persistent launch (whose workgroups own contiguous runs) does
-  int push_wide = 1;       // one-pass push!: 20 columns per pass while >= 20 remain (0: always <= 10)
-  int push_posted = 1;     // push!'s decision scalars: posted into mapped pinned host memory by a one-wave kernel and polled
-                           // by the host (1) or copied with hipMemcpyAsync + a stream synchronisation (0)
-  int push_fused = 1;      // push!(op, s, y): one-pass schedule (new pair held per lane, in-pass slot stores); 0 = copies + dual-x dots
-  int sp_xcds = 1;         // sparse apply: XCDs (L2 domains) the chunk order is banded over (8: XCD k walks the k-th contiguous
-                           // eighth of the chunk table); 1 = plain order, the default: banding measured -8 % … +8 % by pattern
-  int fused_timeout_ms = 2000;   // single-launch (grid-exchange) kernels: how long a workgroup polls for its peers' partials
-                                 // before it gives up, raises the ctx fault flag and stores NaN (a launch that is not fully
-                                 // co-resident — GPU shared with other processes, CU masking — ends instead of hanging)
-  int fused_debug_drop = -1;     // TEST HOOK: this workgroup of a single-launch kernel never publishes its partial
-  int alias_guard = 1;           // res overlapping v: stage v / leave the one-launch kron (stage_alias below); 0 = TEST HOOK,
-                                 // overlapping operands go to the kernels as they are (wrong results where a kernel races)
+struct Tune {   // the members, their defaults and why the defaults are what they are: tune_keys.def
+#define MXLO_TUNE_KEY(type, name, def, lo, hi, rule, doc) type name = def;
+#include "tune_keys.def"
 };
 
 }  // namespace mxlo

@@ -997,7 +997,7 @@ int32_t chermitian(mxlo_ctx *ctx, C<R> *res, const void *d, bool d_real, const C
 }
 
 // the correctness-first form (two passes over the triangle: L*v by rows, L'*v by columns), kept behind
-// mxlo_ctx_tune("cherm_two_pass", 1) as an independent implementation the tests compare the single pass with
+// the tune key cherm_two_pass = 1 as an independent implementation the tests compare the single pass with
 template <typename R>
 int32_t chermitian_two_pass(mxlo_ctx *ctx, C<R> *res, const void *d, bool d_real, const C<R> *A, int64_t lda,
                             const C<R> *v, int64_t n, const ScalArgs &s) {

@@ -7,6 +7,7 @@ Julia glue's device ``Vector{T}``), for the current HIP stream, and — in
 from __future__ import annotations
 
 import ctypes as C
+from contextlib import contextmanager
 from dataclasses import dataclass
 
 import torch
@@ -82,6 +83,32 @@ class Context:
 
     def tune(self, key: str, value: int):
         _lib.call("mxlo_ctx_tune", self.handle, key.encode(), int(value))
+
+    def tune_get(self, key: str) -> int:
+        v = C.c_int64()
+        _lib.call("mxlo_ctx_tune_get", self.handle, key.encode(), C.byref(v))
+        return v.value
+
+    @contextmanager
+    def tuned(self, **keys):
+        """``with ctx.tuned(house_fused=0, fused_timeout_ms=50): ...`` — sets the named keys for the block and writes
+        back on exit (normal, exception, ``pytest.fail``) what each held on entry, whatever the block or the library
+        (the fault path switches the single-launch forms off) did to them in between. Every key is restored even if one
+        restore raises (the first error is re-raised); a key that is refused on entry leaves the earlier ones restored."""
+        old = {k: self.tune_get(k) for k in keys}          # an unknown key raises here, before anything is set
+        try:
+            for k, v in keys.items():
+                self.tune(k, v)
+            yield self
+        finally:
+            errors = []
+            for k in reversed(old):
+                try:
+                    self.tune(k, old[k])
+                except Exception as e:
+                    errors.append(e)
+            if errors:
+                raise errors[0]
 
     def info(self):
         a = (C.c_int64 * 4)()

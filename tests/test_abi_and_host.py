@@ -42,18 +42,55 @@ def test_ctypes_prototypes_cover_header(lo):
     assert declared == set(lo._lib._PROTOS), declared ^ set(lo._lib._PROTOS)
 
 
-def test_every_tune_key_is_documented_in_the_header():
+def test_every_tune_key_is_documented_in_the_header(lo):
     """`mxlo_ctx_tune` keys are part of the boundary (tools and tests set them through the ABI): every key the library
-    accepts must be named in include/mxlo.h."""
-    import os
-    import re
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "linearoperators.jl_amd", "csrc", "api_ctx.hip")).read()
-    hdr = open(os.path.join(root, "include", "mxlo.h")).read()
-    keys = set(re.findall(r'strcmp\(key, "([a-z_0-9]+)"\)', src))
+    enumerates (`mxlo_tune_key`) must be named in include/mxlo.h."""
+    hdr = open(lo._lib.HEADER).read()
+    keys = [k for k, _, _, _ in lo._lib.tune_keys()]
     assert len(keys) >= 15
     missing = sorted(k for k in keys if f'"{k}"' not in hdr)
     assert not missing, missing
+
+
+def test_tune_keys_are_unique_and_their_defaults_lie_in_their_ranges(lo):
+    table = lo._lib.tune_keys()
+    keys = [k for k, _, _, _ in table]
+    assert len(set(keys)) == len(keys), sorted(k for k in set(keys) if keys.count(k) > 1)
+    bad = [(k, d, lo_, hi) for k, d, lo_, hi in table if not lo_ <= d <= hi]
+    assert not bad, bad
+    L = lo._lib.lib()
+    assert L.mxlo_tune_key(len(table), None, None, None, None) == lo._lib.EINVAL
+    assert L.mxlo_tune_key(-1, None, None, None, None) == lo._lib.EINVAL
+    assert L.mxlo_tune_key(0, None, None, None, None) == lo._lib.OK          # every out-pointer is optional
+
+
+# (key, default, lowest, highest) as of the commit that introduced the key table, written down from the `struct Tune`
+# defaults and the range checks of `mxlo_ctx_tune` before it: a default or a range that moves shows up here as well.
+_I64_MAX = (1 << 63) - 1
+TUNE_TABLE = {
+    ("blocks_per_cu", 0, 0, 64), ("nt_min_bytes", 256 << 20, 0, _I64_MAX), ("red_blocks_per_cu", 4, 1, 4096),
+    ("graph_direct_max", 16, 0, 4096), ("house_fused", 1, 0, 1), ("cherm_two_pass", 0, 0, 1),
+    ("house_inline_n", 1 << 23, 0, _I64_MAX), ("house_reverse", 1, 0, 1), ("lbfgs_inv_mode", 0, 0, 1),
+    ("gemm_tile", 0, -1, 128), ("extend_tiles_per_block", 0, 0, 1024), ("fuse_finalize", 1, 0, 1),
+    ("combine_blocks_per_cu", 0, 0, 64), ("qn_fused_max_grid", 256, 1, 256), ("qn_fused_batch12", 1, 0, 1),
+    ("qn_fused_small", 1, 0, 1), ("qn_persist", 1, 0, 1), ("qn_persist_min_n", 1 << 19, 1, _I64_MAX),
+    ("qn_persist_max_bytes", 448 << 20, 0, _I64_MAX), ("qn_persist_min_bytes", 32 << 20, 0, _I64_MAX),
+    ("qn_persist_reverse", 1, 0, 1), ("qn_persist_prefetch", 0, 0, 1), ("qn_persist_lds", 1, 0, 1),
+    ("qn_persist_lds_pad", 0, 0, 112 * 1024), ("kron_fuse", 1, 0, 2), ("alias_guard", 1, 0, 1), ("herm_order", 1, 0, 1),
+    ("herm_nt", -1, -1, 1), ("herm_dp_min_bytes", 96 << 20, 0, _I64_MAX), ("herm_nt_min_bytes", 384 << 20, 0, _I64_MAX),
+    ("house_fused_per_cu", 2, 1, 2), ("herm_poll_sleep", 4, 1, 1024), ("herm_strip", 0, 0, 8),
+    ("herm_lds_pad", 0, 0, 48 * 1024), ("herm_single", 1, 0, 1), ("herm_single_max_bytes", 112 << 20, 0, _I64_MAX),
+    ("herm_single_max_n", 0, 0, _I64_MAX), ("gemv_n_rows", 1, 0, 128), ("gemvb_n_rows", 1, 0, 1), ("gemvb_t_lds", 1, 0, 1),
+    ("combine_reverse", 0, 0, 1), ("sp_xcds", 1, 1, 64), ("fused_timeout_ms", 2000, 1, 600000),
+    ("fused_debug_drop", -1, -1, 4095), ("push_wide", 1, 0, 1), ("push_posted", 1, 0, 2), ("push_fused", 1, 0, 1),
+    ("dots_max_nc", 20, 1, 20),
+}
+
+
+def test_no_tune_default_and_no_range_has_moved(lo):
+    got = set(lo._lib.tune_keys())
+    assert got == TUNE_TABLE, sorted(got ^ TUNE_TABLE)
+    assert lo._lib.INV_TWOPASS == 0 and lo._lib.INV_REFORDER == 1        # what lbfgs_inv_mode's 0 .. 1 stands for
 
 
 def _gfx950_code_objects(lo, td):

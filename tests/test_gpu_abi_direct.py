@@ -100,13 +100,12 @@ def test_tune_keys(lo, dev):
     d, v = rng.standard_normal(n), rng.standard_normal(n)
     D = lo.opDiagonal(torch.from_numpy(d).to(dev))
     want = oracle.diag_mul(np.empty(n), d, v, 1.5, 0.0)
-    try:
-        for key, vals in (("blocks_per_cu", (0, 1, 8)), ("nt_min_bytes", (0, 1 << 40)), ("house_inline_n", (0, 1 << 40)), ("red_blocks_per_cu", (1, 16)),
-                          ("house_reverse", (0, 1)), ("house_fused", (0, 1)), ("gemm_tile", (32, 64, 128, -1, 0)),
-                          ("extend_tiles_per_block", (1, 8, 0)),
-                          ("combine_blocks_per_cu", (0, 4)), ("dots_max_nc", (1, 20))):
-            for val in vals:
-                ctx.tune(key, val)
+    for key, vals in (("blocks_per_cu", (0, 1, 8)), ("nt_min_bytes", (0, 1 << 40)), ("house_inline_n", (0, 1 << 40)), ("red_blocks_per_cu", (1, 16)),
+                      ("house_reverse", (0, 1)), ("house_fused", (0, 1)), ("gemm_tile", (32, 64, 128, -1, 0)),
+                      ("extend_tiles_per_block", (1, 8, 0)),
+                      ("combine_blocks_per_cu", (0, 4)), ("dots_max_nc", (1, 20))):
+        for val in vals:
+            with ctx.tuned(**{key: val}):
                 out = torch.empty(n, dtype=torch.float64, device=dev)
                 lo.mul(out, D, torch.from_numpy(v).to(dev), 1.5, 0.0)
                 assert np.array_equal(out.cpu().numpy(), want)
@@ -114,11 +113,6 @@ def test_tune_keys(lo, dev):
                 hv = lo.opHouseholder(h) * torch.from_numpy(v).to(dev)
                 ref = oracle.householder_mul(np.empty(n), d / np.linalg.norm(d), v, 1.0, 0.0)
                 assert np.linalg.norm(hv.cpu().numpy() - ref) <= 1e-12 * np.linalg.norm(ref)
-    finally:
-        for key, val in (("blocks_per_cu", 0), ("nt_min_bytes", 256 << 20), ("red_blocks_per_cu", 4), ("house_reverse", 1),
-                         ("gemm_tile", 0), ("combine_blocks_per_cu", 0), ("dots_max_nc", 20), ("house_fused", 1),
-                         ("extend_tiles_per_block", 0), ("house_inline_n", 1 << 23)):
-            ctx.tune(key, val)
 
 
 @pytest.mark.parametrize("n,world", [(1, 1), (7, 3), (10, 4), (1000, 8), (12345, 7), (5, 8), (2_000_003, 8)])

@@ -170,8 +170,7 @@ HOUSE_CASES = [(dt, n, f) for dt in HOUSE_TOL for n in (1000, 3_000_001) for f i
 def test_householder(lo, dev, dtype, n, fused):
     tol = HOUSE_TOL[dtype]
     ctx = lo.get_ctx(dev)
-    ctx.tune("house_fused", fused)
-    try:
+    with ctx.tuned(house_fused=fused):
         for rep in range(3):
             rng = np.random.default_rng(n % 1009 + rep)
             h = rand(rng, n, dtype)
@@ -190,8 +189,6 @@ def test_householder(lo, dev, dtype, n, fused):
                 check_windows(lo, dev, H, n, n, dtype, rng)
         if n == 30_000_000 and dtype == torch.float64:
             check_windows(lo, dev, H, n, n, dtype, rng, shifts=(1, 4097))
-    finally:
-        ctx.tune("house_fused", 1)
 
 
 # ------------------------------------------------------------------------------------------------ opHermitian
@@ -200,8 +197,7 @@ def test_householder(lo, dev, dtype, n, fused):
 @pytest.mark.parametrize("single", [1, 0])
 def test_hermitian(lo, dev, dtype, tol, n, single):
     ctx = lo.get_ctx(dev)
-    ctx.tune("herm_single", single)
-    try:
+    with ctx.tuned(herm_single=single):
         for rep in range(3):
             rng = np.random.default_rng(n + rep)
             A = rand(rng, n * n, dtype).reshape(n, n)
@@ -212,8 +208,6 @@ def test_hermitian(lo, dev, dtype, tol, n, single):
                 a, b = ab_of(ab, dtype)
                 return oracle.hermitian_mul(v.copy(), d, A, v, a, b)
             check_aliased(lo, dev, Hm, rand(rng, n, dtype), dtype, want, tol)
-    finally:
-        ctx.tune("herm_single", 1)
 
 
 # ------------------------------------------------------------------------------------------------ opRestriction
@@ -269,8 +263,7 @@ def kron_canary_one_launch(lo, dev):
 def test_kron_square(lo, dev, dtype, tol, m, fuse):
     ctx = lo.get_ctx(dev)
     one = kron_canary_one_launch(lo, dev)
-    ctx.tune("kron_fuse", fuse)
-    try:
+    with ctx.tuned(kron_fuse=fuse):
         for rep in range(3):
             rng = np.random.default_rng(m + rep)
             A, B = rand(rng, m * m, dtype).reshape(m, m), rand(rng, m * m, dtype).reshape(m, m)
@@ -292,8 +285,6 @@ def test_kron_square(lo, dev, dtype, tol, m, fuse):
                 l0 = launches(lo)
                 lo.mul(x, K, x)
                 assert launches(lo) - l0 == 2
-    finally:
-        ctx.tune("kron_fuse", 1)
 
 
 def test_kron_complex_and_diagonal(lo, dev):
@@ -329,10 +320,8 @@ LBFGS_CASES = [(1 << 12, 5, None), (1 << 12, 10, None), (1 << 20, 5, 1), (1 << 2
                                        ("fwd", "compact")])
 def test_lbfgs(lo, dev, n, mem, park, kind, mode):
     ctx = lo.get_ctx(dev)
-    if park is not None:                                   # 2^20: the persistent apply, LDS parking on / off
-        ctx.tune("qn_persist_min_bytes", 0)
-        ctx.tune("qn_persist_lds", park)
-    try:
+    # 2^20: the persistent apply, LDS parking on / off
+    with ctx.tuned(**({"qn_persist_min_bytes": 0, "qn_persist_lds": park} if park is not None else {})):
         for rep in range(3 if n < (1 << 24) else 1):
             rng = np.random.default_rng(n + mem + rep)
             make = lo.InverseLBFGSOperator if kind == "inv" else lo.LBFGSOperator
@@ -349,9 +338,6 @@ def test_lbfgs(lo, dev, n, mem, park, kind, mode):
                           lambda v, ab: ref.mul(v.copy(), v, *ab_of(ab, None)), 1e-9)
             if kind == "inv" and rep == 0:
                 check_windows(lo, dev, op, n, n, torch.float64, rng, shifts=SHIFTS if n < (1 << 24) else (4097,))
-    finally:
-        ctx.tune("qn_persist_lds", 1)
-        ctx.tune("qn_persist_min_bytes", 32 << 20)
 
 
 # ------------------------------------------------------------------------------------------------ wrappers, products

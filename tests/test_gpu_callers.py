@@ -222,8 +222,7 @@ def test_graph_replay_direct_chain_equals_hipgraph_launch(lo, dev):
     v = torch.from_numpy(rng.uniform(-1, 1, n)).to(dev)
     outs = []
     for direct_max in (16, 0):
-        ctx.tune("graph_direct_max", direct_max)
-        try:
+        with ctx.tuned(graph_direct_max=direct_max):
             res = torch.from_numpy(np.full(n, 0.5)).to(dev)
             g = lo.capture_mul(res, op, v, 2.0, -3.0)
             inf = g.info()
@@ -232,16 +231,13 @@ def test_graph_replay_direct_chain_equals_hipgraph_launch(lo, dev):
                 g.replay()
             torch.cuda.synchronize()
             outs.append(res.cpu().numpy().copy())
-        finally:
-            ctx.tune("graph_direct_max", 16)
     assert np.array_equal(outs[0], outs[1])
     # memset node: mxlo_scatter_zero = hipMemsetAsync + scatter kernel
     idx = torch.from_numpy(np.sort(rng.choice(n, 1000, replace=False) + 1).astype(np.int64)).to(dev)
     u = torch.from_numpy(rng.standard_normal(1000)).to(dev)
     outs = []
     for direct_max in (16, 0):
-        ctx.tune("graph_direct_max", direct_max)
-        try:
+        with ctx.tuned(graph_direct_max=direct_max):
             res = torch.full((n,), 7.0, dtype=torch.float64, device=dev)
             with lo.CapturedSequence(dev) as g:
                 c = get_ctx(dev)
@@ -251,8 +247,6 @@ def test_graph_replay_direct_chain_equals_hipgraph_launch(lo, dev):
             g.replay()
             torch.cuda.synchronize()
             outs.append(res.cpu().numpy().copy())
-        finally:
-            ctx.tune("graph_direct_max", 16)
     want = np.zeros(n); want[idx.cpu().numpy() - 1] = u.cpu().numpy()
     assert np.array_equal(outs[0], want) and np.array_equal(outs[1], want)
 

@@ -359,12 +359,9 @@ def test_complex_hermitian_strip_regimes(lo, dev, dtype, tol, n, aligned):
             lo.mul(res, H, T(v, dev), a, b)
             want = oracle.hermitian_mul(r0.copy(), d, A, v, a, b, flags=oracle.scalar_flags(dt, a, b))
             assert rel(res.cpu().numpy(), want) <= tol, (n, a, b)
-            ctx.tune("cherm_two_pass", 1)
-            try:
+            with ctx.tuned(cherm_two_pass=1):
                 res2 = T(r0.copy(), dev)
                 lo.mul(res2, H, T(v, dev), a, b)
-            finally:
-                ctx.tune("cherm_two_pass", 0)
             assert rel(res.cpu().numpy(), res2.cpu().numpy()) <= tol
     # structure: e_j picks column j of the Hermitian matrix (exact products with 0 and 1)
     for j in (0, n // 2, n - 1):

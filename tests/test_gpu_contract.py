@@ -79,13 +79,10 @@ def test_warmed_applies_only_launch_kernels(lo, dev, dtype):
             only_launches(delta(lo, lambda: lo.mul(res, op.T, v, 1.0, 0.0), 2), 2, f"mul! transpose({name})")
     # the two-launch Householder path (what sharded runs use) obeys the same contract
     ctx = lo.get_ctx(dev)
-    ctx.tune("house_fused", 0)
-    try:
+    with ctx.tuned(house_fused=0):
         H = ops["opHouseholder (single launch)"]
         lo.mul(res, H, v, 1.0, 0.0)
         only_launches(delta(lo, lambda: lo.mul(res, H, v, 1.0, 0.0), 3), 3, "mul! opHouseholder (two launches)")
-    finally:
-        ctx.tune("house_fused", 1)
     # diag! and solve_shifted_system! on warmed operators
     B = qn["LBFGS"]
     dvec = torch.empty(n, dtype=dtype, device=dev)

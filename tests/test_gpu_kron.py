@@ -419,9 +419,8 @@ def test_kron_one_launch_form_is_bit_identical_to_the_two_launches(lo, dev, dtyp
     r0 = T(rng.uniform(-1, 1, am * bp).astype(npd), dev)
     ctx = lo.get_ctx(dev)
     got = {}
-    try:
-        for fuse in (0, 1):
-            ctx.tune("kron_fuse", fuse)
+    for fuse in (0, 1):
+        with ctx.tuned(kron_fuse=fuse):
             out = []
             for rep in range(3):                                  # repeated applies: the counters of the fused form re-arm themselves
                 a = torch.full((am * bp,), float("nan"), dtype=dtype, device=dev)
@@ -435,8 +434,6 @@ def test_kron_one_launch_form_is_bit_identical_to_the_two_launches(lo, dev, dtyp
             for rep in (1, 2):
                 assert all(torch.equal(u, v) for u, v in zip(out[0], out[rep]))
             got[fuse] = out[0]
-    finally:
-        ctx.tune("kron_fuse", 1)
     assert all(torch.equal(u, v) for u, v in zip(got[0], got[1]))
     if am * bp * an * bq <= 1 << 26:                               # the dense product as the reference's test does (test_kron.jl:35)
         Kd = np.kron(A.astype(np.float64), B.astype(np.float64))
@@ -458,36 +455,30 @@ def test_one_launch_kron_timeout_is_an_error_not_a_hang(lo, dev):
     x = T(rng.uniform(-1, 1, n * n), dev)
     res = torch.zeros(n * n, dtype=torch.float64, device=dev)
     want = (B @ x.cpu().numpy().reshape(n, n, order="F") @ A.T).reshape(-1, order="F")
-    try:
-        ctx.tune("kron_fuse", 1)
+    # a fault switches all the single-launch forms off: the exit of this block puts them back
+    with ctx.tuned(kron_fuse=1, house_fused=1, qn_fused_small=1, qn_persist=1, herm_single=1):
         lo.mul(res, K, x, 1.0, 0.0)
         torch.cuda.synchronize()
         assert rel(res.cpu().numpy(), want) <= 1e-12
-        ctx.tune("fused_timeout_ms", 30)
-        ctx.tune("fused_debug_drop", 3)
-        t0 = time.perf_counter()
-        lo.mul(res, K, x, 1.0, 0.0)                  # the launch succeeds; the consumers of workgroup 3's row block give up
-        torch.cuda.synchronize()
-        assert time.perf_counter() - t0 < 5.0
-        got = res.cpu().numpy()
-        assert np.isnan(got).any() and not np.isnan(got).all(), "the tiles behind the missing producer are NaN, the others are not"
-        ctx.tune("fused_debug_drop", -1)
-        with pytest.raises(Exception, match="timed out"):
-            lo.mul(res, K, x, 1.0, 0.0)              # reported (and repaired) at the next apply
-        lo.mul(res, K, x, 1.0, 0.0)                  # the one-launch form is off now: two launches
-        torch.cuda.synchronize()
-        assert rel(res.cpu().numpy(), want) <= 1e-12
-        ctx.tune("kron_fuse", 1)                     # counters were re-armed: the one launch works again, repeatedly
-        for _ in range(4):
-            res.zero_()
-            lo.mul(res, K, x, 1.0, 0.0)
-        torch.cuda.synchronize()
-        assert rel(res.cpu().numpy(), want) <= 1e-12
-    finally:
-        ctx.tune("fused_debug_drop", -1)
-        ctx.tune("fused_timeout_ms", 2000)
-        for key in ("kron_fuse", "house_fused", "qn_fused_small", "qn_persist", "herm_single"):
-            ctx.tune(key, 1)
+        with ctx.tuned(fused_timeout_ms=30):
+            with ctx.tuned(fused_debug_drop=3):
+                t0 = time.perf_counter()
+                lo.mul(res, K, x, 1.0, 0.0)          # the launch succeeds; the consumers of workgroup 3's row block give up
+                torch.cuda.synchronize()
+                assert time.perf_counter() - t0 < 5.0
+                got = res.cpu().numpy()
+                assert np.isnan(got).any() and not np.isnan(got).all(), "the tiles behind the missing producer are NaN, the others are not"
+            with pytest.raises(Exception, match="timed out"):
+                lo.mul(res, K, x, 1.0, 0.0)          # reported (and repaired) at the next apply
+            lo.mul(res, K, x, 1.0, 0.0)              # the one-launch form is off now: two launches
+            torch.cuda.synchronize()
+            assert rel(res.cpu().numpy(), want) <= 1e-12
+            with ctx.tuned(kron_fuse=1):             # counters were re-armed: the one launch works again, repeatedly
+                for _ in range(4):
+                    res.zero_()
+                    lo.mul(res, K, x, 1.0, 0.0)
+                torch.cuda.synchronize()
+                assert rel(res.cpu().numpy(), want) <= 1e-12
 
 
 # ---- the one-launch form: where it runs, and its edge shapes ------------------------------------------------------------
@@ -552,29 +543,25 @@ def test_kron_one_launch_form_runs_wherever_the_gate_admits_it(lo, dev, dtype):
     num_cu = ctx.info()["num_cu"]
     npd = NP[dtype]
     admitted = 0
-    try:
-        for shape in GATE_SHAPES:
-            (am, an), (bp, bq) = shape
-            rng = np.random.default_rng(am * bq)
-            K = lo.kron(colmajor(rng.uniform(-1, 1, (am, an)).astype(npd), dev), colmajor(rng.uniform(-1, 1, (bp, bq)).astype(npd), dev))
-            x = T(rng.uniform(-1, 1, an * bq).astype(npd), dev)
-            res = torch.empty(am * bp, dtype=dtype, device=dev)
-            gate = _fused_gate(shape, dtype, num_cu)
-            admitted += gate
-            ctx.tune("kron_fuse", 1)
+    for shape in GATE_SHAPES:
+        (am, an), (bp, bq) = shape
+        rng = np.random.default_rng(am * bq)
+        K = lo.kron(colmajor(rng.uniform(-1, 1, (am, an)).astype(npd), dev), colmajor(rng.uniform(-1, 1, (bp, bq)).astype(npd), dev))
+        x = T(rng.uniform(-1, 1, an * bq).astype(npd), dev)
+        res = torch.empty(am * bp, dtype=dtype, device=dev)
+        gate = _fused_gate(shape, dtype, num_cu)
+        admitted += gate
+        with ctx.tuned(kron_fuse=1):
             got = _kron_launches(lo, res, K, x)
             assert got == 1 if gate else got >= 2, (shape, gate, got)
             if gate:
                 assert _kron_launches(lo, res, K, x, 0.75, -1.25) == 1, shape
-                ctx.tune("kron_fuse", 0)
-                assert _kron_launches(lo, res, K, x) == 2, shape
-                ctx.tune("kron_fuse", 1)
+                with ctx.tuned(kron_fuse=0):
+                    assert _kron_launches(lo, res, K, x) == 2, shape
                 if am * bp == an * bq:                                # square: mul!(x, K, x)
                     l0 = _launches(lo)
                     lo.mul(x, K, x)
                     assert _launches(lo) - l0 == 2, shape
-    finally:
-        ctx.tune("kron_fuse", 1)
     assert admitted >= 4
 
 
@@ -590,23 +577,19 @@ def test_kron_one_launch_form_on_row_blocks_that_share_a_cache_line(lo, dev, dty
     rng = np.random.default_rng(am + bp)
     A, B = rng.uniform(-1, 1, (am, an)).astype(npd), rng.uniform(-1, 1, (bp, bq)).astype(npd)
     K = lo.kron(colmajor(A, dev), colmajor(B, dev))
-    try:
-        for rep in range(3):
-            xh = rng.uniform(-1, 1, an * bq).astype(npd)
-            x = T(xh, dev)
-            got = {}
-            for fuse in (1, 0):
-                ctx.tune("kron_fuse", fuse)
+    for rep in range(3):
+        xh = rng.uniform(-1, 1, an * bq).astype(npd)
+        x = T(xh, dev)
+        got = {}
+        for fuse in (1, 0):
+            with ctx.tuned(kron_fuse=fuse):
                 got[fuse] = torch.full((am * bp,), float("nan"), dtype=dtype, device=dev)
                 lo.mul(got[fuse], K, x)
-            ctx.tune("kron_fuse", 1)
-            assert torch.equal(got[1], got[0]), (rep, int((got[1] != got[0]).nonzero()[0]))
-            want = oracle.kron_mul(np.empty(am * bp), A.astype(np.float64), B.astype(np.float64), xh.astype(np.float64), 1.0, 0.0)
-            err = np.abs(got[1].cpu().numpy().astype(np.float64) - want) / (np.abs(want) + np.abs(want).max() * 1e-3)
-            assert err.max() <= tol * 100, (rep, int(err.argmax()), float(err.max()))
-            assert rel(got[1].cpu().numpy(), want) <= tol
-    finally:
-        ctx.tune("kron_fuse", 1)
+        assert torch.equal(got[1], got[0]), (rep, int((got[1] != got[0]).nonzero()[0]))
+        want = oracle.kron_mul(np.empty(am * bp), A.astype(np.float64), B.astype(np.float64), xh.astype(np.float64), 1.0, 0.0)
+        err = np.abs(got[1].cpu().numpy().astype(np.float64) - want) / (np.abs(want) + np.abs(want).max() * 1e-3)
+        assert err.max() <= tol * 100, (rep, int(err.argmax()), float(err.max()))
+        assert rel(got[1].cpu().numpy(), want) <= tol
 
 
 def test_kron_after_the_no_wait_mode_matches_the_oracle(lo, dev):
@@ -619,13 +602,10 @@ def test_kron_after_the_no_wait_mode_matches_the_oracle(lo, dev):
     xh = rng.uniform(-1, 1, 512 * 512)
     x, res = T(xh, dev), torch.empty(512 * 512, dtype=torch.float64, device=dev)
     want = oracle.kron_mul(np.empty(512 * 512), A, B, xh, 1.0, 0.0)
-    try:
-        ctx.tune("kron_fuse", 2)
+    with ctx.tuned(kron_fuse=2):
         for _ in range(3):
             lo.mul(res, K, x)
         torch.cuda.synchronize()
-    finally:
-        ctx.tune("kron_fuse", 1)
     for _ in range(3):
         res.fill_(float("nan"))
         lo.mul(res, K, x)

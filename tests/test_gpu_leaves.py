@@ -557,12 +557,9 @@ def test_single_launch_householder_matches_two_pass_and_oracle(lo, dev):
                     fl = oracle.scalar_flags(NP[dtype], alpha, beta)
                     want = oracle.householder_mul(r0.copy(), h, v, float(alpha), float(beta), flags=fl)
                     assert rel(res.cpu().numpy(), want) <= tol, (dtype, n, off, alpha, beta)
-                    ctx.tune("house_fused", 0)
-                    try:
+                    with ctx.tuned(house_fused=0):
                         res2 = rb.clone()[off:]
                         lo.mul(res2, H, vt, alpha, beta)
-                    finally:
-                        ctx.tune("house_fused", 1)
                     assert rel(res.cpu().numpy(), res2.cpu().numpy()) <= tol
     # the 257 ... 512-workgroup range really is ONE launch, and one workgroup per CU (tune house_fused_per_cu = 1) sends it to two passes
     def launches():
@@ -578,13 +575,10 @@ def test_single_launch_householder_matches_two_pass_and_oracle(lo, dev):
     l0 = launches()
     lo.mul(res, H, v, 1.0, 0.0)
     assert launches() - l0 == 1
-    ctx.tune("house_fused_per_cu", 1)
-    try:
+    with ctx.tuned(house_fused_per_cu=1):
         l0 = launches()
         lo.mul(res, H, v, 1.0, 0.0)
         assert launches() - l0 >= 2
-    finally:
-        ctx.tune("house_fused_per_cu", 2)
     # a NaN in v poisons the dot: every element becomes NaN (and the exchange does not hang on a NaN partial)
     n = 70_000
     h = torch.full((n,), 1.0 / np.sqrt(n), dtype=torch.float64, device=dev)
@@ -655,25 +649,22 @@ def test_householder_update_pass_summing_the_partials_is_bit_identical(lo, dev, 
     from linearoperators_jl_amd.device import get_ctx
     ctx = get_ctx(dev)
     gen = torch.Generator(device=dev).manual_seed(5)
-    try:
-        for n in (1 << 20 | 1, 3_000_001, 1 << 22, (1 << 23) - 3):
-            hb = torch.rand(n + 1, dtype=dtype, device=dev, generator=gen) - 0.5
-            hb /= hb.norm()
-            vb = torch.rand(n + 1, dtype=dtype, device=dev, generator=gen) * 2 - 1
-            r0 = torch.rand(n, dtype=dtype, device=dev, generator=gen)
-            for off in (0, 1):
-                h, v = hb[off:off + n], vb[off:off + n]
-                H = lo.opHouseholder(h)
-                for a, b in ((1.0, 0.0), (2.0, -3.0)):
-                    got = {}
-                    for inline in (1 << 23, 0):
-                        ctx.tune("house_inline_n", inline)
+    for n in (1 << 20 | 1, 3_000_001, 1 << 22, (1 << 23) - 3):
+        hb = torch.rand(n + 1, dtype=dtype, device=dev, generator=gen) - 0.5
+        hb /= hb.norm()
+        vb = torch.rand(n + 1, dtype=dtype, device=dev, generator=gen) * 2 - 1
+        r0 = torch.rand(n, dtype=dtype, device=dev, generator=gen)
+        for off in (0, 1):
+            h, v = hb[off:off + n], vb[off:off + n]
+            H = lo.opHouseholder(h)
+            for a, b in ((1.0, 0.0), (2.0, -3.0)):
+                got = {}
+                for inline in (1 << 23, 0):
+                    with ctx.tuned(house_inline_n=inline):
                         res = r0.clone()
                         lo.mul(res, H, v, a, b)
                         got[inline] = res
-                    assert torch.equal(got[1 << 23], got[0]), (n, off, a, b)
-    finally:
-        ctx.tune("house_inline_n", 1 << 23)
+                assert torch.equal(got[1 << 23], got[0]), (n, off, a, b)
 
 
 def test_single_launch_householder_timeout_is_an_error_not_a_hang(lo, dev):
@@ -691,54 +682,42 @@ def test_single_launch_householder_timeout_is_an_error_not_a_hang(lo, dev):
     dv = torch.from_numpy(v).to(dev)
     res = torch.zeros(n, dtype=torch.float64, device=dev)
     want = oracle.householder_mul(np.empty(n), h, v, 1.0, 0.0)
-    try:
-        lo.mul(res, H, dv, 1.0, 0.0)
-        torch.cuda.synchronize()
-        assert rel(res.cpu().numpy(), want) <= 1e-12
-        ctx.tune("fused_timeout_ms", 20)
-        ctx.tune("fused_debug_drop", 1)
-        t0 = time.perf_counter()
-        lo.mul(res, H, dv, 1.0, 0.0)                 # the launch itself succeeds; its workgroups give up after ~20 ms
-        torch.cuda.synchronize()
-        assert time.perf_counter() - t0 < 5.0
-        assert bool(torch.isnan(res).all()), "a timed-out single-launch apply must not leave plausible numbers behind"
-        ctx.tune("fused_debug_drop", -1)
+    lo.mul(res, H, dv, 1.0, 0.0)
+    torch.cuda.synchronize()
+    assert rel(res.cpu().numpy(), want) <= 1e-12
+    # a fault switches all the single-launch forms off: the exit of this block puts them back
+    with ctx.tuned(house_fused=1, qn_fused_small=1, qn_persist=1, herm_single=1, kron_fuse=1, fused_timeout_ms=20):
+        with ctx.tuned(fused_debug_drop=1):
+            t0 = time.perf_counter()
+            lo.mul(res, H, dv, 1.0, 0.0)             # the launch itself succeeds; its workgroups give up after ~20 ms
+            torch.cuda.synchronize()
+            assert time.perf_counter() - t0 < 5.0
+            assert bool(torch.isnan(res).all()), "a timed-out single-launch apply must not leave plausible numbers behind"
         with pytest.raises(Exception, match="timed out"):
             lo.mul(res, H, dv, 1.0, 0.0)             # reported (and repaired) at the next single-launch apply
         lo.mul(res, H, dv, 1.0, 0.0)                 # single-launch forms are off now: two passes
         torch.cuda.synchronize()
         assert rel(res.cpu().numpy(), want) <= 1e-12
-        ctx.tune("house_fused", 1)                   # the exchange slots were re-armed: the single launch works again
-        for _ in range(5):
-            res.zero_()
+        with ctx.tuned(house_fused=1):               # the exchange slots were re-armed: the single launch works again
+            for _ in range(5):
+                res.zero_()
+                lo.mul(res, H, dv, 1.0, 0.0)
+            torch.cuda.synchronize()
+            assert rel(res.cpu().numpy(), want) <= 1e-12
+            # the same fault is also reported by mxlo_ctx_sync when no further apply follows; and the wait lasts what the
+            # tune key says (the device's constant-rate clock, hipDeviceAttributeWallClockRate): 300 ms here
+            with ctx.tuned(fused_debug_drop=0, fused_timeout_ms=300):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                lo.mul(res, H, dv, 1.0, 0.0)
+                with pytest.raises(Exception, match="timed out"):
+                    ctx.sync()
+                waited = time.perf_counter() - t0
+                assert 0.25 <= waited <= 1.5, waited
+        with ctx.tuned(house_fused=1):
             lo.mul(res, H, dv, 1.0, 0.0)
-        torch.cuda.synchronize()
-        assert rel(res.cpu().numpy(), want) <= 1e-12
-        # the same fault is also reported by mxlo_ctx_sync when no further apply follows; and the wait lasts what the
-        # tune key says (the device's constant-rate clock, hipDeviceAttributeWallClockRate): 300 ms here
-        ctx.tune("fused_debug_drop", 0)
-        ctx.tune("fused_timeout_ms", 300)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        lo.mul(res, H, dv, 1.0, 0.0)
-        with pytest.raises(Exception, match="timed out"):
             ctx.sync()
-        waited = time.perf_counter() - t0
-        assert 0.25 <= waited <= 1.5, waited
-        ctx.tune("fused_timeout_ms", 20)
-        ctx.tune("fused_debug_drop", -1)
-        ctx.tune("house_fused", 1)
-        lo.mul(res, H, dv, 1.0, 0.0)
-        ctx.sync()
-        assert rel(res.cpu().numpy(), want) <= 1e-12
-    finally:
-        ctx.tune("fused_debug_drop", -1)
-        ctx.tune("fused_timeout_ms", 2000)
-        ctx.tune("house_fused", 1)
-        ctx.tune("qn_fused_small", 1)
-        ctx.tune("qn_persist", 1)
-        ctx.tune("herm_single", 1)
-        ctx.tune("kron_fuse", 1)
+            assert rel(res.cpu().numpy(), want) <= 1e-12
 
 
 def test_graph_replay_on_its_capture_stream_is_ordered_with_the_ctx_stream(lo, dev):

@@ -132,7 +132,8 @@ def launches(lo):
     return a[10]
 
 
-FUSED_KEYS = ("house_fused", "qn_fused_small", "qn_persist", "herm_single", "kron_fuse")
+# what a single-launch fault switches off: named in a tuned(...) block, its exit puts them back
+FUSED_ON = dict.fromkeys(("house_fused", "qn_fused_small", "qn_persist", "herm_single", "kron_fuse"), 1)
 
 
 # =========================================================================== 1. elementwise real leaves, bit for bit
@@ -292,9 +293,7 @@ def test_householder_nonfinite_every_form(lo, dev, dtype, form):
     ctx = lo.get_ctx(dev)
     fused, inline_n, nlaunch = HOUSE_FORMS[form]
     rng = np.random.default_rng(2024)
-    ctx.tune("house_fused", fused)
-    ctx.tune("house_inline_n", inline_n)
-    try:
+    with ctx.tuned(house_fused=fused, house_inline_n=inline_n):
         for n in (4099, 1 << 16):
             for case in HOUSE_CASES:
                 for p in ((5,) if case in ("big_v", "small_v") else (5, n - 700, n - 1)):
@@ -313,9 +312,6 @@ def test_householder_nonfinite_every_form(lo, dev, dtype, form):
                         fl = oracle.scalar_flags(npd, a, b)
                         want = oracle.householder_mul(r0.copy(), h, v, a, b, flags=fl)
                         check_against_oracle(res.cpu().numpy(), want, tol=TOL_HOUSE[npd], what=str((form, n, case, p, a, b)))
-    finally:
-        ctx.tune("house_fused", 1)
-        ctx.tune("house_inline_n", 1 << 23)
     ctx.sync()
 
 
@@ -330,23 +326,18 @@ def test_complex_householder_nan_in_v(lo, dev, dtype):
     h = rng.standard_normal(n) + 1j * rng.standard_normal(n)
     h = (h / np.linalg.norm(h)).astype(npd)
     payloads = [np.nan] + ([np.array([SENTINEL_BITS], np.uint64).view(np.float64)[0]] if dtype == torch.complex128 else [])
-    ctx.tune("fused_timeout_ms", 250)
-    try:
+    with ctx.tuned(fused_timeout_ms=250, **FUSED_ON):
         for pay in payloads:
             for fused in (1, 0):
-                ctx.tune("house_fused", fused)
-                v = (rng.uniform(-1, 1, n) + 1j * rng.uniform(-1, 1, n)).astype(npd)
-                _real_view(v)[2 * 4321] = pay
-                res = torch.empty(n, dtype=dtype, device=dev)
-                lo.mul(res, lo.opHouseholder(T(h, dev)), T(v, dev), 1.0, 0.0)
-                ctx.sync()
-                want = oracle.householder_mul(np.empty(n, npd), h, v, 1.0, 0.0, flags=oracle.scalar_flags(npd, 1.0, 0.0))
-                assert np.isnan(_real_view(want)).all()
-                check_against_oracle(res.cpu().numpy(), want, tol=TOL_CHOUSE[npd], what=f"complex householder fused={fused}")
-    finally:
-        ctx.tune("fused_timeout_ms", 2000)
-        for key in FUSED_KEYS:
-            ctx.tune(key, 1)
+                with ctx.tuned(house_fused=fused):
+                    v = (rng.uniform(-1, 1, n) + 1j * rng.uniform(-1, 1, n)).astype(npd)
+                    _real_view(v)[2 * 4321] = pay
+                    res = torch.empty(n, dtype=dtype, device=dev)
+                    lo.mul(res, lo.opHouseholder(T(h, dev)), T(v, dev), 1.0, 0.0)
+                    ctx.sync()
+                    want = oracle.householder_mul(np.empty(n, npd), h, v, 1.0, 0.0, flags=oracle.scalar_flags(npd, 1.0, 0.0))
+                    assert np.isnan(_real_view(want)).all()
+                    check_against_oracle(res.cpu().numpy(), want, tol=TOL_CHOUSE[npd], what=f"complex householder fused={fused}")
 
 
 # =========================================================================== 3. the sentinel payload
@@ -377,8 +368,7 @@ def _sentinel_leg(lo, dev, apply, x_clean, pos, want_clean, tol, what):
     """One apply with the empty-slot NaN at x[pos]: returns without raising, all NaN, ONE launch; then the next ordinary
     apply on the same ctx is right and still one launch. `apply(x_tensor) -> result tensor`."""
     ctx = lo.get_ctx(dev)
-    ctx.tune("fused_timeout_ms", 250)
-    try:
+    with ctx.tuned(fused_timeout_ms=250, **FUSED_ON):
         xt = T(x_clean, dev)
         apply(xt)                                        # warm: slot layouts armed for this shape
         l0 = launches(lo)
@@ -400,10 +390,6 @@ def _sentinel_leg(lo, dev, apply, x_clean, pos, want_clean, tol, what):
         ctx.sync()
         assert nl == 1, (what, "after", nl)
         check_against_oracle(got.cpu().numpy(), want_clean, tol=tol, what=what + " (clean, after)")
-    finally:
-        ctx.tune("fused_timeout_ms", 2000)
-        for key in FUSED_KEYS:
-            ctx.tune(key, 1)
 
 
 def test_sentinel_payload_single_launch_householder(lo, dev):
@@ -449,12 +435,8 @@ def test_sentinel_payload_quasi_newton_single_launch(lo, dev, kind, form):
         res = torch.empty(n, dtype=torch.float64, device=dev)
         lo.mul(res, op, xt, 1.0, 0.0)
         return res
-    if form == "persist":
-        ctx.tune("qn_persist_min_bytes", 0)
-    try:
+    with ctx.tuned(**({"qn_persist_min_bytes": 0} if form == "persist" else {})):
         _sentinel_leg(lo, dev, apply, x, 777, want, TOL_QN_ALT[np.float64], f"quasi-Newton {form} form, {kind}")
-    finally:
-        ctx.tune("qn_persist_min_bytes", 32 << 20)
 
 
 def test_sentinel_payload_single_launch_hermitian(lo, dev):
@@ -528,9 +510,7 @@ def _qn_apply_cases(lo, dev, kind, dtype, n, mem, schedules, scaled=True):
         assert amb.mean() <= 0.01
         for sched, small, persist in schedules:
             what = f"{kind} {label} {sched} n={n} mem={mem} {npd.__name__}"
-            ctx.tune("qn_fused_small", small)
-            ctx.tune("qn_persist", persist)
-            try:
+            with ctx.tuned(qn_fused_small=small, qn_persist=persist):
                 def run(xv, a=1.0, b=0.0):
                     res = T(r0.copy(), dev)
                     if b == 0:
@@ -551,9 +531,6 @@ def _qn_apply_cases(lo, dev, kind, dtype, n, mem, schedules, scaled=True):
                         xs = reduction_operand((x * sc).astype(npd), npd, scaled=True)
                         want = (base.astype(np.float64) * float(sc)).astype(npd)   # the apply is linear in x
                         check_against_oracle(run(xs), want, tol=tol, what=what + f" x * {sc:g}")
-            finally:
-                ctx.tune("qn_fused_small", 1)
-                ctx.tune("qn_persist", 1)
     ctx.sync()
 
 
@@ -577,20 +554,12 @@ def test_quasi_newton_apply_nonfinite_x(lo, dev, dtype, kind, n, mem):
 def test_quasi_newton_persistent_apply_nonfinite_x(lo, dev, dtype, kind):
     """The persistent form (n = 2^19, mem 5, `qn_persist_min_bytes` = 0): NaN and Inf in x as above."""
     ctx = lo.get_ctx(dev)
-    ctx.tune("qn_persist_min_bytes", 0)
-    try:
+    with ctx.tuned(qn_persist_min_bytes=0):
         _qn_apply_cases(lo, dev, kind, dtype, 1 << 19, 5, QN_SCHEDULES[:1], scaled=False)
-    finally:
-        ctx.tune("qn_persist_min_bytes", 32 << 20)
 
 
 # =========================================================================== 5. push! with non-finite pairs
-def _push_tunes(ctx):
-    for fused in (1, 0):
-        for posted in (1, 0):
-            ctx.tune("push_fused", fused)
-            ctx.tune("push_posted", posted)
-            yield fused, posted
+PUSH_TUNES = [(fused, posted) for fused in (1, 0) for posted in (1, 0)]
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
@@ -608,8 +577,8 @@ def test_lbfgs_push_nan_and_inf_pairs(lo, dev, dtype, kind):
     prs = qn_pairs(rng, n, 3, npd)
     x = rng.uniform(-1, 1, n).astype(npd)
     fl = oracle.scalar_flags(npd, 1.0, 0.0)
-    try:
-        for fused, posted in _push_tunes(ctx):
+    for fused, posted in PUSH_TUNES:
+        with ctx.tuned(push_fused=fused, push_posted=posted):
             fresh, _ = make_qn(lo, dev, kind, dtype, n, mem)       # (same schedule: the two schedules sum their dots in other orders)
             for s, y in prs:
                 lo.push(fresh, T(s, dev), T(y, dev))
@@ -656,9 +625,6 @@ def test_lbfgs_push_nan_and_inf_pairs(lo, dev, dtype, kind):
                     for s, y in prs:
                         lo.push(op, T(s, dev), T(y, dev))
                     assert torch.equal(op * T(x, dev), fresh_out), what + ": reset! + clean pushes == fresh operator"
-    finally:
-        ctx.tune("push_fused", 1)
-        ctx.tune("push_posted", 1)
     ctx.sync()
 
 
@@ -675,8 +641,8 @@ def test_damped_lbfgs_push_nan_pair_takes_the_oracles_branch(lo, dev, dtype):
     x = rng.uniform(-1, 1, n).astype(npd)
     g = rng.uniform(-1, 1, n).astype(npd)
     fl = oracle.scalar_flags(npd, 1.0, 0.0)
-    try:
-        for fused, posted in _push_tunes(ctx):
+    for fused, posted in PUSH_TUNES:
+        with ctx.tuned(push_fused=fused, push_posted=posted):
             for off in (0, 1):
                 for kind, with_bs in (("fwd", False), ("fwd", True), ("inv", False), ("inv", True)):
                     what = str((kind, with_bs, npd.__name__, fused, posted, off))
@@ -702,9 +668,6 @@ def test_damped_lbfgs_push_nan_pair_takes_the_oracles_branch(lo, dev, dtype):
                     want = O.mul(np.empty(n, npd), x, 1.0, 0.0, flags=fl)
                     assert np.isnan(want).all()
                     check_against_oracle((op * T(x, dev)).cpu().numpy(), want, tol=TOL_QN_ALT[npd], what=what)
-    finally:
-        ctx.tune("push_fused", 1)
-        ctx.tune("push_posted", 1)
     ctx.sync()
 
 
@@ -719,8 +682,8 @@ def test_lsr1_push_rejects_nonfinite_pairs_and_leaves_the_operator_untouched(lo,
     n, mem = 4099, 5
     rng = np.random.default_rng(14)
     x = T(rng.uniform(-1, 1, n).astype(npd), dev)
-    try:
-        for fused, posted in _push_tunes(ctx):
+    for fused, posted in PUSH_TUNES:
+        with ctx.tuned(push_fused=fused, push_posted=posted):
             op, O = make_qn(lo, dev, "lsr1", dtype, n, mem)
             op.set_push_mode(push_mode)
             for s, y in qn_pairs(rng, n, mem + 2, npd):
@@ -745,9 +708,6 @@ def test_lsr1_push_rejects_nonfinite_pairs_and_leaves_the_operator_untouched(lo,
                     assert torch.equal(after[0], before[0]) and torch.equal(after[1], before[1]), what
                     assert after[2][0] == before[2][0] and np.array_equal(after[2][1], before[2][1]) \
                         and np.array_equal(after[2][2], before[2][2]), what
-    finally:
-        ctx.tune("push_fused", 1)
-        ctx.tune("push_posted", 1)
     ctx.sync()
 
 
@@ -777,8 +737,7 @@ def test_hermitian_nonfinite(lo, dev, dtype, n, pad, single):
         big[:, :n] = T(np.ascontiguousarray(M.T), dev)
         return big[:, :n].t()
 
-    ctx.tune("herm_single", single)
-    try:
+    with ctx.tuned(herm_single=single):
         for case in ("nan_v", "inf_v", "nan_d", "inf_L", "big_v"):
             Ac, dc, vc = A.copy(), d.copy(), v.copy()
             i, j = n - 2, n // 3
@@ -806,8 +765,6 @@ def test_hermitian_nonfinite(lo, dev, dtype, n, pad, single):
                 if case == "inf_v":
                     assert np.isinf(want).all()
                 check_against_oracle(res.cpu().numpy(), want, tol=TOL_HERM[npd], what=str((n, pad, single, case, a, b)))
-    finally:
-        ctx.tune("herm_single", 1)
     ctx.sync()
 
 
@@ -1088,8 +1045,7 @@ def test_block_apply_poison_stays_in_its_column(lo, dev, dtype, family):
     V = unit_mags(rng, (nin, k), npd)
     R0 = rng.standard_normal((nout, k)).astype(npd)
     pos = nin // 2 + 1
-    ctx.tune("herm_single", 0 if family == "hermitian_single_off" else 1)
-    try:
+    with ctx.tuned(herm_single=0 if family == "hermitian_single_off" else 1):
         for a, b in ((1.0, 0.0), (2.0, -3.0)):
             def run(Vh):
                 R = _colmajor(np.full_like(R0, np.nan) if b == 0 else R0, 3, dtype, dev)
@@ -1110,8 +1066,6 @@ def test_block_apply_poison_stays_in_its_column(lo, dev, dtype, family):
                 assert not np.isfinite(want).all()
                 check_against_oracle(got[:, j].copy(), want, tol=tol, atol=atol_of and atol_of(Vp[:, j], a, b),
                                      what=str((family, val, "poisoned column", a, b)))
-    finally:
-        ctx.tune("herm_single", 1)
     ctx.sync()
 
 

@@ -130,8 +130,7 @@ def test_hermitian_block_apply_is_bit_identical_to_the_column_loop(lo, dev, n, d
         big[:, :X.shape[0]] = T(np.ascontiguousarray(X.T), dev)
         return big[:, :X.shape[0]].t()
 
-    ctx.tune("herm_single", 0)                                     # the column loop below must be the same two-launch form
-    try:
+    with ctx.tuned(herm_single=0):   # the column loop below must be the same two-launch form
         for k, pad, (a, b) in ((1, 0, (1.0, 0.0)), (2, 1, (2.0, -3.0)), (3, 0, (1.0, 0.0)), (4, 2, (1.5, 0.5)), (7, 1, (2.0, -3.0))):
             H = lo.opHermitian(T(d, dev), cm(A, pad % 2))
             Vh, R0 = rng.standard_normal((n, k)).astype(npd), rng.standard_normal((n, k)).astype(npd)
@@ -144,9 +143,6 @@ def test_hermitian_block_apply_is_bit_identical_to_the_column_loop(lo, dev, n, d
             assert torch.equal(res, cols), (n, k, pad)
             want = np.stack([oracle.hermitian_mul(R0[:, j].copy(), d, np.tril(A, -1), Vh[:, j].copy(), a, b, flags=fl) for j in range(k)], axis=1)
             assert rel(res.cpu().numpy(), want) <= tol, (n, k)
-    finally:
-        ctx.tune("herm_single", 1)
-        ctx.tune("kron_fuse", 1)
     with pytest.raises(lo.LinearOperatorException):
         lo.mul(torch.empty(n, 2, dtype=dtype, device=dev), H, torch.empty(n, 3, dtype=dtype, device=dev), 1.0, 0.0)
 
@@ -165,16 +161,13 @@ def test_hermitian_strip_order_does_not_change_a_bit(lo, dev, dtype, n):
     H = lo.opHermitian(d, M)
     ctx = lo.get_ctx(dev)
     got = {}
-    try:
-        for order in (0, 1):
-            ctx.tune("herm_order", order)
+    for order in (0, 1):
+        with ctx.tuned(herm_order=order):
             r = torch.empty(n, dtype=dtype, device=dev)
             lo.mul(r, H, x, 0.7, 0.0)
             R = torch.empty(4, n, dtype=dtype, device=dev).t()
             lo.mul(R, H, V, 1.0, 0.0)
             got[order] = (r, R)
-    finally:
-        ctx.tune("herm_order", 1)
     assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1])
 
 
@@ -206,25 +199,18 @@ def test_hermitian_load_policy_poll_interval_and_strip_width_do_not_change_the_r
         lo.mul(R, H, V, 1.0, 0.0)
         return r, R
 
-    try:
-        base = run()
-        for key, values, default in (("herm_nt", (0, 1), -1), ("herm_poll_sleep", (1, 64), 4)):
-            for val in values:
-                ctx.tune(key, val)
+    base = run()
+    for key, values in (("herm_nt", (0, 1)), ("herm_poll_sleep", (1, 64))):
+        for val in values:
+            with ctx.tuned(**{key: val}):
                 got = run()
-                assert torch.equal(got[0], base[0]) and (base[1] is None or torch.equal(got[1], base[1])), (key, val)
-            ctx.tune(key, default)
-        if not dtype.is_complex:
-            for width in (1, 2):
-                ctx.tune("herm_strip", width)
+            assert torch.equal(got[0], base[0]) and (base[1] is None or torch.equal(got[1], base[1])), (key, val)
+    if not dtype.is_complex:
+        for width in (1, 2):
+            with ctx.tuned(herm_strip=width):
                 got = run()
-                tol = 1e-12 if dtype == torch.float64 else 3e-5
-                assert float((got[0].double() - base[0].double()).norm() / base[0].double().norm()) <= tol, width
-            ctx.tune("herm_strip", 0)
-    finally:
-        ctx.tune("herm_nt", -1)
-        ctx.tune("herm_poll_sleep", 4)
-        ctx.tune("herm_strip", 0)
+            tol = 1e-12 if dtype == torch.float64 else 3e-5
+            assert float((got[0].double() - base[0].double()).norm() / base[0].double().norm()) <= tol, width
 
 
 def test_hermitian_single_launch_is_bit_identical_to_the_two_launch_form(lo, dev):
@@ -247,42 +233,37 @@ def test_hermitian_single_launch_is_bit_identical_to_the_two_launch_form(lo, dev
         lo._lib.call("mxlo_debug_counters", a)
         return a[10]
 
-    ctx.tune("herm_single_max_n", 8192)                           # (the default rule is by size — 112 MiB of triangle —, see common.h)
-    for dtype, n in cases:
-        npd = NP[dtype]
-        if (dtype, n) not in ops:
-            A = rng.standard_normal((n, n)).astype(npd)
-            A[np.triu_indices(n)] = np.nan                        # never read
-            d, v, r0 = (rng.standard_normal(n).astype(npd) for _ in range(3))
-            ops[(dtype, n)] = (lo.opHermitian(T(d, dev), TM(A, dev)), A, d, v, r0)
-        H, A, d, v, r0 = ops[(dtype, n)]
-        got = {}
-        for single in (1, 0, 1):
-            ctx.tune("herm_single", single)
-            try:
-                res = T(r0.copy(), dev)
-                l0 = launches()
-                lo.mul(res, H, T(v, dev), 3.0, -4.0)
-                nl = launches() - l0
-                assert (nl <= 2) if single else (nl == 2), (dtype, n, single, nl)   # 1, or 2 when the slots were re-armed for a new layout
-                got.setdefault(single, []).append(res.cpu().numpy())
-            finally:
-                ctx.tune("herm_single", 1)
-                ctx.tune("kron_fuse", 1)
-        assert np.array_equal(got[1][0], got[0][0]) and np.array_equal(got[1][0], got[1][1]), (dtype, n)
-        fl = oracle.SCALARS_F64 if dtype == torch.float32 else 0
-        want = oracle.hermitian_mul(r0.copy(), d, np.tril(A, -1), v, 3.0, -4.0, flags=fl)
-        assert rel(got[1][0], want) <= (1e-12 if dtype == torch.float64 else 3e-5), (dtype, n)
-    H, A, d, v, r0 = ops[(torch.float64, 4096)]
-    vt, res = T(v, dev), torch.empty(4096, dtype=torch.float64, device=dev)
-    lo.mul(res, H, vt, 1.0, 0.0)
-    first = res.clone()
-    l0 = launches()
-    for _ in range(200):
+    with ctx.tuned(herm_single_max_n=8192):                       # (the default rule is by size — 112 MiB of triangle —, see tune_keys.def)
+        for dtype, n in cases:
+            npd = NP[dtype]
+            if (dtype, n) not in ops:
+                A = rng.standard_normal((n, n)).astype(npd)
+                A[np.triu_indices(n)] = np.nan                        # never read
+                d, v, r0 = (rng.standard_normal(n).astype(npd) for _ in range(3))
+                ops[(dtype, n)] = (lo.opHermitian(T(d, dev), TM(A, dev)), A, d, v, r0)
+            H, A, d, v, r0 = ops[(dtype, n)]
+            got = {}
+            for single in (1, 0, 1):
+                with ctx.tuned(herm_single=single):
+                    res = T(r0.copy(), dev)
+                    l0 = launches()
+                    lo.mul(res, H, T(v, dev), 3.0, -4.0)
+                    nl = launches() - l0
+                    assert (nl <= 2) if single else (nl == 2), (dtype, n, single, nl)   # 1, or 2 when the slots were re-armed for a new layout
+                    got.setdefault(single, []).append(res.cpu().numpy())
+            assert np.array_equal(got[1][0], got[0][0]) and np.array_equal(got[1][0], got[1][1]), (dtype, n)
+            fl = oracle.SCALARS_F64 if dtype == torch.float32 else 0
+            want = oracle.hermitian_mul(r0.copy(), d, np.tril(A, -1), v, 3.0, -4.0, flags=fl)
+            assert rel(got[1][0], want) <= (1e-12 if dtype == torch.float64 else 3e-5), (dtype, n)
+        H, A, d, v, r0 = ops[(torch.float64, 4096)]
+        vt, res = T(v, dev), torch.empty(4096, dtype=torch.float64, device=dev)
         lo.mul(res, H, vt, 1.0, 0.0)
-    assert launches() - l0 == 200                                  # ONE launch per apply
-    assert torch.equal(res, first)
-    ctx.tune("herm_single_max_n", 0)                               # back to the by-size rule
+        first = res.clone()
+        l0 = launches()
+        for _ in range(200):
+            lo.mul(res, H, vt, 1.0, 0.0)
+        assert launches() - l0 == 200                                  # ONE launch per apply
+        assert torch.equal(res, first)
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32, torch.complex128, torch.complex64])
@@ -613,12 +594,9 @@ def test_block_gemv_row_bands_are_bit_identical_to_the_single_applies(lo, dev, d
             assert torch.equal(res, cols), (alpha, beta)
         ref = alpha * (Mh.astype(np.float64) @ Vh) + beta * r0
         assert rel(res.cpu().numpy(), ref) <= tol
-    ctx.tune("gemvb_n_rows", 0)
-    try:
+    with ctx.tuned(gemvb_n_rows=0):
         old = TM(r0, dev)
         lo.mul(old, op, V, 2.0, -0.5)
-    finally:
-        ctx.tune("gemvb_n_rows", 1)
     assert rel(old.cpu().numpy(), 2.0 * (Mh.astype(np.float64) @ Vh) - 0.5 * r0) <= tol
 
 
@@ -768,16 +746,13 @@ def test_dense_mul_row_band_kernel(lo, dev, dtype, m, n, pad):
     tol = 1e-12 if dtype == torch.float64 else 3e-5
     outs = {}
     for rows in (1, 0):
-        ctx.tune("gemv_n_rows", rows)
-        try:
+        with ctx.tuned(gemv_n_rows=rows):
             res = torch.full((m,), float("nan"), dtype=dtype, device=dev)
             lo.mul(res, op, T(v, dev), 1.0, 0.0)
             a = res.cpu().numpy()
             res2 = T(r0.copy(), dev)
             lo.mul(res2, op, T(v, dev), 3.0, -4.0)
             outs[rows] = (a, res2.cpu().numpy())
-        finally:
-            ctx.tune("gemv_n_rows", 1)
     want = A @ v.astype(np.float64)
     for rows in (1, 0):
         assert np.isfinite(outs[rows][0]).all()

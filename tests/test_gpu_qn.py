@@ -375,9 +375,8 @@ def test_allreduce_hook_world1(lo, dev):
         h = rng.standard_normal(n); h /= np.linalg.norm(h)
         v = rng.uniform(-1, 1, n)
         H = lo.opHouseholder(T(h, dev))
-        ctx.tune("house_fused", 0)               # a hooked apply is the two-launch path (the hook sits between the passes):
-        want = (H * T(v, dev)).clone()           # compare with the SAME reduction order, un-hooked
-        ctx.tune("house_fused", 1)
+        with ctx.tuned(house_fused=0):           # a hooked apply is the two-launch path (the hook sits between the passes):
+            want = (H * T(v, dev)).clone()       # compare with the SAME reduction order, un-hooked
         ctx.set_allreduce(hook)
         got = H * T(v, dev)
         assert torch.equal(got, want) and calls == [1]
@@ -388,11 +387,8 @@ def test_allreduce_hook_world1(lo, dev):
         r1 = Hq * T(v, dev)
         assert calls == [8]                      # ONE all-reduce of 2m doubles per apply
         ctx.set_allreduce(None)
-        ctx.tune("qn_fused_small", 0)            # a hooked apply is the four-launch schedule: same reduction order un-hooked
-        try:
+        with ctx.tuned(qn_fused_small=0):        # a hooked apply is the four-launch schedule: same reduction order un-hooked
             assert torch.equal(r1, Hq * T(v, dev))
-        finally:
-            ctx.tune("qn_fused_small", 1)
     finally:
         lo.get_ctx(dev).set_allreduce(None)
         dist.destroy_process_group()
@@ -435,9 +431,8 @@ def test_native_rccl_hook_world1(lo, dev):
     h = rng.standard_normal(n); h /= np.linalg.norm(h)
     v = rng.uniform(-1, 1, n)
     H = lo.opHouseholder(T(h, dev))
-    ctx.tune("house_fused", 0)                   # same (two-launch) reduction order as the hooked apply
-    want = (H * T(v, dev)).clone()
-    ctx.tune("house_fused", 1)
+    with ctx.tuned(house_fused=0):               # same (two-launch) reduction order as the hooked apply
+        want = (H * T(v, dev)).clone()
     hook = lo.sharded.NativeRcclHook(0, 1)
     try:
         hook.install(ctx)
@@ -447,10 +442,9 @@ def test_native_rccl_hook_world1(lo, dev):
             lo.push(B, T(s, dev), T(y, dev))
         r1 = B * T(v, dev)
         ctx.set_allreduce(None)
-        ctx.tune("qn_fused_small", 0)            # same (four-launch) reduction order as the hooked apply
-        assert torch.equal(r1, B * T(v, dev))
+        with ctx.tuned(qn_fused_small=0):        # same (four-launch) reduction order as the hooked apply
+            assert torch.equal(r1, B * T(v, dev))
     finally:
-        ctx.tune("qn_fused_small", 1)
         ctx.set_allreduce(None)
         torch.cuda.synchronize()
         hook.close()
@@ -653,18 +647,17 @@ def test_one_pass_push_matches_two_kernel_schedule_and_oracle(lo, dev, dtype, ki
     make = lo.InverseLBFGSOperator if kind == "inv" else lo.LBFGSOperator
     tol = 1e-9 if dtype == torch.float64 else QN_F32
     ops = {}
-    try:
-        for fused in (1, 0):
-            ctx.tune("push_fused", fused)
+    for fused in (1, 0):
+        with ctx.tuned(push_fused=fused):
             ops[fused] = make(dtype, n, mem=mem, scaling=True, device=dev)
-        Oo = oracle.LBFGS(n, mem=mem, scaling=True, inverse=(kind == "inv"), dtype=npd)
-        x = rng.uniform(-1, 1, n).astype(npd)
-        prs = pairs(rng, n, mem + 4, npd)
-        prs.insert(3, (prs[0][0], (-prs[0][0]).astype(npd)))          # y's < 0: rejected (src/lbfgs.jl:281-284)
-        for k, (s, y) in enumerate(prs):
-            want = Oo.push(s, y)
-            for fused in (1, 0):
-                ctx.tune("push_fused", fused)
+    Oo = oracle.LBFGS(n, mem=mem, scaling=True, inverse=(kind == "inv"), dtype=npd)
+    x = rng.uniform(-1, 1, n).astype(npd)
+    prs = pairs(rng, n, mem + 4, npd)
+    prs.insert(3, (prs[0][0], (-prs[0][0]).astype(npd)))          # y's < 0: rejected (src/lbfgs.jl:281-284)
+    for k, (s, y) in enumerate(prs):
+        want = Oo.push(s, y)
+        for fused in (1, 0):
+            with ctx.tuned(push_fused=fused):
                 if k % 5 == 4:                                         # misaligned views: element offset 1
                     sb, yb = torch.empty(n + 1, dtype=dtype, device=dev), torch.empty(n + 1, dtype=dtype, device=dev)
                     sb[1:].copy_(T(s, dev)); yb[1:].copy_(T(y, dev))
@@ -672,23 +665,21 @@ def test_one_pass_push_matches_two_kernel_schedule_and_oracle(lo, dev, dtype, ki
                 else:
                     lo.push(ops[fused], T(s, dev), T(y, dev))
                 assert ops[fused].data.insert == Oo.insert, (k, fused, want)
-            if k in (0, 3, mem - 1, mem, len(prs) - 1):
-                got = {}
-                for fused in (1, 0):
-                    res = torch.full((n,), float("nan"), dtype=dtype, device=dev)
-                    lo.mul(res, ops[fused], T(x, dev), 1.0, 0.0)
-                    got[fused] = res.cpu().numpy()
-                ref = Oo.mul(np.empty(n, dtype=npd), x, 1.0, 0.0)
-                assert rel(got[1], ref) <= tol and rel(got[0], ref) <= tol, (k, rel(got[1], ref), rel(got[0], ref))
-                assert rel(got[1], got[0]) <= (1e-12 if dtype == torch.float64 else 1e-4), (k, rel(got[1], got[0]))
-        for fused in (1, 0):                                           # replicated scalars of the two schedules
-            assert abs(ops[fused].data.scaling_factor - Oo.scaling_factor) <= 1e-6 * abs(Oo.scaling_factor)
-        if kind == "fwd":
-            d1, d0 = lo.diag(ops[1]).cpu().numpy(), lo.diag(ops[0]).cpu().numpy()
-            assert rel(d1, Oo.diag()) <= tol and rel(d1, d0) <= (1e-12 if dtype == torch.float64 else 1e-4)
-            assert rel(ops[1].data.opnorm_upper_bound, Oo.opnorm_upper_bound) <= 1e-5
-    finally:
-        ctx.tune("push_fused", 1)
+        if k in (0, 3, mem - 1, mem, len(prs) - 1):
+            got = {}
+            for fused in (1, 0):
+                res = torch.full((n,), float("nan"), dtype=dtype, device=dev)
+                lo.mul(res, ops[fused], T(x, dev), 1.0, 0.0)
+                got[fused] = res.cpu().numpy()
+            ref = Oo.mul(np.empty(n, dtype=npd), x, 1.0, 0.0)
+            assert rel(got[1], ref) <= tol and rel(got[0], ref) <= tol, (k, rel(got[1], ref), rel(got[0], ref))
+            assert rel(got[1], got[0]) <= (1e-12 if dtype == torch.float64 else 1e-4), (k, rel(got[1], got[0]))
+    for fused in (1, 0):                                           # replicated scalars of the two schedules
+        assert abs(ops[fused].data.scaling_factor - Oo.scaling_factor) <= 1e-6 * abs(Oo.scaling_factor)
+    if kind == "fwd":
+        d1, d0 = lo.diag(ops[1]).cpu().numpy(), lo.diag(ops[0]).cpu().numpy()
+        assert rel(d1, Oo.diag()) <= tol and rel(d1, d0) <= (1e-12 if dtype == torch.float64 else 1e-4)
+        assert rel(ops[1].data.opnorm_upper_bound, Oo.opnorm_upper_bound) <= 1e-5
 
 
 @pytest.mark.parametrize("kind", ["inv", "fwd", "lsr1"])
@@ -707,31 +698,28 @@ def test_posted_read_back_of_the_push_decision(lo, dev, kind, n):
     rng = np.random.default_rng(n + len(kind))
     make = {"inv": lo.InverseLBFGSOperator, "fwd": lo.LBFGSOperator, "lsr1": lo.LSR1Operator}[kind]
     ops = {}
-    try:
+    for posted in (1, 0, 2):
+        ops[posted] = make(torch.float64, n, mem=mem, scaling=True, device=dev)
+    x = T(rng.uniform(-1, 1, n), dev)
+    prs = pairs(rng, n, 7 if n > 10**6 else mem + 4, np.float64)
+    prs.insert(2, (prs[0][0], -prs[0][0]))                           # y's < 0: rejected by the L-BFGS operators
+    prs.insert(4, (prs[1][0], np.zeros(n)))                          # y = 0: rejected by all three
+    accepted = 0
+    for k, (s, y) in enumerate(prs):
+        got = {}
         for posted in (1, 0, 2):
-            ops[posted] = make(torch.float64, n, mem=mem, scaling=True, device=dev)
-        x = T(rng.uniform(-1, 1, n), dev)
-        prs = pairs(rng, n, 7 if n > 10**6 else mem + 4, np.float64)
-        prs.insert(2, (prs[0][0], -prs[0][0]))                           # y's < 0: rejected by the L-BFGS operators
-        prs.insert(4, (prs[1][0], np.zeros(n)))                          # y = 0: rejected by all three
-        accepted = 0
-        for k, (s, y) in enumerate(prs):
-            got = {}
-            for posted in (1, 0, 2):
-                ctx.tune("push_posted", posted)
+            with ctx.tuned(push_posted=posted):
                 lo.push(ops[posted], T(s, dev), T(y, dev))
                 res = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
                 lo.mul(res, ops[posted], x, 1.0, 0.0)
                 got[posted] = res.cpu().numpy()
-            for posted in (1, 2):
-                assert ops[posted].data.insert == ops[0].data.insert, (k, posted)
-                assert ops[posted].data.scaling_factor == ops[0].data.scaling_factor, (k, posted)
-                assert np.array_equal(got[posted], got[0], equal_nan=True), (k, posted)
-            assert n == 1 or np.isfinite(got[1]).all(), k
-            accepted += int(getattr(ops[1], "_last_push_accepted", True))
-        assert n == 1 or 3 <= accepted <= len(prs) - (0 if kind == "lsr1" else 2)   # both outcomes occurred (L-BFGS)
-    finally:
-        ctx.tune("push_posted", 1)
+        for posted in (1, 2):
+            assert ops[posted].data.insert == ops[0].data.insert, (k, posted)
+            assert ops[posted].data.scaling_factor == ops[0].data.scaling_factor, (k, posted)
+            assert np.array_equal(got[posted], got[0], equal_nan=True), (k, posted)
+        assert n == 1 or np.isfinite(got[1]).all(), k
+        accepted += int(getattr(ops[1], "_last_push_accepted", True))
+    assert n == 1 or 3 <= accepted <= len(prs) - (0 if kind == "lsr1" else 2)   # both outcomes occurred (L-BFGS)
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
@@ -749,28 +737,27 @@ def test_lsr1_streaming_push_matches_apply_based_schedule_and_oracle(lo, dev, dt
     npd = NP[dtype]
     tol = 1e-9 if dtype == torch.float64 else QN_F32
     same = 1e-11 if dtype == torch.float64 else 1e-4
-    try:
-        for n in ((10_006, 6_001) if mem <= 10 else (4_002,)):
-            rng = np.random.default_rng(mem * 11 + n)
-            ops = {}
-            for fused in (1, 0):
-                ctx.tune("push_fused", fused)
+    for n in ((10_006, 6_001) if mem <= 10 else (4_002,)):
+        rng = np.random.default_rng(mem * 11 + n)
+        ops = {}
+        for fused in (1, 0):
+            with ctx.tuned(push_fused=fused):
                 ops[fused] = lo.LSR1Operator(dtype, n, mem=mem, scaling=scaling, device=dev)
-            Oo = oracle.LSR1(n, mem=mem, scaling=scaling, dtype=npd)
-            x = rng.uniform(-1, 1, n).astype(npd)
-            prs = pairs(rng, n, mem + 4, npd)
-            s0 = prs[1][0]
-            prs.insert(0, (s0, s0.copy()))                 # empty memory, B = I: y - B s = 0 exactly, not well defined (:131)
-            prs.insert(3, (s0, (npd(3.0) * s0).astype(npd)))                     # y ∥ s: |y - s/sf| ≈ eps|y| ≪ eps|y||s| (:141)
-            if scaling:
-                yperp = np.zeros(n, npd); yperp[0], yperp[1] = s0[1], -s0[0]     # y's = O(eps): no curvature (:137)
-                prs.insert(5, (s0, yperp))
-            nacc = 0
-            for k, (s, y) in enumerate(prs):
-                want = Oo.push(s, y)
-                nacc += want
-                for fused in (1, 0):
-                    ctx.tune("push_fused", fused)
+        Oo = oracle.LSR1(n, mem=mem, scaling=scaling, dtype=npd)
+        x = rng.uniform(-1, 1, n).astype(npd)
+        prs = pairs(rng, n, mem + 4, npd)
+        s0 = prs[1][0]
+        prs.insert(0, (s0, s0.copy()))                 # empty memory, B = I: y - B s = 0 exactly, not well defined (:131)
+        prs.insert(3, (s0, (npd(3.0) * s0).astype(npd)))                     # y ∥ s: |y - s/sf| ≈ eps|y| ≪ eps|y||s| (:141)
+        if scaling:
+            yperp = np.zeros(n, npd); yperp[0], yperp[1] = s0[1], -s0[0]     # y's = O(eps): no curvature (:137)
+            prs.insert(5, (s0, yperp))
+        nacc = 0
+        for k, (s, y) in enumerate(prs):
+            want = Oo.push(s, y)
+            nacc += want
+            for fused in (1, 0):
+                with ctx.tuned(push_fused=fused):
                     if k % 5 == 4:                                                         # misaligned views: element offset 1
                         sb, yb = torch.empty(n + 1, dtype=dtype, device=dev), torch.empty(n + 1, dtype=dtype, device=dev)
                         sb[1:].copy_(T(s, dev)); yb[1:].copy_(T(y, dev))
@@ -779,32 +766,31 @@ def test_lsr1_streaming_push_matches_apply_based_schedule_and_oracle(lo, dev, dt
                         lo.push(ops[fused], T(s, dev), T(y, dev))
                     assert ops[fused]._last_push_accepted == want, (n, k, fused, want)
                     assert ops[fused].data.insert == Oo.insert, (n, k, fused)
-                if k in (0, 1, 3, 5, mem - 1, mem, len(prs) - 1):
-                    got = {}
-                    for fused in (1, 0):
-                        res = torch.full((n,), float("nan"), dtype=dtype, device=dev)
-                        lo.mul(res, ops[fused], T(x, dev), 1.0, 0.0)
-                        got[fused] = res.cpu().numpy()
-                    ref = Oo.mul(np.empty(n, dtype=npd), x, 1.0, 0.0)
-                    assert rel(got[1], ref) <= tol and rel(got[0], ref) <= tol, (n, k, rel(got[1], ref), rel(got[0], ref))
-                    assert rel(got[1], got[0]) <= same, (n, k, rel(got[1], got[0]))
-            assert nacc >= mem + 1
-            for fused in (1, 0):
-                assert abs(ops[fused].data.scaling_factor - Oo.scaling_factor) <= 1e-6 * abs(Oo.scaling_factor)
-            d1, d0 = lo.diag(ops[1]).cpu().numpy(), lo.diag(ops[0]).cpu().numpy()
-            assert rel(d1, Oo.diag()) <= tol and rel(d1, d0) <= same
-            # the panels hold exactly the accepted pairs (the inserts rode in the rebuild) and the padding stayed zero
-            for slot in range(mem):
-                for which in ("s", "y"):
-                    assert torch.equal(ops[1].data.column(which, slot), ops[0].data.column(which, slot)), (n, which, slot)
+            if k in (0, 1, 3, 5, mem - 1, mem, len(prs) - 1):
+                got = {}
+                for fused in (1, 0):
+                    res = torch.full((n,), float("nan"), dtype=dtype, device=dev)
+                    lo.mul(res, ops[fused], T(x, dev), 1.0, 0.0)
+                    got[fused] = res.cpu().numpy()
+                ref = Oo.mul(np.empty(n, dtype=npd), x, 1.0, 0.0)
+                assert rel(got[1], ref) <= tol and rel(got[0], ref) <= tol, (n, k, rel(got[1], ref), rel(got[0], ref))
+                assert rel(got[1], got[0]) <= same, (n, k, rel(got[1], got[0]))
+        assert nacc >= mem + 1
+        for fused in (1, 0):
+            assert abs(ops[fused].data.scaling_factor - Oo.scaling_factor) <= 1e-6 * abs(Oo.scaling_factor)
+        d1, d0 = lo.diag(ops[1]).cpu().numpy(), lo.diag(ops[0]).cpu().numpy()
+        assert rel(d1, Oo.diag()) <= tol and rel(d1, d0) <= same
+        # the panels hold exactly the accepted pairs (the inserts rode in the rebuild) and the padding stayed zero
+        for slot in range(mem):
+            for which in ("s", "y"):
+                assert torch.equal(ops[1].data.column(which, slot), ops[0].data.column(which, slot)), (n, which, slot)
+        with ctx.tuned(push_fused=0):                # (what the loops above ran their last pushes with)
             lo.reset(ops[1]); Oo.reset()
             for s, y in prs[:2]:
                 lo.push(ops[1], T(s, dev), T(y, dev)); Oo.push(s, y)
             res = torch.empty(n, dtype=dtype, device=dev)
             lo.mul(res, ops[1], T(x, dev), 1.0, 0.0)
             assert rel(res.cpu().numpy(), Oo.mul(np.empty(n, dtype=npd), x, 1.0, 0.0)) <= tol
-    finally:
-        ctx.tune("push_fused", 1)
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
@@ -870,8 +856,7 @@ def test_single_launch_dots_and_coefficients_match_the_four_launch_apply(lo, dev
             want = O.mul(r0.copy(), x, a, b, flags=fl)
             got = {}
             for fused in (1, 0):
-                ctx.tune("qn_fused_small", fused)
-                try:
+                with ctx.tuned(qn_fused_small=fused):
                     res = T(r0.copy(), dev)
                     lo.mul(res, op, T(x, dev), a, b)
                     got[fused] = res.cpu().numpy()
@@ -882,8 +867,6 @@ def test_single_launch_dots_and_coefficients_match_the_four_launch_apply(lo, dev
                         res3 = T(r0.copy(), dev)
                         lo.mul(res3, op, xm[1:], a, b)                       # misaligned x: the four-launch path
                         assert rel(res3.cpu().numpy(), want) <= tol
-                finally:
-                    ctx.tune("qn_fused_small", 1)
             assert rel(got[1], want) <= tol and rel(got[0], want) <= tol, (k, a, b, rel(got[1], want), rel(got[0], want))
             assert rel(got[1], got[0]) <= (1e-12 if dtype == torch.float64 else 2e-5), (k, a, b)
     sh = lo.ShiftedOperator(op, 0.37)
@@ -936,16 +919,11 @@ def test_single_launch_apply_exchange_stress(lo, dev):
             torch.cuda.synchronize()
             for op, x, res, first in ops:
                 assert torch.equal(res, first), it
-    ctx.tune("qn_fused_small", 0)
-    ctx.tune("qn_persist", 0)
-    try:
+    with ctx.tuned(qn_fused_small=0, qn_persist=0):
         for op, x, res, first in ops:
             lo.mul(res, op, x, 1.0, 0.0)
             tol = 1e-12 if res.dtype == torch.float64 else 2e-5
             assert (torch.linalg.vector_norm((res - first).double()) / torch.linalg.vector_norm(first.double())).item() <= tol
-    finally:
-        ctx.tune("qn_fused_small", 1)
-        ctx.tune("qn_persist", 1)
 
 
 @pytest.mark.parametrize("kind", ["inv", "fwd", "lsr1"])
@@ -963,31 +941,26 @@ def test_single_launch_apply_timeout_is_an_error_not_a_hang(lo, dev, kind):
         lo.push(op, T(s, dev), T(y, dev))
     x = T(rng.uniform(-1, 1, n), dev)
     res = torch.zeros(n, dtype=torch.float64, device=dev)
-    try:
-        lo.mul(res, op, x, 1.0, 0.0)
-        torch.cuda.synchronize()
-        good = res.clone()
-        ctx.tune("fused_timeout_ms", 20)
-        ctx.tune("fused_debug_drop", 3)
+    lo.mul(res, op, x, 1.0, 0.0)
+    torch.cuda.synchronize()
+    good = res.clone()
+    # a fault switches all the single-launch forms off: the exit of this block puts them back
+    with ctx.tuned(house_fused=1, qn_fused_small=1, qn_persist=1, herm_single=1, kron_fuse=1,
+                   fused_timeout_ms=20, fused_debug_drop=3):
         lo.mul(res, op, x, 1.0, 0.0)
         torch.cuda.synchronize()
         assert bool(torch.isnan(res).any())
-        ctx.tune("fused_debug_drop", -1)
-        with pytest.raises(Exception, match="timed out"):
-            lo.mul(res, op, x, 1.0, 0.0)
-        lo.mul(res, op, x, 1.0, 0.0)                     # four launches now
-        torch.cuda.synchronize()
-        assert float((res - good).norm() / good.norm()) <= 1e-13
-        ctx.tune("qn_fused_small", 1)
-        for _ in range(4):
-            lo.mul(res, op, x, 1.0, 0.0)
-        torch.cuda.synchronize()
-        assert torch.equal(res, good)                    # the re-armed single launch is bit-identical to the first one
-    finally:
-        ctx.tune("fused_debug_drop", -1)
-        ctx.tune("fused_timeout_ms", 2000)
-        for key in ("house_fused", "qn_fused_small", "qn_persist", "herm_single", "kron_fuse"):   # a fault switches them all off
-            ctx.tune(key, 1)
+        with ctx.tuned(fused_debug_drop=-1):
+            with pytest.raises(Exception, match="timed out"):
+                lo.mul(res, op, x, 1.0, 0.0)
+            lo.mul(res, op, x, 1.0, 0.0)                     # four launches now
+            torch.cuda.synchronize()
+            assert float((res - good).norm() / good.norm()) <= 1e-13
+            with ctx.tuned(qn_fused_small=1):
+                for _ in range(4):
+                    lo.mul(res, op, x, 1.0, 0.0)
+                torch.cuda.synchronize()
+                assert torch.equal(res, good)                # the re-armed single launch is bit-identical to the first one
 
 
 # ------------------------------------------------------------------------------- the persistent single-launch apply
@@ -1018,44 +991,38 @@ def test_persistent_apply_matches_the_four_launch_apply_and_the_oracle(lo, dev, 
         a = (C.c_int64 * 12)()
         lo._lib.call("mxlo_debug_counters", a)
         return a[10]
-    ctx.tune("qn_persist_min_bytes", 0)          # (default 32 MiB: a two-column panel would take the other forms) — restored below
-    for k, (s, y) in enumerate(pairs(rng, n, mem + 2, npd)):
-        lo.push(op, T(s, dev), T(y, dev)); O.push(s, y)
-        if k not in (0, mem // 2, mem + 1):
-            continue
-        for a, b in ((1.0, 0.0), (2.0, -3.0)):
-            fl = oracle.SCALARS_F64 if dtype == torch.float32 else 0
-            want = O.mul(r0.copy(), x, a, b, flags=fl)
-            got = {}
-            for persist in (1, 0):
-                ctx.tune("qn_persist", persist)
-                ctx.tune("qn_fused_small", persist)      # (n = 2^19 is still within reach of the single-launch slice form)
-                try:
-                    res = T(r0.copy(), dev)
-                    xd = T(x, dev)
-                    l0 = launches()
-                    lo.mul(res, op, xd, a, b)
-                    nl = launches() - l0
-                    assert (nl == 1) if persist else (nl >= 3), (persist, nl)
-                    got[persist] = res.cpu().numpy()
-                    if persist:
-                        res2 = T(r0.copy(), dev)
-                        lo.mul(res2, op, xd, a, b)
-                        assert np.array_equal(res2.cpu().numpy(), got[1]), "run-to-run determinism"
-                        res3 = T(r0.copy(), dev)
-                        lo.mul(res3, op, xm[1:], a, b)                       # misaligned x: the four-launch path
-                        assert rel(res3.cpu().numpy(), want) <= tol
-                finally:
-                    ctx.tune("qn_persist", 1)
-                    ctx.tune("qn_fused_small", 1)
-            assert rel(got[1], want) <= tol and rel(got[0], want) <= tol, (k, a, b, rel(got[1], want), rel(got[0], want))
-            assert rel(got[1], got[0]) <= (1e-12 if dtype == torch.float64 else 2e-5), (k, a, b)
-    sh = lo.ShiftedOperator(op, 0.37)
-    res = T(r0.copy(), dev)
-    lo.mul(res, sh, T(x, dev), 1.5, 0.5)
-    want = 1.5 * (O.mul(np.empty(n, npd), x).astype(np.float64) + 0.37 * x.astype(np.float64)) + 0.5 * r0.astype(np.float64)
-    assert rel(res.cpu().numpy().astype(np.float64), want) <= tol
-    ctx.tune("qn_persist_min_bytes", 32 << 20)
+    with ctx.tuned(qn_persist_min_bytes=0):      # (default 32 MiB: a two-column panel would take the other forms)
+        for k, (s, y) in enumerate(pairs(rng, n, mem + 2, npd)):
+            lo.push(op, T(s, dev), T(y, dev)); O.push(s, y)
+            if k not in (0, mem // 2, mem + 1):
+                continue
+            for a, b in ((1.0, 0.0), (2.0, -3.0)):
+                fl = oracle.SCALARS_F64 if dtype == torch.float32 else 0
+                want = O.mul(r0.copy(), x, a, b, flags=fl)
+                got = {}
+                for persist in (1, 0):
+                    with ctx.tuned(qn_persist=persist, qn_fused_small=persist):   # (n = 2^19 is still within reach of the single-launch slice form)
+                        res = T(r0.copy(), dev)
+                        xd = T(x, dev)
+                        l0 = launches()
+                        lo.mul(res, op, xd, a, b)
+                        nl = launches() - l0
+                        assert (nl == 1) if persist else (nl >= 3), (persist, nl)
+                        got[persist] = res.cpu().numpy()
+                        if persist:
+                            res2 = T(r0.copy(), dev)
+                            lo.mul(res2, op, xd, a, b)
+                            assert np.array_equal(res2.cpu().numpy(), got[1]), "run-to-run determinism"
+                            res3 = T(r0.copy(), dev)
+                            lo.mul(res3, op, xm[1:], a, b)                       # misaligned x: the four-launch path
+                            assert rel(res3.cpu().numpy(), want) <= tol
+                assert rel(got[1], want) <= tol and rel(got[0], want) <= tol, (k, a, b, rel(got[1], want), rel(got[0], want))
+                assert rel(got[1], got[0]) <= (1e-12 if dtype == torch.float64 else 2e-5), (k, a, b)
+        sh = lo.ShiftedOperator(op, 0.37)
+        res = T(r0.copy(), dev)
+        lo.mul(res, sh, T(x, dev), 1.5, 0.5)
+        want = 1.5 * (O.mul(np.empty(n, npd), x).astype(np.float64) + 0.37 * x.astype(np.float64)) + 0.5 * r0.astype(np.float64)
+        assert rel(res.cpu().numpy().astype(np.float64), want) <= tol
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
@@ -1075,8 +1042,7 @@ def test_persistent_apply_with_lds_parking_has_the_bits_of_the_plain_form(lo, de
     make = {"inv": lo.InverseLBFGSOperator, "fwd": lo.LBFGSOperator, "lsr1": lo.LSR1Operator}[kind]
     op = make(dtype, n, mem=mem, scaling=True, device=dev)
     x, r0 = T(rng.uniform(-1, 1, n).astype(npd), dev), T(rng.uniform(-1, 1, n).astype(npd), dev)
-    ctx.tune("qn_persist_min_bytes", 0)
-    try:
+    with ctx.tuned(qn_persist_min_bytes=0):
         for k, (s, y) in enumerate(pairs(rng, n, mem + 1, npd)):
             lo.push(op, T(s, dev), T(y, dev))
             if k not in (0, mem):
@@ -1084,14 +1050,11 @@ def test_persistent_apply_with_lds_parking_has_the_bits_of_the_plain_form(lo, de
             for target, a, b in ((op, 1.0, 0.0), (op, 0.7, -1.3), (lo.ShiftedOperator(op, 0.37), 1.5, 0.5)):
                 got = {}
                 for park in (1, 0):
-                    ctx.tune("qn_persist_lds", park)
-                    res = r0.clone()
-                    lo.mul(res, target, x, a, b)
-                    got[park] = res
+                    with ctx.tuned(qn_persist_lds=park):
+                        res = r0.clone()
+                        lo.mul(res, target, x, a, b)
+                        got[park] = res
                 assert torch.equal(got[1], got[0]), (k, a, b)
-    finally:
-        ctx.tune("qn_persist_lds", 1)
-        ctx.tune("qn_persist_min_bytes", 32 << 20)
 
 
 def test_persistent_apply_timeout_is_an_error_not_a_hang(lo, dev):
@@ -1108,34 +1071,26 @@ def test_persistent_apply_timeout_is_an_error_not_a_hang(lo, dev):
         lo.push(op, T(s, dev), T(y, dev))
     x = T(rng.uniform(-1, 1, n), dev)
     res = torch.zeros(n, dtype=torch.float64, device=dev)
-    try:
-        lo.mul(res, op, x, 1.0, 0.0)
-        torch.cuda.synchronize()
-        good = res.clone()
-        ctx.tune("fused_timeout_ms", 20)
-        ctx.tune("fused_debug_drop", 100)
+    lo.mul(res, op, x, 1.0, 0.0)
+    torch.cuda.synchronize()
+    good = res.clone()
+    # a fault switches all the single-launch forms off: the exit of this block puts them back
+    with ctx.tuned(house_fused=1, qn_fused_small=1, qn_persist=1, herm_single=1, kron_fuse=1,
+                   fused_timeout_ms=20, fused_debug_drop=100):
         lo.mul(res, op, x, 1.0, 0.0)
         torch.cuda.synchronize()
         assert bool(torch.isnan(res).any())
-        ctx.tune("fused_debug_drop", -1)
-        with pytest.raises(Exception, match="timed out"):
-            lo.mul(res, op, x, 1.0, 0.0)
-        lo.mul(res, op, x, 1.0, 0.0)                     # four launches now
-        torch.cuda.synchronize()
-        assert float((res - good).norm() / good.norm()) <= 1e-12
-        ctx.tune("qn_persist", 1)
-        for _ in range(4):
-            lo.mul(res, op, x, 1.0, 0.0)
-        torch.cuda.synchronize()
-        assert torch.equal(res, good)
-    finally:
-        ctx.tune("fused_debug_drop", -1)
-        ctx.tune("fused_timeout_ms", 2000)
-        ctx.tune("house_fused", 1)
-        ctx.tune("qn_fused_small", 1)
-        ctx.tune("qn_persist", 1)
-        ctx.tune("herm_single", 1)
-        ctx.tune("kron_fuse", 1)
+        with ctx.tuned(fused_debug_drop=-1):
+            with pytest.raises(Exception, match="timed out"):
+                lo.mul(res, op, x, 1.0, 0.0)
+            lo.mul(res, op, x, 1.0, 0.0)                     # four launches now
+            torch.cuda.synchronize()
+            assert float((res - good).norm() / good.norm()) <= 1e-12
+            with ctx.tuned(qn_persist=1):
+                for _ in range(4):
+                    lo.mul(res, op, x, 1.0, 0.0)
+                torch.cuda.synchronize()
+                assert torch.equal(res, good)
 
 
 @pytest.mark.parametrize("kind", ["inv", "fwd", "lsr1"])
@@ -1192,77 +1147,74 @@ def test_lsr1_streaming_push_decisions_agree_with_the_apply_based_schedule(lo, d
     eps = float(np.finfo(npd).eps)
     same = 1e-9 if dtype == torch.float64 else 2e-3
     decided = gray = 0
-    try:
-        for seed in range(12):
-            rng = np.random.default_rng(900 + seed)
-            n, mem = int(rng.integers(200, 5000)) * 2, int(rng.integers(2, 8))
-            ops = {}
-            for fused in (1, 0):
-                ctx.tune("push_fused", fused)
+    for seed in range(12):
+        rng = np.random.default_rng(900 + seed)
+        n, mem = int(rng.integers(200, 5000)) * 2, int(rng.integers(2, 8))
+        ops = {}
+        for fused in (1, 0):
+            with ctx.tuned(push_fused=fused):
                 ops[fused] = lo.LSR1Operator(dtype, n, mem=mem, scaling=scaling, device=dev)
-            hist = []
-            tainted = False                                    # a pair decided by noise sits in one of the memories
-            for k in range(3 * mem + 6):
-                c = int(rng.integers(0, 7))
-                s = rng.uniform(-1, 1, n).astype(npd)
-                if c <= 1 or not hist:
-                    y = ((0.5 + 1.5 * rng.random(n)) * s + 1e-2 * rng.standard_normal(n)).astype(npd)
-                elif c == 2:                                   # the same pair again: r is rounding noise
-                    s, y = hist[int(rng.integers(len(hist)))]
-                elif c == 3:                                   # y = B s (+ a perturbation from 1e-15 to 1e-6): r tiny
-                    Bs = torch.empty(n, dtype=dtype, device=dev)
-                    lo.mul(Bs, ops[0], T(s, dev), 1.0, 0.0)
-                    y = (Bs.cpu().numpy() + npd(10.0 ** rng.uniform(-15, -6)) * rng.standard_normal(n).astype(npd)).astype(npd)
-                elif c == 4:                                   # y almost orthogonal to s
-                    y = rng.standard_normal(n).astype(npd)
-                    y = (y - (y @ s) / (s @ s) * s * npd(1.0 - 10.0 ** rng.uniform(-16, -3))).astype(npd)
-                elif c == 5:                                   # y almost parallel to s
-                    y = (npd(2.5) * s + npd(10.0 ** rng.uniform(-16, -4)) * rng.standard_normal(n).astype(npd)).astype(npd)
-                else:                                          # y orthogonal to s up to a few eps: y's ≈ eps |y||s| (:137)
-                    y = rng.standard_normal(n).astype(npd)
-                    y = (y - (y @ s) / (s @ s) * s).astype(npd)
-                    y = (y + npd(eps * 10.0 ** rng.uniform(-1, 2)) * np.sqrt(y @ y / (s @ s)).astype(npd) * s).astype(npd)
-                # independent margin (float64 on the host, r through the apply-based operator)
+        hist = []
+        tainted = False                                    # a pair decided by noise sits in one of the memories
+        for k in range(3 * mem + 6):
+            c = int(rng.integers(0, 7))
+            s = rng.uniform(-1, 1, n).astype(npd)
+            if c <= 1 or not hist:
+                y = ((0.5 + 1.5 * rng.random(n)) * s + 1e-2 * rng.standard_normal(n)).astype(npd)
+            elif c == 2:                                   # the same pair again: r is rounding noise
+                s, y = hist[int(rng.integers(len(hist)))]
+            elif c == 3:                                   # y = B s (+ a perturbation from 1e-15 to 1e-6): r tiny
                 Bs = torch.empty(n, dtype=dtype, device=dev)
                 lo.mul(Bs, ops[0], T(s, dev), 1.0, 0.0)
-                s64, y64 = s.astype(np.float64), y.astype(np.float64)
-                with np.errstate(all="ignore"):
-                    r64 = y64 - Bs.cpu().numpy().astype(np.float64)
-                sN, yN, rN = np.linalg.norm(s64), np.linalg.norm(y64), np.linalg.norm(r64)
-                budget = 256 * eps * ((2 * yN + rN) * sN + 1)
-                clear = np.isfinite(rN) and abs(r64 @ s64) > 16 * ((eps + eps * rN * sN) + budget)
-                if scaling and clear:
-                    ys, yy = y64 @ s64, y64 @ y64
-                    thr = eps * yN * sN
-                    clear = abs(ys) > 16 * thr * 257 and \
-                        np.linalg.norm(y64 - s64 * (yy / ys)) > 16 * (thr + 256 * eps * (yN + sN * yy / abs(ys)))
-                acc = {}
-                for fused in (1, 0):
-                    ctx.tune("push_fused", fused)
+                y = (Bs.cpu().numpy() + npd(10.0 ** rng.uniform(-15, -6)) * rng.standard_normal(n).astype(npd)).astype(npd)
+            elif c == 4:                                   # y almost orthogonal to s
+                y = rng.standard_normal(n).astype(npd)
+                y = (y - (y @ s) / (s @ s) * s * npd(1.0 - 10.0 ** rng.uniform(-16, -3))).astype(npd)
+            elif c == 5:                                   # y almost parallel to s
+                y = (npd(2.5) * s + npd(10.0 ** rng.uniform(-16, -4)) * rng.standard_normal(n).astype(npd)).astype(npd)
+            else:                                          # y orthogonal to s up to a few eps: y's ≈ eps |y||s| (:137)
+                y = rng.standard_normal(n).astype(npd)
+                y = (y - (y @ s) / (s @ s) * s).astype(npd)
+                y = (y + npd(eps * 10.0 ** rng.uniform(-1, 2)) * np.sqrt(y @ y / (s @ s)).astype(npd) * s).astype(npd)
+            # independent margin (float64 on the host, r through the apply-based operator)
+            Bs = torch.empty(n, dtype=dtype, device=dev)
+            lo.mul(Bs, ops[0], T(s, dev), 1.0, 0.0)
+            s64, y64 = s.astype(np.float64), y.astype(np.float64)
+            with np.errstate(all="ignore"):
+                r64 = y64 - Bs.cpu().numpy().astype(np.float64)
+            sN, yN, rN = np.linalg.norm(s64), np.linalg.norm(y64), np.linalg.norm(r64)
+            budget = 256 * eps * ((2 * yN + rN) * sN + 1)
+            clear = np.isfinite(rN) and abs(r64 @ s64) > 16 * ((eps + eps * rN * sN) + budget)
+            if scaling and clear:
+                ys, yy = y64 @ s64, y64 @ y64
+                thr = eps * yN * sN
+                clear = abs(ys) > 16 * thr * 257 and \
+                    np.linalg.norm(y64 - s64 * (yy / ys)) > 16 * (thr + 256 * eps * (yN + sN * yy / abs(ys)))
+            acc = {}
+            for fused in (1, 0):
+                with ctx.tuned(push_fused=fused):
                     lo.push(ops[fused], T(s, dev), T(y, dev))
                     acc[fused] = ops[fused]._last_push_accepted
-                if clear:
-                    decided += 1
-                    assert acc[1] == acc[0], (seed, k, c, acc)
-                    assert ops[1].data.insert == ops[0].data.insert
-                else:
-                    gray += 1
-                    if acc[1] != acc[0]:                       # noise decided differently: legitimate, start over
-                        for fused in (1, 0):
-                            lo.reset(ops[fused])
-                        hist = []
-                        tainted = False
-                        continue
-                    tainted = tainted or acc[1]
-                if acc[1]:
-                    hist.append((s, y))
-            x = T(rng.uniform(-1, 1, n).astype(npd), dev)
-            r1, r0 = torch.empty_like(x), torch.empty_like(x)
-            lo.mul(r1, ops[1], x, 1.0, 0.0)
-            lo.mul(r0, ops[0], x, 1.0, 0.0)
-            if not tainted:                                    # every pair in the memories was decided by a clear margin
-                assert bool(torch.isfinite(r0).all()) and bool(torch.isfinite(r1).all()), seed
-                assert float((r1 - r0).norm()) <= same * max(float(r0.norm()), float(x.norm())), seed
-        assert decided >= 40 and gray >= 20, (decided, gray)
-    finally:
-        ctx.tune("push_fused", 1)
+            if clear:
+                decided += 1
+                assert acc[1] == acc[0], (seed, k, c, acc)
+                assert ops[1].data.insert == ops[0].data.insert
+            else:
+                gray += 1
+                if acc[1] != acc[0]:                       # noise decided differently: legitimate, start over
+                    for fused in (1, 0):
+                        lo.reset(ops[fused])
+                    hist = []
+                    tainted = False
+                    continue
+                tainted = tainted or acc[1]
+            if acc[1]:
+                hist.append((s, y))
+        x = T(rng.uniform(-1, 1, n).astype(npd), dev)
+        r1, r0 = torch.empty_like(x), torch.empty_like(x)
+        lo.mul(r1, ops[1], x, 1.0, 0.0)
+        lo.mul(r0, ops[0], x, 1.0, 0.0)
+        if not tainted:                                    # every pair in the memories was decided by a clear margin
+            assert bool(torch.isfinite(r0).all()) and bool(torch.isfinite(r1).all()), seed
+            assert float((r1 - r0).norm()) <= same * max(float(r0.norm()), float(x.norm())), seed
+    assert decided >= 40 and gray >= 20, (decided, gray)

@@ -45,14 +45,11 @@ def test_random_operation_sequences_in_the_range_of_the_persistent_apply(lo, dev
     columns, fp64 and (every third seed) fp32."""
     from linearoperators_jl_amd.device import get_ctx
     ctx = get_ctx(dev)
-    ctx.tune("qn_persist_min_bytes", 0)
-    try:
+    with ctx.tuned(qn_persist_min_bytes=0):
         f32 = seed % 3 == 2
         run_sequence(lo, dev, 50_000 + seed, torch.float32 if f32 else torch.float64,
                      (QN_F32_FUZZ_LSR1 if (50_000 + seed) % 3 == 2 else QN_F32_FUZZ_LBFGS) if f32 else 1e-8, QN_F32_SOLVE if f32 else 1e-7,
                      sizes=[1 << 19, (1 << 19) + 5, 700_001, 1 << 20, (1 << 20) + 3, 1_400_007], max_steps=12)
-    finally:
-        ctx.tune("qn_persist_min_bytes", 32 << 20)
 
 
 ILL_CONDITIONED_F32_SEED = 1154
