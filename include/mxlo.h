@@ -764,6 +764,49 @@ int32_t mxlo_krylov_orth(mxlo_ctx *ctx, int32_t dtype, const void *V, int64_t ld
 int32_t mxlo_krylov_combine(mxlo_ctx *ctx, int32_t dtype, const void *V, int64_t ldv, int64_t n, int32_t k,
                             const double *y_dev, void *out, double *coef);
 
+/* ======================================================================== */
+/*  opCholesky and triangular opInverse                                      */
+/* ======================================================================== */
+/* src/linalg.jl:3-9 (mulFact!), :27-32 (opInverse), :44-58 (opCholesky): `res .= α .* (F \ v) .+ β .* res` with F a
+ * Cholesky factorisation or a triangular matrix. Real f32 / f64, column-major, any leading dimension and alignment.
+ * Everything is cut into block columns of 64 (a compile-time constant). The sweeps use launch boundaries as their only
+ * dependency: one launch per block column, no workgroup waits for another. Per block the solve is a 64 x 64 product with
+ * the explicit inverse of the diagonal block, stored as DOUBLES for both element types in `dinv`: ceil(n/64) blocks of
+ * 64 x 64, column-major, identity-padded. All accumulation is f64 in a fixed order (bit-reproducible); `work` is n
+ * doubles the caller owns. An apply is kernel launches and nothing else; with beta == 0 res is not read.
+ * res == v is allowed (the result is that of separate buffers); any other overlap of res and v, and any overlap of either
+ * with the matrix, dinv or work, is MXLO_EINVAL. A zero on the diagonal is not detected: the result holds Inf / NaN, as
+ * the reference's triangular `\` gives on a device array.
+ *
+ * mxlo_tri_kind — the test dense `\` makes before it picks a triangular solve (src/linalg.jl:28 `M \ v`): one reduction,
+ * *kind_dev (device word) = bit 0: the strict upper triangle holds a non-zero, bit 1: the strict lower triangle does.
+ * Stream-ordered; the caller reads the word once. */
+int32_t mxlo_tri_kind(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ld, int64_t n, int32_t *kind_dev);
+/* The inverses of the diagonal blocks of a lower (upper != 0: upper) triangular T into dinv; one launch. */
+int32_t mxlo_tri_prepare(mxlo_ctx *ctx, int32_t dtype, const void *T, int64_t ld, int64_t n, int32_t upper, double *dinv);
+/* `cholesky(M)` of src/linalg.jl:51 — blocked right-looking factorisation W = L with L L' = M, lower triangle, in place
+ * in W (n x n, ldw). M != NULL: W's lower triangle is first filled from the UPPER triangle of M, the one `cholesky(M)` =
+ * `cholesky(Hermitian(M, :U))` reads (m_rowmajor: M[i, j] at M[i * ldm + j]); M is not modified and its strict lower
+ * triangle is not read. M == NULL: W already holds the lower triangle. Per block column: (a) the diagonal block is
+ * factored and inverted by one workgroup in LDS (f64 for both element types), (b) the panel below is multiplied by that
+ * inverse in row bands, (c) the trailing lower triangle is updated with v_mfma_f64_16x16x4_f64 (f32 data: the f32 MFMA
+ * with f32 accumulation, in this phase only), tiles above the diagonal skipped. dinv receives the block inverses the
+ * solves use. A pivot that is not positive and finite stores its 1-BASED index (LinearAlgebra.PosDefException(info),
+ * test/test_linop.jl:498) in *info_dev with an ordinary store; every later launch reads the word and does nothing.
+ * *info (host) = that word, copied once after the last launch — the only synchronisation. Not capturable. */
+int32_t mxlo_potrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_rowmajor, void *W, int64_t ldw,
+                   int64_t n, double *dinv, int32_t *info_dev, int32_t *info);
+/* mulFact!(res, M, v, α, β) / mulFact!(res, transpose(M), u, α, β) for triangular M (src/linalg.jl:28-30):
+ * res = alpha * op(T)^{-1} v + beta * res, op_mode MXLO_OP_N / MXLO_OP_T (MXLO_OP_C == T). The strict triangle is read
+ * once (nontemporal), the diagonal blocks not at all. ceil(n/64) launches. */
+int32_t mxlo_trisolve_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *T, int64_t ld, int64_t n, int32_t upper,
+                          int32_t op_mode, const double *dinv, double *work, const void *v, double alpha, double beta);
+/* mulFact!(res, LL, v, α, β) with LL = cholesky(M) (src/linalg.jl:52-54): res = alpha * L^{-T} (L^{-1} v) + beta * res
+ * with L and dinv from mxlo_potrf; the epilogue is fused into the last launch of the back sweep. The triangle is read
+ * twice. 2 ceil(n/64) - 1 launches (one for n <= 64). */
+int32_t mxlo_chol_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *L, int64_t ld, int64_t n, const double *dinv,
+                      double *work, const void *v, double alpha, double beta);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,7 @@ module LinearOperatorsMXLOExt
 
 using LinearOperators, LinearAlgebra
 import LinearOperators: storage_type, LinearOperator, LinearOperatorException, AbstractQuasiNewtonOperator,
-  opDiagonal, opHouseholder, opHermitian, opRestriction, opEye, opOnes, opZeros, BlockDiagonalOperator,
+  opDiagonal, opHouseholder, opHermitian, opCholesky, opInverse, opRestriction, opEye, opOnes, opZeros, BlockDiagonalOperator,
   LBFGSOperator, InverseLBFGSOperator, LSR1Operator, reset!, diag!, solve_shifted_system!, has_args5,
   isallocated5, mulOpEye!, mulOpOnes!, mulOpZeros!, mulSquareOpDiagonal!, mulOpDiagonal!, mulHouseholder!,
   mulRestrict!, multRestrict!
@@ -931,5 +931,66 @@ function solve_shifted_sharded!(q::ShardedQN{T}, x, b, σ) where {T}
   x
 end
 reset!(q::ShardedQN) = (scheck(ccall((:mxlo_qn_reset_sharded, rccl), Int32, (P,), q.h)); q)
+
+# ---- a7 opCholesky / triangular opInverse (src/linalg.jl:3-9, 27-32, 44-58) -------------------------------------------------
+# `F \ v` on the device: the factorisation (mxlo_potrf), the inverses of the 64 x 64 diagonal blocks and the block substitution
+# sweeps (mxlo_chol_mul, mxlo_trisolve_mul) are the entry points the Python mirror uses. Real element types only; `dinv` and
+# `work` are Float64 for both. The keyword of opCholesky is called `check` upstream, hence the alias for the status check.
+chk(st::Int32) = check(st)
+struct CholSolve{T}
+  L::MXMatrix{T}
+  dinv::MXVector{Float64}
+  work::MXVector{Float64}
+end
+(f::CholSolve{T})(res::MXVector{T}, v::MXVector{T}, α, β) where {T <: RealT} = chk(ccall((:mxlo_chol_mul, lib), Int32,
+    (P, Int32, P, P, Int64, Int64, P, P, P, Float64, Float64),
+    ctx(), dt(T), res.ptr, f.L.data.ptr, f.L.m, f.L.n, f.dinv.ptr, f.work.ptr, v.ptr, α, β))
+function opCholesky(M::MXMatrix{T}; check::Bool = false) where {T <: RealT}
+  m, n = size(M)
+  m == n || throw(LinearOperatorException("shape mismatch"))
+  if check
+    check_hermitian(M) || throw(LinearOperatorException("matrix is not Hermitian"))
+    check_positive_definite(M) || throw(LinearOperatorException("matrix is not positive definite"))
+  end
+  L = MXMatrix{T}(MXVector{T}(undef, n * n), n, n)                  # the factor: storage the operator owns, M is only read
+  dinv = MXVector{Float64}(undef, ((n + 63) ÷ 64) * 4096)
+  work = MXVector{Float64}(undef, n)
+  infod = MXVector{Int32}(undef, 1)
+  info = Ref{Int32}(0)
+  chk(ccall((:mxlo_potrf, lib), Int32, (P, Int32, P, Int64, Int32, P, Int64, Int64, P, P, Ptr{Int32}),
+            ctx(), dt(T), M.data.ptr, m, Int32(0), L.data.ptr, n, n, dinv.ptr, infod.ptr, info))
+  info[] == 0 || throw(LinearAlgebra.PosDefException(info[]))       # test/test_linop.jl:498
+  f = CholSolve{T}(L, dinv, work)
+  LinearOperator{T, MXVector{T}}(n, n, true, true, f, f, f)
+end
+
+struct TriSolve{T}
+  A::MXMatrix{T}
+  dinv::MXVector{Float64}
+  work::MXVector{Float64}
+  upper::Int32
+  mode::Int32                                                       # MXLO_OP_N / MXLO_OP_T
+end
+function (f::TriSolve{T})(res::MXVector{T}, v::MXVector{T}, α, β) where {T <: RealT}
+  # M is aliased and a device matrix carries no version counter here: the block inverses are rebuilt on every apply (one launch)
+  chk(ccall((:mxlo_tri_prepare, lib), Int32, (P, Int32, P, Int64, Int64, Int32, P),
+            ctx(), dt(T), f.A.data.ptr, f.A.m, f.A.n, f.upper, f.dinv.ptr))
+  chk(ccall((:mxlo_trisolve_mul, lib), Int32, (P, Int32, P, P, Int64, Int64, Int32, Int32, P, P, P, Float64, Float64),
+            ctx(), dt(T), res.ptr, f.A.data.ptr, f.A.m, f.A.n, f.upper, f.mode, f.dinv.ptr, f.work.ptr, v.ptr, α, β))
+end
+function opInverse(M::MXMatrix{T}; symm = false, herm = false) where {T <: RealT}
+  m, n = size(M)
+  m == n || throw(LinearOperatorException("shape mismatch"))
+  kd = MXVector{Int32}(undef, 1)
+  chk(ccall((:mxlo_tri_kind, lib), Int32, (P, Int32, P, Int64, Int64, P), ctx(), dt(T), M.data.ptr, m, n, kd.ptr))
+  bits = Array(kd)[1]                                               # bit 0: strict upper part non-zero, bit 1: strict lower part
+  bits == 3 && throw(LinearOperatorException("opInverse: M is neither lower nor upper triangular; general dense opInverse needs a pivoted LU, which this package does not have"))
+  upper = Int32(bits == 1 ? 1 : 0)                                  # a diagonal M counts as lower
+  dinv = MXVector{Float64}(undef, ((n + 63) ÷ 64) * 4096)
+  work = MXVector{Float64}(undef, n)
+  solve = TriSolve{T}(M, dinv, work, upper, Int32(0))
+  tsolve = TriSolve{T}(M, dinv, work, upper, Int32(1))
+  LinearOperator{T, MXVector{T}}(n, n, symm, herm, solve, tsolve, tsolve)
+end
 
 end # module

@@ -178,6 +178,11 @@ _PROTOS = {
     "mxlo_qn_set_push_mode": [_vp, _i32],
     "mxlo_krylov_orth": [_vp, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _i32],
     "mxlo_krylov_combine": [_vp, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp],
+    "mxlo_tri_kind": [_vp, _i32, _vp, _i64, _i64, _vp],
+    "mxlo_tri_prepare": [_vp, _i32, _vp, _i64, _i64, _i32, _vp],
+    "mxlo_potrf": [_vp, _i32, _vp, _i64, _i32, _vp, _i64, _i64, _vp, _vp, C.POINTER(_i32)],
+    "mxlo_trisolve_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _dbl, _dbl],
+    "mxlo_chol_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _dbl, _dbl],
 }
 
 

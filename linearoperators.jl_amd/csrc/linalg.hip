@@ -1,0 +1,527 @@
+// linalg.hip — opCholesky and triangular opInverse (src/linalg.jl:3-9, 27-32, 44-58): the factorisation, the inverses of the
+// diagonal blocks and the block substitution sweeps. Everything is cut into block columns of NB = 64.
+//
+// The only dependency mechanism is the LAUNCH BOUNDARY: no workgroup waits for another one. A sweep is a chain of launches,
+// one per block column (block row for a transposed solve). In launch k every workgroup reads the solved block x_k (64
+// doubles, finished by the launch before) and subtracts its 64 x 64 piece of the panel from the right-hand side; the ONE
+// workgroup whose 64 entries are the next diagonal block goes on and solves it, x_{k+1} = inv(T_{k+1,k+1}) b_{k+1}, with the
+// stored inverse. The right-hand side lives in one f64 work vector z whose blocks turn into the solution one by one, so the
+// data a launch reads (x_k) and writes (entries not solved yet) never meet. All sums run in a fixed order in f64.
+#include "common.h"
+
+using namespace mxlo;
+
+namespace {
+
+constexpr int NB = 64;               // block column width; one diagonal block (f64) is 32 KiB of LDS
+constexpr int NB2 = NB * NB;
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+
+template <typename T>
+__device__ __forceinline__ double ld_stream(const T *p) {   // the triangle is read once per sweep: do not keep it in cache
+  return (double)__builtin_nontemporal_load(p);
+}
+
+// ---------------------------------------------------------------------------------------------- triangularity
+// bit 0: the strict upper triangle holds a non-zero (NaN counts), bit 1: the strict lower one does
+template <typename T>
+__global__ void __launch_bounds__(kBlock) tri_kind_kernel(const T *__restrict__ M, int64_t ld, int64_t n, int *flag) {
+  int f = 0;
+  for (int64_t c = blockIdx.x; c < n; c += gridDim.x)
+    for (int64_t i = threadIdx.x; i < n; i += kBlock) {
+      const T x = M[i + c * ld];
+      if (x != T(0)) f |= i < c ? 1 : (i > c ? 2 : 0);
+    }
+  const int up = __syncthreads_or(f & 1), lo = __syncthreads_or(f & 2);
+  if (threadIdx.x == 0 && (up || lo)) atomicOr(flag, (up ? 1 : 0) | (lo ? 2 : 0));
+}
+
+// ---------------------------------------------------------------------------------------------- 64 x 64 blocks in LDS
+// Blocks are stored column-major without padding, s[c * NB + i]; a wave's lanes are the ROWS i (conflict-free), its wave
+// index q picks the columns c = q, q + 4, ... A block narrower than NB is padded with the identity.
+
+// Cholesky of the lower triangle held in sA; the factor goes to sL (zero above the diagonal). Returns 0, or the 1-based
+// index of the first pivot that is not positive and finite (the same value in every thread).
+__device__ int chol_block(double *sA, double *sL, int lane, int q) {
+  for (int p = 0; p < NB; ++p) {
+    const double app = sA[p * NB + p];
+    if (!(app > 0.0) || !(app < __builtin_inf())) return p + 1;
+    const double lpp = sqrt(app);
+    if (q == 0) sL[p * NB + lane] = lane > p ? sA[p * NB + lane] / lpp : (lane == p ? lpp : 0.0);
+    __syncthreads();
+    const double lip = sL[p * NB + lane];
+#pragma unroll 4
+    for (int c = q; c < NB; c += 4)
+      if (c > p && lane >= c) sA[c * NB + lane] = fma(-lip, sL[p * NB + c], sA[c * NB + lane]);
+    __syncthreads();
+  }
+  return 0;
+}
+
+// sX = inv(sL) for a lower triangular sL: forward substitution on the identity, all 64 columns at once.
+__device__ void invert_block(const double *sL, double *sX, int tid, int lane, int q) {
+  for (int e = tid; e < NB2; e += kBlock) sX[e] = (e >> 6) == (e & 63) ? 1.0 : 0.0;
+  __syncthreads();
+  for (int p = 0; p < NB; ++p) {
+    if (tid < NB) sX[tid * NB + p] = sX[tid * NB + p] / sL[p * NB + p];     // row p of the inverse is final
+    __syncthreads();
+    const double lip = sL[p * NB + lane];
+#pragma unroll 4
+    for (int c = q; c < NB; c += 4)
+      if (lane > p) sX[c * NB + lane] = fma(-lip, sX[c * NB + p], sX[c * NB + lane]);
+    __syncthreads();
+  }
+}
+
+// inverses of ALL diagonal blocks of a triangular matrix, one workgroup each (opInverse). An upper block is inverted as the
+// lower block that is its transpose and stored transposed back.
+template <typename T>
+__global__ void __launch_bounds__(kBlock) tri_prepare_kernel(const T *__restrict__ Tm, int64_t ld, int64_t n, int upper,
+                                                             double *__restrict__ dinv) {
+  __shared__ double sL[NB2], sX[NB2];
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int64_t j0 = (int64_t)blockIdx.x * NB;
+  const int jb = (int)(n - j0 < NB ? n - j0 : NB);
+  for (int c = q; c < NB; c += 4) {
+    double x = lane == c ? 1.0 : 0.0;
+    if (lane >= c && lane < jb) x = (double)(upper ? Tm[(j0 + c) + (j0 + lane) * ld] : Tm[(j0 + lane) + (j0 + c) * ld]);
+    sL[c * NB + lane] = x;
+  }
+  __syncthreads();
+  invert_block(sL, sX, tid, lane, q);
+  double *out = dinv + (int64_t)blockIdx.x * NB2;
+  for (int c = q; c < NB; c += 4) out[upper ? lane * NB + c : c * NB + lane] = sX[c * NB + lane];
+}
+
+// ---------------------------------------------------------------------------------------------- potrf
+// W (lower triangle, column-major) = the UPPER triangle of M, transposed: W[i, c] = M[c, i], i >= c.
+template <typename T>
+__global__ void __launch_bounds__(kBlock) pack_upper_kernel(T *__restrict__ W, int64_t ldw, const T *__restrict__ M, int64_t ldm,
+                                                            int rowmajor, int64_t n) {
+  if (blockIdx.y > blockIdx.x) return;                 // tile (bi, bc) of W with bi >= bc
+  __shared__ T s[NB * (NB + 1)];
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int64_t i0 = (int64_t)blockIdx.x * NB, c0 = (int64_t)blockIdx.y * NB;
+  if (rowmajor) {                                      // M[c, i] = M[c * ldm + i]: unit stride along i, as W wants it
+    for (int cl = q; cl < NB; cl += 4) {
+      const int64_t i = i0 + lane, c = c0 + cl;
+      if (i < n && c < n) W[i + c * ldw] = i >= c ? M[c * ldm + i] : T(0);
+    }
+    return;
+  }
+  for (int il = q; il < NB; il += 4) {                 // M[c, i] = M[c + i * ldm]: unit stride along c, transposed through LDS
+    const int64_t i = i0 + il, c = c0 + lane;
+    s[il * (NB + 1) + lane] = (i < n && c < n && i >= c) ? M[c + i * ldm] : T(0);
+  }
+  __syncthreads();
+  for (int cl = q; cl < NB; cl += 4) {
+    const int64_t i = i0 + lane, c = c0 + cl;
+    if (i < n && c < n) W[i + c * ldw] = s[lane * (NB + 1) + cl];
+  }
+}
+
+// phase (a): factor the diagonal block, store its explicit inverse
+template <typename T>
+__global__ void __launch_bounds__(kBlock) potrf_diag_kernel(T *__restrict__ W, int64_t ldw, int64_t n, int64_t j0,
+                                                            double *__restrict__ dinv, int *info) {
+  __shared__ double sA[NB2], sL[NB2];
+  if (*info != 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int jb = (int)(n - j0 < NB ? n - j0 : NB);
+  for (int c = q; c < NB; c += 4) {
+    double x = lane == c ? 1.0 : 0.0;
+    if (lane >= c && lane < jb) x = (double)W[(j0 + lane) + (j0 + c) * ldw];
+    sA[c * NB + lane] = x;
+  }
+  __syncthreads();
+  const int bad = chol_block(sA, sL, lane, q);
+  if (bad) {
+    if (tid == 0) *info = (int)(j0 + bad);
+    return;
+  }
+  for (int c = q; c < NB; c += 4)
+    if (lane >= c && lane < jb) W[(j0 + lane) + (j0 + c) * ldw] = (T)sL[c * NB + lane];
+  invert_block(sL, sA, tid, lane, q);
+  for (int e = tid; e < NB2; e += kBlock) dinv[e] = sA[e];
+}
+
+// phase (b): the panel below the diagonal block, W[i, j0 + c] = sum_{p <= c} W[i, j0 + p] inv(L_kk)[c, p], 64 rows a workgroup
+template <typename T>
+__global__ void __launch_bounds__(kBlock) potrf_panel_kernel(T *__restrict__ W, int64_t ldw, int64_t n, int64_t j0, int jb,
+                                                             const double *__restrict__ dinv, const int *info) {
+  __shared__ double sP[NB2], sD[NB2];
+  if (*info != 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int64_t i = j0 + jb + (int64_t)blockIdx.x * NB + lane;
+  for (int e = tid; e < NB2; e += kBlock) sD[e] = dinv[e];
+  for (int p = q; p < NB; p += 4) sP[p * NB + lane] = (p < jb && i < n) ? (double)W[i + (j0 + p) * ldw] : 0.0;
+  __syncthreads();
+  for (int c = q; c < jb; c += 4) {
+    double acc = 0.0;
+    for (int p = 0; p <= c; ++p) acc = fma(sP[p * NB + lane], sD[p * NB + c], acc);
+    if (i < n) W[i + (j0 + c) * ldw] = (T)acc;
+  }
+}
+
+// phase (c): C -= P P' on the lower triangle of the trailing matrix; 64 x 64 tiles, the ones above the diagonal are skipped.
+// v_mfma_f64_16x16x4_f64: C/D row = (lane >> 4) + 4 reg, col = lane & 15; the f32 form has row = 4 (lane >> 4) + reg.
+template <typename T>
+struct Mfma;
+template <>
+struct Mfma<double> {
+  using Acc = f64x4;
+  static __device__ __forceinline__ Acc run(double a, double b, Acc c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+  static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) + 4 * r; }
+};
+template <>
+struct Mfma<float> {
+  using Acc = f32x4v;
+  static __device__ __forceinline__ Acc run(float a, float b, Acc c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+  static __device__ __forceinline__ int row(int lane, int r) { return 4 * (lane >> 4) + r; }
+};
+
+constexpr int SK = 16, SLD = 80;     // k-slab and padded LDS row of the SYRK tiles (dense.hip's gemm_kernel uses the same)
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) potrf_syrk_kernel(T *__restrict__ C, const T *__restrict__ P, int64_t ld, int M, int K,
+                                                            const int *info) {
+  if (blockIdx.y > blockIdx.x) return;
+  if (*info != 0) return;
+  __shared__ T sA[SK][SLD], sB[SK][SLD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bm = blockIdx.x * NB, bn = blockIdx.y * NB;
+  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
+  using Acc = typename Mfma<T>::Acc;
+  Acc acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[a][b][r] = 0;
+  for (int k0 = 0; k0 < K; k0 += SK) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int e = tid + t * kBlock, i = e & 63, k = e >> 6, gk = k0 + k;
+      sA[k][i] = (bm + i < M && gk < K) ? P[(bm + i) + (int64_t)gk * ld] : T(0);
+      sB[k][i] = (bn + i < M && gk < K) ? P[(bn + i) + (int64_t)gk * ld] : T(0);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < SK; kk += 4) {
+      const int kr = kk + (lane >> 4);
+      const T a0 = sA[kr][wm + (lane & 15)], a1 = sA[kr][wm + 16 + (lane & 15)];
+      const T b0 = sB[kr][wn + (lane & 15)], b1 = sB[kr][wn + 16 + (lane & 15)];
+      acc[0][0] = Mfma<T>::run(a0, b0, acc[0][0]);
+      acc[0][1] = Mfma<T>::run(a0, b1, acc[0][1]);
+      acc[1][0] = Mfma<T>::run(a1, b0, acc[1][0]);
+      acc[1][1] = Mfma<T>::run(a1, b1, acc[1][1]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int gi = bm + wm + a * 16 + Mfma<T>::row(lane, r), gj = bn + wn + b * 16 + (lane & 15);
+        if (gi < M && gj <= gi) {
+          T *p = C + gi + (int64_t)gj * ld;
+          *p = *p - acc[a][b][r];
+        }
+      }
+}
+
+// ---------------------------------------------------------------------------------------------- substitution sweeps
+struct SweepArgs {
+  const void *Tm;        // the triangle, column-major
+  int64_t ld, n;
+  double *z;             // right-hand side turning into the solution, block by block
+  const void *v;         // first launch of an apply: the right-hand side is read from v (no panel yet), else NULL
+  int64_t xs;            // the solved block is x = z[xs .. xs + xl); xl == 0: no panel
+  int xl;
+  int64_t r0, r1;        // entries this launch updates, in chunks of NB from r0
+  int nchunks;
+  int rowpanel;          // 0: z[i] -= sum_c T[i, xs + c] x[c]      1: z[c] -= sum_i T[xs + i, c] x[i]
+  int gd;                // the chunk that is the next diagonal block (-1: none) ...
+  const double *dinv;    // ... its stored inverse, applied transposed if dinv_t
+  int dinv_t;
+  const double *dinv2;   // Cholesky turn-around: a second product with this block (transposed), or NULL
+  int epi;               // last launch: res = alpha x + beta res — chunk gd for its own block, the further workgroups for the rest
+  void *res;
+  double alpha, beta;
+};
+
+__device__ __forceinline__ double block_gemv(const double *__restrict__ D, bool trans, const double *sb, double (*spart)[NB],
+                                             int lane, int q) {
+  double part = 0.0;
+#pragma unroll
+  for (int t = 0; t < 16; ++t) {
+    const int c = q * 16 + t;
+    part = fma(trans ? D[lane * NB + c] : D[c * NB + lane], sb[c], part);
+  }
+  spart[q][lane] = part;
+  __syncthreads();
+  const double x = (spart[0][lane] + spart[1][lane]) + (spart[2][lane] + spart[3][lane]);
+  __syncthreads();
+  return x;
+}
+
+template <typename T, bool BETA0>
+__device__ __forceinline__ void store_res(T *res, int64_t i, double x, double alpha, double beta) {
+  res[i] = BETA0 ? (T)(alpha * x) : (T)(alpha * x + beta * (double)res[i]);
+}
+
+template <typename T, bool BETA0>
+__global__ void __launch_bounds__(kBlock) sweep_kernel(SweepArgs a) {
+  __shared__ double sx[NB], sb[NB], spart[4][NB];
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int g = blockIdx.x;
+  T *res = (T *)a.res;
+  if (g >= a.nchunks) {                                  // epilogue of everything outside the block chunk gd solves
+    const int64_t d_lo = a.r0 + (int64_t)a.gd * NB;
+    const int64_t dl = a.r1 - d_lo < NB ? a.r1 - d_lo : NB;
+    const int64_t idx = (int64_t)(g - a.nchunks) * kBlock + tid;
+    if (idx < a.n - dl) {
+      const int64_t i = idx < d_lo ? idx : idx + dl;
+      store_res<T, BETA0>(res, i, a.z[i], a.alpha, a.beta);
+    }
+    return;
+  }
+  const T *Tm = (const T *)a.Tm;
+  const int64_t c_lo = a.r0 + (int64_t)g * NB;
+  const int cl = (int)(a.r1 - c_lo < NB ? a.r1 - c_lo : NB);
+  if (a.xl > 0) {
+    if (tid < NB) sx[tid] = tid < a.xl ? a.z[a.xs + tid] : 0.0;
+    __syncthreads();
+    if (!a.rowpanel) {
+      double acc = 0.0;
+      if (lane < cl) {
+        const T *row = Tm + (c_lo + lane) + a.xs * a.ld;
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+          const int c = q * 16 + t;
+          if (c < a.xl) acc = fma(ld_stream(row + (int64_t)c * a.ld), sx[c], acc);
+        }
+      }
+      spart[q][lane] = acc;
+    } else {
+      const double xi = sx[lane];
+      double val[16];
+#pragma unroll
+      for (int t = 0; t < 16; ++t) {
+        const int c = q * 16 + t;
+        val[t] = (c < cl && lane < a.xl) ? ld_stream(Tm + (a.xs + lane) + (c_lo + c) * a.ld) * xi : 0.0;
+      }
+#pragma unroll
+      for (int t = 0; t < 16; ++t) {
+        const double s = wave_sum(val[t]);
+        if (lane == 0) spart[0][q * 16 + t] = s;
+      }
+    }
+    __syncthreads();
+  }
+  double b = 0.0;
+  if (tid < cl) {
+    b = a.v ? (double)((const T *)a.v)[c_lo + tid] : a.z[c_lo + tid];
+    if (a.xl > 0) b -= a.rowpanel ? spart[0][tid] : (spart[0][tid] + spart[1][tid]) + (spart[2][tid] + spart[3][tid]);
+  }
+  if (g != a.gd) {
+    if (tid < cl) a.z[c_lo + tid] = b;
+    return;
+  }
+  __syncthreads();                                       // spart is reused below
+  if (tid < NB) sb[tid] = b;
+  __syncthreads();
+  double x = block_gemv(a.dinv, a.dinv_t != 0, sb, spart, lane, q);
+  if (a.dinv2) {
+    if (tid < NB) sb[tid] = x;
+    __syncthreads();
+    x = block_gemv(a.dinv2, true, sb, spart, lane, q);
+  }
+  if (tid < cl) {
+    a.z[c_lo + tid] = x;
+    if (a.epi) store_res<T, BETA0>(res, c_lo + tid, x, a.alpha, a.beta);
+  }
+}
+
+template <typename T>
+int32_t launch_sweep(mxlo_ctx *ctx, const SweepArgs &a) {
+  int64_t grid = a.nchunks;
+  if (a.epi) {
+    const int64_t d_lo = a.r0 + (int64_t)a.gd * NB, dl = a.r1 - d_lo < NB ? a.r1 - d_lo : NB;
+    grid += (a.n - dl + kBlock - 1) / kBlock;
+  }
+  MXLO_REQUIRE(grid < (1LL << 31), MXLO_ESHAPE, "triangular solve: n = %lld is too large", (long long)a.n);
+  if (a.beta == 0.0) hipLaunchKernelGGL((sweep_kernel<T, true>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
+  else hipLaunchKernelGGL((sweep_kernel<T, false>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
+  MXLO_LAUNCH_CHECK();
+  return MXLO_OK;
+}
+
+// One sweep: solves op(T) x = rhs. `ascending` = (lower, N) or (upper, T); the panel of a transposed solve is a block ROW.
+// first: the right-hand side comes from v (else z holds it and its first block is already solved). turn: after the last
+// block, multiply it by its transposed inverse once more (the first block of the Cholesky back sweep). epi: fuse the
+// alpha/beta epilogue into the last launch.
+template <typename T>
+int32_t sweep(mxlo_ctx *ctx, const T *Tm, int64_t ld, int64_t n, bool upper, bool trans, const double *dinv, double *z,
+              const T *v, bool first, bool turn, bool epi, T *res, double alpha, double beta) {
+  const int64_t nb = (n + NB - 1) / NB;
+  const bool asc = upper == trans;
+  SweepArgs a{};
+  a.Tm = Tm; a.ld = ld; a.n = n; a.z = z; a.rowpanel = trans; a.dinv_t = trans; a.res = res; a.alpha = alpha; a.beta = beta;
+  const int64_t kfirst = asc ? 0 : nb - 1, klast = asc ? nb - 1 : 0, step = asc ? 1 : -1;
+  if (first) {                                            // z = v, and the first block solved
+    a.v = v; a.xl = 0; a.r0 = 0; a.r1 = n; a.nchunks = (int)nb; a.gd = (int)kfirst;
+    a.dinv = dinv + kfirst * NB2;
+    a.dinv2 = (turn && nb == 1) ? a.dinv : nullptr;
+    a.epi = epi && nb == 1;
+    MXLO_TRY(launch_sweep<T>(ctx, a));
+    a.v = nullptr;
+  }
+  for (int64_t k = kfirst; k != klast; k += step) {       // panel k, then block k + step
+    const int64_t kn = k + step;
+    a.xs = k * NB;
+    a.xl = (int)(n - a.xs < NB ? n - a.xs : NB);
+    if (asc) { a.r0 = (k + 1) * NB; a.r1 = n; a.gd = 0; }
+    else { a.r0 = 0; a.r1 = k * NB; a.gd = (int)(k - 1); }
+    a.nchunks = (int)((a.r1 - a.r0 + NB - 1) / NB);
+    a.dinv = dinv + kn * NB2;
+    a.dinv2 = (turn && kn == klast) ? a.dinv : nullptr;
+    a.epi = epi && kn == klast;
+    MXLO_TRY(launch_sweep<T>(ctx, a));
+  }
+  return MXLO_OK;
+}
+
+int32_t check_common(mxlo_ctx *ctx, int32_t dtype, const void *A, int64_t ld, int64_t n, const char *what) {
+  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
+  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
+  MXLO_REQUIRE(n >= 0 && ld >= (n > 1 ? n : 1), MXLO_ESHAPE, "%s: n = %lld, ld = %lld", what, (long long)n, (long long)ld);
+  MXLO_REQUIRE(A || n == 0, MXLO_EINVAL, "%s: null matrix", what);
+  return MXLO_OK;
+}
+
+int32_t check_apply(mxlo_ctx *ctx, int32_t dtype, const void *res, const void *A, int64_t ld, int64_t n, const double *dinv,
+                    const double *work, const void *v, const char *what) {
+  MXLO_TRY(check_common(ctx, dtype, A, ld, n, what));
+  if (n == 0) return MXLO_OK;
+  MXLO_REQUIRE(res && v && dinv && work, MXLO_EINVAL, "%s: null operand", what);
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4, vb = n * es, ab = ((n - 1) * ld + n) * es, db = (n + NB - 1) / NB * NB2 * 8;
+  MXLO_REQUIRE(res == v || !bytes_overlap(res, vb, v, vb), MXLO_EINVAL,
+               "%s: res overlaps v without being v (only mul!(x, op, x) is defined)", what);
+  for (const void *p : {res, v})
+    MXLO_REQUIRE(!bytes_overlap(p, vb, A, ab) && !bytes_overlap(p, vb, dinv, db) && !bytes_overlap(p, vb, work, n * 8), MXLO_EINVAL,
+                 "%s: res / v overlap the matrix, the block inverses or the work vector", what);
+  return MXLO_OK;
+}
+
+template <typename T>
+int32_t potrf_t(mxlo_ctx *ctx, const T *M, int64_t ldm, int rowmajor, T *W, int64_t ldw, int64_t n, double *dinv, int *info_dev) {
+  const int64_t nb = (n + NB - 1) / NB;
+  MXLO_HIP(hipMemsetAsync(info_dev, 0, sizeof(int), ctx->stream));
+  if (M) {
+    hipLaunchKernelGGL((pack_upper_kernel<T>), dim3((unsigned)nb, (unsigned)nb), dim3(kBlock), 0, ctx->stream, W, ldw, M, ldm,
+                       rowmajor, n);
+    MXLO_LAUNCH_CHECK();
+  }
+  for (int64_t k = 0; k < nb; ++k) {
+    const int64_t j0 = k * NB, jb = n - j0 < NB ? n - j0 : NB, j1 = j0 + jb, m = n - j1;
+    hipLaunchKernelGGL((potrf_diag_kernel<T>), dim3(1), dim3(kBlock), 0, ctx->stream, W, ldw, n, j0, dinv + k * NB2, info_dev);
+    MXLO_LAUNCH_CHECK();
+    if (m <= 0) break;
+    const unsigned tiles = (unsigned)((m + NB - 1) / NB);
+    hipLaunchKernelGGL((potrf_panel_kernel<T>), dim3(tiles), dim3(kBlock), 0, ctx->stream, W, ldw, n, j0, (int)jb,
+                       (const double *)(dinv + k * NB2), (const int *)info_dev);
+    MXLO_LAUNCH_CHECK();
+    hipLaunchKernelGGL((potrf_syrk_kernel<T>), dim3(tiles, tiles), dim3(kBlock), 0, ctx->stream, W + j1 + j1 * ldw,
+                       (const T *)(W + j1 + j0 * ldw), ldw, (int)m, (int)jb, (const int *)info_dev);
+    MXLO_LAUNCH_CHECK();
+  }
+  return MXLO_OK;
+}
+
+}  // namespace
+
+MXLO_API int32_t mxlo_tri_kind(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ld, int64_t n, int32_t *kind_dev) {
+  MXLO_TRY(check_common(ctx, dtype, M, ld, n, "mxlo_tri_kind"));
+  MXLO_REQUIRE(kind_dev, MXLO_EINVAL, "mxlo_tri_kind: null result word");
+  MXLO_DEVICE_GUARD(ctx);
+  MXLO_HIP(hipMemsetAsync(kind_dev, 0, sizeof(int32_t), ctx->stream));
+  if (n == 0) return MXLO_OK;
+  const unsigned grid = (unsigned)(n < 4096 ? n : 4096);
+  if (dtype == MXLO_F64) hipLaunchKernelGGL((tri_kind_kernel<double>), dim3(grid), dim3(kBlock), 0, ctx->stream, (const double *)M, ld, n, kind_dev);
+  else hipLaunchKernelGGL((tri_kind_kernel<float>), dim3(grid), dim3(kBlock), 0, ctx->stream, (const float *)M, ld, n, kind_dev);
+  MXLO_LAUNCH_CHECK();
+  return MXLO_OK;
+}
+
+MXLO_API int32_t mxlo_tri_prepare(mxlo_ctx *ctx, int32_t dtype, const void *Tm, int64_t ld, int64_t n, int32_t upper, double *dinv) {
+  MXLO_TRY(check_common(ctx, dtype, Tm, ld, n, "mxlo_tri_prepare"));
+  if (n == 0) return MXLO_OK;
+  MXLO_REQUIRE(dinv, MXLO_EINVAL, "mxlo_tri_prepare: null storage for the block inverses");
+  MXLO_DEVICE_GUARD(ctx);
+  const unsigned nb = (unsigned)((n + NB - 1) / NB);
+  if (dtype == MXLO_F64) hipLaunchKernelGGL((tri_prepare_kernel<double>), dim3(nb), dim3(kBlock), 0, ctx->stream, (const double *)Tm, ld, n, upper ? 1 : 0, dinv);
+  else hipLaunchKernelGGL((tri_prepare_kernel<float>), dim3(nb), dim3(kBlock), 0, ctx->stream, (const float *)Tm, ld, n, upper ? 1 : 0, dinv);
+  MXLO_LAUNCH_CHECK();
+  return MXLO_OK;
+}
+
+MXLO_API int32_t mxlo_potrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_rowmajor, void *W, int64_t ldw,
+                            int64_t n, double *dinv, int32_t *info_dev, int32_t *info) {
+  MXLO_TRY(check_common(ctx, dtype, W, ldw, n, "mxlo_potrf"));
+  MXLO_REQUIRE(info, MXLO_EINVAL, "mxlo_potrf: null info");
+  *info = 0;
+  if (n == 0) return MXLO_OK;
+  MXLO_REQUIRE(dinv && info_dev, MXLO_EINVAL, "mxlo_potrf: null storage for the block inverses / the info word");
+  MXLO_REQUIRE(n < (1LL << 31) - NB, MXLO_ESHAPE, "mxlo_potrf: n = %lld is too large", (long long)n);
+  if (M) {
+    MXLO_REQUIRE(ldm >= (n > 1 ? n : 1), MXLO_ESHAPE, "mxlo_potrf: ldm = %lld < n", (long long)ldm);
+    const int64_t es = dtype == MXLO_F64 ? 8 : 4;
+    MXLO_REQUIRE(!bytes_overlap(M, ((n - 1) * ldm + n) * es, W, ((n - 1) * ldw + n) * es), MXLO_EINVAL,
+                 "mxlo_potrf: the factor's storage overlaps M");
+  }
+  MXLO_REQUIRE(!ctx->capturing, MXLO_ESTATE, "mxlo_potrf: reads its info word back, which a graph capture cannot hold");
+  MXLO_DEVICE_GUARD(ctx);
+  if (dtype == MXLO_F64) MXLO_TRY(potrf_t<double>(ctx, (const double *)M, ldm, m_rowmajor, (double *)W, ldw, n, dinv, info_dev));
+  else MXLO_TRY(potrf_t<float>(ctx, (const float *)M, ldm, m_rowmajor, (float *)W, ldw, n, dinv, info_dev));
+  MXLO_HIP(hipMemcpyAsync(info, info_dev, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MXLO_HIP(hipStreamSynchronize(ctx->stream));
+  return MXLO_OK;
+}
+
+MXLO_API int32_t mxlo_trisolve_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *Tm, int64_t ld, int64_t n, int32_t upper,
+                                   int32_t op_mode, const double *dinv, double *work, const void *v, double alpha, double beta) {
+  MXLO_TRY(check_apply(ctx, dtype, res, Tm, ld, n, dinv, work, v, "mxlo_trisolve_mul"));
+  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "mxlo_trisolve_mul: op_mode %d", op_mode);
+  if (n == 0) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  const bool tr = op_mode != MXLO_OP_N;
+  if (dtype == MXLO_F64)
+    return sweep<double>(ctx, (const double *)Tm, ld, n, upper != 0, tr, dinv, work, (const double *)v, true, false, true, (double *)res, alpha, beta);
+  return sweep<float>(ctx, (const float *)Tm, ld, n, upper != 0, tr, dinv, work, (const float *)v, true, false, true, (float *)res, alpha, beta);
+}
+
+namespace {
+template <typename T>
+int32_t chol_mul_t(mxlo_ctx *ctx, T *res, const T *L, int64_t ld, int64_t n, const double *dinv, double *work, const T *v, double alpha,
+                   double beta) {
+  const bool one = n <= NB;                              // a single block: both products and the epilogue in one launch
+  MXLO_TRY(sweep<T>(ctx, L, ld, n, false, false, dinv, work, v, true, true, one, res, alpha, beta));
+  if (one) return MXLO_OK;
+  return sweep<T>(ctx, L, ld, n, false, true, dinv, work, (const T *)nullptr, false, false, true, res, alpha, beta);
+}
+}  // namespace
+
+MXLO_API int32_t mxlo_chol_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *L, int64_t ld, int64_t n, const double *dinv,
+                               double *work, const void *v, double alpha, double beta) {
+  MXLO_TRY(check_apply(ctx, dtype, res, L, ld, n, dinv, work, v, "mxlo_chol_mul"));
+  if (n == 0) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  if (dtype == MXLO_F64) return chol_mul_t<double>(ctx, (double *)res, (const double *)L, ld, n, dinv, work, (const double *)v, alpha, beta);
+  return chol_mul_t<float>(ctx, (float *)res, (const float *)L, ld, n, dinv, work, (const float *)v, alpha, beta);
+}

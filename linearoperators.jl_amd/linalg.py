@@ -1,0 +1,143 @@
+"""opCholesky and triangular opInverse — src/linalg.jl:3-9 (mulFact!), :27-32 (opInverse), :44-58 (opCholesky).
+
+The factorisation, the inverses of the diagonal blocks and the block substitution sweeps run in libmxlo.so
+(csrc/linalg.hip); this module is the host mirror: argument checks, the storage an operator owns, the closures.
+Real Float64 / Float32 only. A pivoted LU for general dense `opInverse` and `opLDL` are not provided.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib
+from .device import Storage, ctx_of, dtype_code, get_ctx
+from .leaves import _stored_colmajor
+from .operators import LinearOperator, LinearOperatorException, columnwise, state_version
+
+BLOCK = 64            # block column width of csrc/linalg.hip (NB)
+
+
+class PosDefException(Exception):
+    """LinearAlgebra.PosDefException(info): the leading minor of order `info` (1-based) is not positive definite."""
+
+    def __init__(self, info: int):
+        super().__init__(f"matrix is not positive definite; Factorization failed (leading minor of order {info}).")
+        self.info = int(info)
+
+
+def _check_matrix(M, name: str) -> int:
+    """The checks that need no device, in the reference's order: square first, then the element type."""
+    if not isinstance(M, torch.Tensor) or M.dim() != 2:
+        raise TypeError(f"{name}: M must be a 2-D torch.Tensor on the GPU")
+    m, n = M.shape
+    if m != n:
+        raise LinearOperatorException("shape mismatch")
+    if M.dtype.is_complex:
+        raise TypeError(f"{name}: real Float64 / Float32 only, got {M.dtype} (complex factorisations are not instantiated)")
+    dtype_code(M.dtype)
+    if not M.is_cuda:
+        raise RuntimeError(f"{name}: M lives on {M.device}: the MI355X path has no CPU fallback")
+    return n
+
+
+def _check_operands(res, v, T):
+    if res.dtype is not T or v.dtype is not T:
+        raise TypeError(f"mul!: {res.dtype} / {v.dtype} operands next to a {T} factorisation")
+    if (res.numel() > 1 and res.stride(0) != 1) or (v.numel() > 1 and v.stride(0) != 1):
+        raise ValueError("mul!: res and v must have unit stride")
+
+
+def opCholesky(M: torch.Tensor, check: bool = False):
+    """opCholesky(M; check=false) — src/linalg.jl:44-58: the inverse of a symmetric positive definite matrix through its
+    Cholesky factorisation, computed ONCE here, on the device, into storage the operator owns (M is not modified).
+
+    Like `cholesky(M)` = `cholesky(Hermitian(M, :U))`, only the UPPER triangle of M is read; column-major and row-major
+    M are read in place, anything else is copied to column-major first. A pivot that is not positive and finite raises
+    `PosDefException(info)` with the 1-based order of the failing leading minor. `check=True` runs `check_hermitian`
+    and `check_positive_definite` first. prod! = tprod! = ctprod!: res = α (M⁻¹ v) + β res; with β == 0 res is not
+    read; res may be v. An apply allocates nothing and never synchronises, so it can be captured (`capture_mul`)."""
+    n = _check_matrix(M, "opCholesky")
+    T = M.dtype
+    if check:
+        from .utilities import check_hermitian, check_positive_definite
+        if not check_hermitian(M):
+            raise LinearOperatorException("matrix is not Hermitian")
+        if not check_positive_definite(M):
+            raise LinearOperatorException("matrix is not positive definite")
+    St, tr = _stored_colmajor(M)                       # tr: St is the column-major storage of Mᵀ, i.e. M is row-major
+    ldm = max(1, St.stride(1)) if n > 1 else 1
+    ctx = get_ctx(M.device)
+    W = torch.zeros((n, n), dtype=T, device=M.device).t()            # column-major, ld = n; the lower triangle is L
+    ldw = max(1, n)
+    nblk = (n + BLOCK - 1) // BLOCK
+    dinv = torch.empty(max(1, nblk) * BLOCK * BLOCK, dtype=torch.float64, device=M.device)
+    work = torch.empty(max(1, n), dtype=torch.float64, device=M.device)
+    info_dev = torch.zeros(1, dtype=torch.int32, device=M.device)
+    info = C.c_int32(0)
+    code = dtype_code(T)
+    _lib.call("mxlo_potrf", ctx.handle, code, St.data_ptr(), ldm, 1 if tr else 0, W.data_ptr(), ldw, n, dinv.data_ptr(),
+              info_dev.data_ptr(), C.byref(info))
+    if info.value != 0:
+        raise PosDefException(info.value)
+    pW, pD, pZ = W.data_ptr(), dinv.data_ptr(), work.data_ptr()
+
+    def prod(res, v, a, b):                             # mulFact!(res, LL, v, α, β) — src/linalg.jl:3-9
+        _check_operands(res, v, T)
+        _lib.call("mxlo_chol_mul", ctx_of(res).handle, code, res.data_ptr(), pW, ldw, n, pD, pZ, v.data_ptr(), float(a), float(b))
+
+    columnwise(prod)                                    # `F \ V` takes matrices: column by column
+    op = LinearOperator(T, n, n, True, True, prod, prod, prod, S=Storage(T, M.device))      # isreal(M), hermitian = true
+    op._deps = (W,)
+    op._factor = (W, dinv, work)                        # owned storage (kept alive with the operator)
+    return op
+
+
+def opInverse(M: torch.Tensor, symm: bool = False, herm: bool = False):
+    """opInverse(M; symm=false, herm=false) — src/linalg.jl:27-32, for a TRIANGULAR M: each apply is a triangular solve.
+
+    Whether M is lower or upper triangular is decided here, once, on the device (strict upper / strict lower part
+    exactly zero — the test dense `\\` makes; a diagonal M counts as lower). A square M that is neither raises: general
+    dense opInverse needs a pivoted LU, which this package does not have. M is ALIASED (column-major or row-major
+    storage; any other striding is copied once): a later in-place change of its values is seen by the next apply — the
+    inverses of its 64 x 64 diagonal blocks are cached under `state_version(M)` and rebuilt (one launch) when it
+    changes. The triangle kind stays what it was at construction. prod! solves with M, tprod! / ctprod! with Mᵀ.
+    A zero on the diagonal is NOT detected: the result then holds Inf / NaN and no exception is raised, as with the
+    reference's triangular `\\` on a device array. res may be v; with β == 0 res is not read."""
+    n = _check_matrix(M, "opInverse")
+    T = M.dtype
+    St, tr = _stored_colmajor(M)
+    ld = max(1, St.stride(1)) if n > 1 else 1
+    ctx = get_ctx(M.device)
+    code = dtype_code(T)
+    kind_dev = torch.zeros(1, dtype=torch.int32, device=M.device)
+    _lib.call("mxlo_tri_kind", ctx.handle, code, St.data_ptr(), ld, n, kind_dev.data_ptr())
+    bits = int(kind_dev.item())                         # the one read of the device word
+    if bits == 3:
+        raise LinearOperatorException("opInverse: M is neither lower nor upper triangular; general dense opInverse needs a "
+                                      "pivoted LU, which this package does not have")
+    st_upper = bits == 1                                # of the stored matrix; bits == 0 (diagonal) counts as lower
+    nblk = (n + BLOCK - 1) // BLOCK
+    dinv = torch.empty(max(1, nblk) * BLOCK * BLOCK, dtype=torch.float64, device=M.device)
+    work = torch.empty(max(1, n), dtype=torch.float64, device=M.device)
+    pT, pD, pZ = St.data_ptr(), dinv.data_ptr(), work.data_ptr()
+    cache = {"version": None}
+
+    def solve(res, v, a, b, mode):
+        _check_operands(res, v, T)
+        h = ctx_of(res).handle
+        ver = state_version(St)
+        if ver != cache["version"]:                     # M changed in place: its diagonal blocks' inverses are stale
+            _lib.call("mxlo_tri_prepare", h, code, pT, ld, n, 1 if st_upper else 0, pD)
+            cache["version"] = ver
+        _lib.call("mxlo_trisolve_mul", h, code, res.data_ptr(), pT, ld, n, 1 if st_upper else 0, mode, pD, pZ, v.data_ptr(),
+                  float(a), float(b))
+
+    fwd, bwd = (_lib.OP_T, _lib.OP_N) if tr else (_lib.OP_N, _lib.OP_T)
+    prod = columnwise(lambda res, v, a, b: solve(res, v, a, b, fwd))       # mulFact!(res, M, v, α, β)
+    tprod = columnwise(lambda res, u, a, b: solve(res, u, a, b, bwd))      # mulFact!(res, transpose(M), u, α, β)
+    op = LinearOperator(T, n, n, bool(symm), bool(herm), prod, tprod, tprod, S=Storage(T, M.device))
+    op._deps = (M,)
+    op._triangle = "lower" if (bits == 0 or st_upper == tr) else "upper"   # of M itself
+    op._factor = (St, dinv, work)
+    return op
