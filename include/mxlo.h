@@ -765,7 +765,7 @@ int32_t mxlo_krylov_combine(mxlo_ctx *ctx, int32_t dtype, const void *V, int64_t
                             const double *y_dev, void *out, double *coef);
 
 /* ======================================================================== */
-/*  opCholesky and triangular opInverse                                      */
+/*  opCholesky, opLDL and triangular opInverse                               */
 /* ======================================================================== */
 /* src/linalg.jl:3-9 (mulFact!), :27-32 (opInverse), :44-58 (opCholesky): `res .= α .* (F \ v) .+ β .* res` with F a
  * Cholesky factorisation or a triangular matrix. Real f32 / f64, column-major, any leading dimension and alignment.
@@ -796,6 +796,17 @@ int32_t mxlo_tri_prepare(mxlo_ctx *ctx, int32_t dtype, const void *T, int64_t ld
  * *info (host) = that word, copied once after the last launch — the only synchronisation. Not capturable. */
 int32_t mxlo_potrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_rowmajor, void *W, int64_t ldw,
                    int64_t n, double *dinv, int32_t *info_dev, int32_t *info);
+/* `ldlt(M)` of ext/LinearOperatorsLDLFactorizationsExt.jl:11 (opLDL(M::AbstractMatrix; check), :5-18; the docstring and
+ * stub are src/linalg.jl:60-75) for a DENSE symmetric M — M = L D L' with L unit lower triangular and D diagonal, WITHOUT
+ * pivoting: a static elimination order keeps the factorisation the same fixed chain of launches as mxlo_potrf (same
+ * arguments, same three phases per block column, same info word). W's strict lower triangle and diagonal receive
+ * Lt = L D (column c of L times d_c; the diagonal is d), so that M = Lt inv(D) Lt'; d (n doubles, f64 for both element
+ * types) receives the pivots and dinv the inverses of the diagonal blocks of Lt. Phase (c) is C -= (P inv(D_k)) P' with the
+ * column scaling applied while one operand is staged. Negative and tiny non-zero pivots are taken as they come. A pivot
+ * that is exactly zero or not finite stores its 1-BASED index, counted from the start of the matrix, in *info_dev; every
+ * later launch returns at once; *info (host) = that word, copied once after the last launch. Not capturable. */
+int32_t mxlo_ldlt(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_rowmajor, void *W, int64_t ldw,
+                  int64_t n, double *dinv, double *d, int32_t *info_dev, int32_t *info);
 /* mulFact!(res, M, v, α, β) / mulFact!(res, transpose(M), u, α, β) for triangular M (src/linalg.jl:28-30):
  * res = alpha * op(T)^{-1} v + beta * res, op_mode MXLO_OP_N / MXLO_OP_T (MXLO_OP_C == T). The strict triangle is read
  * once (nontemporal), the diagonal blocks not at all. ceil(n/64) launches. */
@@ -806,6 +817,15 @@ int32_t mxlo_trisolve_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *T
  * twice. 2 ceil(n/64) - 1 launches (one for n <= 64). */
 int32_t mxlo_chol_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *L, int64_t ld, int64_t n, const double *dinv,
                       double *work, const void *v, double alpha, double beta);
+
+/* mulFact!(res, LDL, v, α, β) with LDL = ldlt(M) (ext/LinearOperatorsLDLFactorizationsExt.jl:12-14, the closures of
+ * src/linalg.jl:3-9): res = alpha * Lt^{-T} (d .* (Lt^{-1} v)) + beta * res = alpha * M^{-1} v + beta * res with Lt, dinv
+ * and d from mxlo_ldlt. The sweeps are those of mxlo_chol_mul; the product with d costs no launch and no pass: the last
+ * block of the forward sweep is multiplied between its two 64 x 64 products, every other block as the first launch of
+ * the back sweep reads it. The triangle is read twice. 2 ceil(n/64) - 1 launches (one for n <= 64). res / v may not
+ * overlap d either. */
+int32_t mxlo_ldl_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *L, int64_t ld, int64_t n, const double *dinv,
+                     const double *d, double *work, const void *v, double alpha, double beta);
 
 #ifdef __cplusplus
 }

@@ -183,6 +183,8 @@ _PROTOS = {
     "mxlo_potrf": [_vp, _i32, _vp, _i64, _i32, _vp, _i64, _i64, _vp, _vp, C.POINTER(_i32)],
     "mxlo_trisolve_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _dbl, _dbl],
     "mxlo_chol_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _dbl, _dbl],
+    "mxlo_ldlt": [_vp, _i32, _vp, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _vp, C.POINTER(_i32)],
+    "mxlo_ldl_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _dbl, _dbl],
 }
 
 

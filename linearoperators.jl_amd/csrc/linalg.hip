@@ -1,5 +1,5 @@
-// linalg.hip — opCholesky and triangular opInverse (src/linalg.jl:3-9, 27-32, 44-58): the factorisation, the inverses of the
-// diagonal blocks and the block substitution sweeps. Everything is cut into block columns of NB = 64.
+// linalg.hip — opCholesky, opLDL (dense) and triangular opInverse (src/linalg.jl:3-9, 27-32, 44-58, 60-75): the factorisations, the
+// inverses of the diagonal blocks and the block substitution sweeps. Everything is cut into block columns of NB = 64.
 //
 // The only dependency mechanism is the LAUNCH BOUNDARY: no workgroup waits for another one. A sweep is a chain of launches,
 // one per block column (block row for a transposed solve). In launch k every workgroup reads the solved block x_k (64
@@ -55,6 +55,22 @@ __device__ int chol_block(double *sA, double *sL, int lane, int q) {
 #pragma unroll 4
     for (int c = q; c < NB; c += 4)
       if (c > p && lane >= c) sA[c * NB + lane] = fma(-lip, sL[p * NB + c], sA[c * NB + lane]);
+    __syncthreads();
+  }
+  return 0;
+}
+
+// Unpivoted LDL' of the lower triangle held in sA, in place: sA becomes Lt = L D (the pivots d on its diagonal, column c of
+// the unit L times d_c below it) — right-looking elimination that never scales a column. Returns 0, or the 1-based index
+// of the first pivot that is zero or not finite (the same value in every thread). Negative and tiny pivots are taken.
+__device__ int ldlt_block(double *sA, int lane, int q) {
+  for (int p = 0; p < NB; ++p) {
+    const double dp = sA[p * NB + p];
+    if (dp == 0.0 || !(fabs(dp) < __builtin_inf())) return p + 1;
+    const double lip = sA[p * NB + lane] / dp;
+#pragma unroll 4
+    for (int c = q; c < NB; c += 4)
+      if (c > p && lane >= c) sA[c * NB + lane] = fma(-lip, sA[p * NB + c], sA[c * NB + lane]);
     __syncthreads();
   }
   return 0;
@@ -147,10 +163,38 @@ __global__ void __launch_bounds__(kBlock) potrf_diag_kernel(T *__restrict__ W, i
   for (int e = tid; e < NB2; e += kBlock) dinv[e] = sA[e];
 }
 
-// phase (b): the panel below the diagonal block, W[i, j0 + c] = sum_{p <= c} W[i, j0 + p] inv(L_kk)[c, p], 64 rows a workgroup
+// phase (a) of mxlo_ldlt: M_kk = L_kk D_k L_kk'. The block keeps Lt_kk = L_kk D_k, d gets the pivots, dinv the inverse of Lt_kk
 template <typename T>
+__global__ void __launch_bounds__(kBlock) ldlt_diag_kernel(T *__restrict__ W, int64_t ldw, int64_t n, int64_t j0,
+                                                           double *__restrict__ dinv, double *__restrict__ d, int *info) {
+  __shared__ double sA[NB2], sX[NB2];
+  if (*info != 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int jb = (int)(n - j0 < NB ? n - j0 : NB);
+  for (int c = q; c < NB; c += 4) {
+    double x = lane == c ? 1.0 : 0.0;
+    if (lane >= c && lane < jb) x = (double)W[(j0 + lane) + (j0 + c) * ldw];
+    sA[c * NB + lane] = x;
+  }
+  __syncthreads();
+  const int bad = ldlt_block(sA, lane, q);
+  if (bad) {
+    if (tid == 0) *info = (int)(j0 + bad);
+    return;
+  }
+  for (int c = q; c < NB; c += 4)
+    if (lane >= c && lane < jb) W[(j0 + lane) + (j0 + c) * ldw] = (T)sA[c * NB + lane];
+  if (tid < jb) d[j0 + tid] = sA[tid * NB + tid];
+  invert_block(sA, sX, tid, lane, q);
+  for (int e = tid; e < NB2; e += kBlock) dinv[e] = sX[e];
+}
+
+// phase (b): the panel below the diagonal block, W[i, j0 + c] = sum_{p <= c} W[i, j0 + p] inv(L_kk)[c, p], 64 rows a workgroup.
+// LDL: dinv is inv(Lt_kk) = inv(D_k) inv(L_kk), so the sum is the panel of the unit L; times d_c it is the panel of Lt = L D.
+template <typename T, bool LDL>
 __global__ void __launch_bounds__(kBlock) potrf_panel_kernel(T *__restrict__ W, int64_t ldw, int64_t n, int64_t j0, int jb,
-                                                             const double *__restrict__ dinv, const int *info) {
+                                                             const double *__restrict__ dinv, const double *__restrict__ d,
+                                                             const int *info) {
   __shared__ double sP[NB2], sD[NB2];
   if (*info != 0) return;
   const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
@@ -161,11 +205,13 @@ __global__ void __launch_bounds__(kBlock) potrf_panel_kernel(T *__restrict__ W, 
   for (int c = q; c < jb; c += 4) {
     double acc = 0.0;
     for (int p = 0; p <= c; ++p) acc = fma(sP[p * NB + lane], sD[p * NB + c], acc);
+    if constexpr (LDL) acc *= d[j0 + c];
     if (i < n) W[i + (j0 + c) * ldw] = (T)acc;
   }
 }
 
 // phase (c): C -= P P' on the lower triangle of the trailing matrix; 64 x 64 tiles, the ones above the diagonal are skipped.
+// LDL: C -= (P inv(D_k)) P' with P the panel of Lt; the column scaling 1 / d is applied while the row operand is staged.
 // v_mfma_f64_16x16x4_f64: C/D row = (lane >> 4) + 4 reg, col = lane & 15; the f32 form has row = 4 (lane >> 4) + reg.
 template <typename T>
 struct Mfma;
@@ -184,13 +230,18 @@ struct Mfma<float> {
 
 constexpr int SK = 16, SLD = 80;     // k-slab and padded LDS row of the SYRK tiles (dense.hip's gemm_kernel uses the same)
 
-template <typename T>
+template <typename T, bool LDL>
 __global__ void __launch_bounds__(kBlock) potrf_syrk_kernel(T *__restrict__ C, const T *__restrict__ P, int64_t ld, int M, int K,
-                                                            const int *info) {
+                                                            const double *__restrict__ d, const int *info) {
   if (blockIdx.y > blockIdx.x) return;
   if (*info != 0) return;
   __shared__ T sA[SK][SLD], sB[SK][SLD];
+  __shared__ T sR[LDL ? NB : 1];                         // 1 / d of this block column (K <= NB)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if constexpr (LDL) {
+    if (tid < NB) sR[tid] = tid < K ? (T)(1.0 / d[tid]) : T(0);
+    __syncthreads();
+  }
   const int bm = blockIdx.x * NB, bn = blockIdx.y * NB;
   const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
   using Acc = typename Mfma<T>::Acc;
@@ -205,7 +256,9 @@ __global__ void __launch_bounds__(kBlock) potrf_syrk_kernel(T *__restrict__ C, c
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int e = tid + t * kBlock, i = e & 63, k = e >> 6, gk = k0 + k;
-      sA[k][i] = (bm + i < M && gk < K) ? P[(bm + i) + (int64_t)gk * ld] : T(0);
+      T pa = (bm + i < M && gk < K) ? P[(bm + i) + (int64_t)gk * ld] : T(0);
+      if constexpr (LDL) pa *= sR[gk & (NB - 1)];
+      sA[k][i] = pa;
       sB[k][i] = (bn + i < M && gk < K) ? P[(bn + i) + (int64_t)gk * ld] : T(0);
     }
     __syncthreads();
@@ -253,6 +306,8 @@ struct SweepArgs {
   int epi;               // last launch: res = alpha x + beta res — chunk gd for its own block, the further workgroups for the rest
   void *res;
   double alpha, beta;
+  const double *dsc;     // opLDL: the pivots d. The turn-around block is multiplied by them between its two products, and ...
+  int zscale;            // ... in the first launch of the back sweep every right-hand side block is, as it is read
 };
 
 __device__ __forceinline__ double block_gemv(const double *__restrict__ D, bool trans, const double *sb, double (*spart)[NB],
@@ -275,7 +330,7 @@ __device__ __forceinline__ void store_res(T *res, int64_t i, double x, double al
   res[i] = BETA0 ? (T)(alpha * x) : (T)(alpha * x + beta * (double)res[i]);
 }
 
-template <typename T, bool BETA0>
+template <typename T, bool BETA0, bool LDL>
 __global__ void __launch_bounds__(kBlock) sweep_kernel(SweepArgs a) {
   __shared__ double sx[NB], sb[NB], spart[4][NB];
   const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
@@ -327,6 +382,9 @@ __global__ void __launch_bounds__(kBlock) sweep_kernel(SweepArgs a) {
   double b = 0.0;
   if (tid < cl) {
     b = a.v ? (double)((const T *)a.v)[c_lo + tid] : a.z[c_lo + tid];
+    if constexpr (LDL) {
+      if (a.zscale) b *= a.dsc[c_lo + tid];
+    }
     if (a.xl > 0) b -= a.rowpanel ? spart[0][tid] : (spart[0][tid] + spart[1][tid]) + (spart[2][tid] + spart[3][tid]);
   }
   if (g != a.gd) {
@@ -338,6 +396,9 @@ __global__ void __launch_bounds__(kBlock) sweep_kernel(SweepArgs a) {
   __syncthreads();
   double x = block_gemv(a.dinv, a.dinv_t != 0, sb, spart, lane, q);
   if (a.dinv2) {
+    if constexpr (LDL) {
+      if (tid < cl) x *= a.dsc[c_lo + tid];
+    }
     if (tid < NB) sb[tid] = x;
     __syncthreads();
     x = block_gemv(a.dinv2, true, sb, spart, lane, q);
@@ -348,7 +409,7 @@ __global__ void __launch_bounds__(kBlock) sweep_kernel(SweepArgs a) {
   }
 }
 
-template <typename T>
+template <typename T, bool LDL>
 int32_t launch_sweep(mxlo_ctx *ctx, const SweepArgs &a) {
   int64_t grid = a.nchunks;
   if (a.epi) {
@@ -356,8 +417,8 @@ int32_t launch_sweep(mxlo_ctx *ctx, const SweepArgs &a) {
     grid += (a.n - dl + kBlock - 1) / kBlock;
   }
   MXLO_REQUIRE(grid < (1LL << 31), MXLO_ESHAPE, "triangular solve: n = %lld is too large", (long long)a.n);
-  if (a.beta == 0.0) hipLaunchKernelGGL((sweep_kernel<T, true>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
-  else hipLaunchKernelGGL((sweep_kernel<T, false>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
+  if (a.beta == 0.0) hipLaunchKernelGGL((sweep_kernel<T, true, LDL>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
+  else hipLaunchKernelGGL((sweep_kernel<T, false, LDL>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
   MXLO_LAUNCH_CHECK();
   return MXLO_OK;
 }
@@ -365,21 +426,23 @@ int32_t launch_sweep(mxlo_ctx *ctx, const SweepArgs &a) {
 // One sweep: solves op(T) x = rhs. `ascending` = (lower, N) or (upper, T); the panel of a transposed solve is a block ROW.
 // first: the right-hand side comes from v (else z holds it and its first block is already solved). turn: after the last
 // block, multiply it by its transposed inverse once more (the first block of the Cholesky back sweep). epi: fuse the
-// alpha/beta epilogue into the last launch.
-template <typename T>
+// alpha/beta epilogue into the last launch. dsc (opLDL): the pivots; they multiply the turn-around block between its two
+// products and, in a sweep that continues (!first), every other block as the first launch reads it.
+template <typename T, bool LDL = false>
 int32_t sweep(mxlo_ctx *ctx, const T *Tm, int64_t ld, int64_t n, bool upper, bool trans, const double *dinv, double *z,
-              const T *v, bool first, bool turn, bool epi, T *res, double alpha, double beta) {
+              const T *v, bool first, bool turn, bool epi, T *res, double alpha, double beta, const double *dsc = nullptr) {
   const int64_t nb = (n + NB - 1) / NB;
   const bool asc = upper == trans;
   SweepArgs a{};
   a.Tm = Tm; a.ld = ld; a.n = n; a.z = z; a.rowpanel = trans; a.dinv_t = trans; a.res = res; a.alpha = alpha; a.beta = beta;
+  a.dsc = dsc;
   const int64_t kfirst = asc ? 0 : nb - 1, klast = asc ? nb - 1 : 0, step = asc ? 1 : -1;
   if (first) {                                            // z = v, and the first block solved
     a.v = v; a.xl = 0; a.r0 = 0; a.r1 = n; a.nchunks = (int)nb; a.gd = (int)kfirst;
     a.dinv = dinv + kfirst * NB2;
     a.dinv2 = (turn && nb == 1) ? a.dinv : nullptr;
     a.epi = epi && nb == 1;
-    MXLO_TRY(launch_sweep<T>(ctx, a));
+    MXLO_TRY((launch_sweep<T, LDL>(ctx, a)));
     a.v = nullptr;
   }
   for (int64_t k = kfirst; k != klast; k += step) {       // panel k, then block k + step
@@ -392,7 +455,8 @@ int32_t sweep(mxlo_ctx *ctx, const T *Tm, int64_t ld, int64_t n, bool upper, boo
     a.dinv = dinv + kn * NB2;
     a.dinv2 = (turn && kn == klast) ? a.dinv : nullptr;
     a.epi = epi && kn == klast;
-    MXLO_TRY(launch_sweep<T>(ctx, a));
+    a.zscale = LDL && !first && k == kfirst;
+    MXLO_TRY((launch_sweep<T, LDL>(ctx, a)));
   }
   return MXLO_OK;
 }
@@ -419,8 +483,10 @@ int32_t check_apply(mxlo_ctx *ctx, int32_t dtype, const void *res, const void *A
   return MXLO_OK;
 }
 
-template <typename T>
-int32_t potrf_t(mxlo_ctx *ctx, const T *M, int64_t ldm, int rowmajor, T *W, int64_t ldw, int64_t n, double *dinv, int *info_dev) {
+// LDL: the chain of mxlo_ldlt — the same launches with the LDL' diagonal step and the pivots d handed to phases (b) and (c)
+template <typename T, bool LDL>
+int32_t potrf_t(mxlo_ctx *ctx, const T *M, int64_t ldm, int rowmajor, T *W, int64_t ldw, int64_t n, double *dinv, double *d,
+                int *info_dev) {
   const int64_t nb = (n + NB - 1) / NB;
   MXLO_HIP(hipMemsetAsync(info_dev, 0, sizeof(int), ctx->stream));
   if (M) {
@@ -430,15 +496,17 @@ int32_t potrf_t(mxlo_ctx *ctx, const T *M, int64_t ldm, int rowmajor, T *W, int6
   }
   for (int64_t k = 0; k < nb; ++k) {
     const int64_t j0 = k * NB, jb = n - j0 < NB ? n - j0 : NB, j1 = j0 + jb, m = n - j1;
-    hipLaunchKernelGGL((potrf_diag_kernel<T>), dim3(1), dim3(kBlock), 0, ctx->stream, W, ldw, n, j0, dinv + k * NB2, info_dev);
+    if constexpr (LDL) hipLaunchKernelGGL((ldlt_diag_kernel<T>), dim3(1), dim3(kBlock), 0, ctx->stream, W, ldw, n, j0, dinv + k * NB2, d, info_dev);
+    else hipLaunchKernelGGL((potrf_diag_kernel<T>), dim3(1), dim3(kBlock), 0, ctx->stream, W, ldw, n, j0, dinv + k * NB2, info_dev);
     MXLO_LAUNCH_CHECK();
     if (m <= 0) break;
     const unsigned tiles = (unsigned)((m + NB - 1) / NB);
-    hipLaunchKernelGGL((potrf_panel_kernel<T>), dim3(tiles), dim3(kBlock), 0, ctx->stream, W, ldw, n, j0, (int)jb,
-                       (const double *)(dinv + k * NB2), (const int *)info_dev);
+    hipLaunchKernelGGL((potrf_panel_kernel<T, LDL>), dim3(tiles), dim3(kBlock), 0, ctx->stream, W, ldw, n, j0, (int)jb,
+                       (const double *)(dinv + k * NB2), (const double *)d, (const int *)info_dev);
     MXLO_LAUNCH_CHECK();
-    hipLaunchKernelGGL((potrf_syrk_kernel<T>), dim3(tiles, tiles), dim3(kBlock), 0, ctx->stream, W + j1 + j1 * ldw,
-                       (const T *)(W + j1 + j0 * ldw), ldw, (int)m, (int)jb, (const int *)info_dev);
+    hipLaunchKernelGGL((potrf_syrk_kernel<T, LDL>), dim3(tiles, tiles), dim3(kBlock), 0, ctx->stream, W + j1 + j1 * ldw,
+                       (const T *)(W + j1 + j0 * ldw), ldw, (int)m, (int)jb, (const double *)(LDL ? d + j0 : nullptr),
+                       (const int *)info_dev);
     MXLO_LAUNCH_CHECK();
   }
   return MXLO_OK;
@@ -471,27 +539,47 @@ MXLO_API int32_t mxlo_tri_prepare(mxlo_ctx *ctx, int32_t dtype, const void *Tm, 
   return MXLO_OK;
 }
 
-MXLO_API int32_t mxlo_potrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_rowmajor, void *W, int64_t ldw,
-                            int64_t n, double *dinv, int32_t *info_dev, int32_t *info) {
-  MXLO_TRY(check_common(ctx, dtype, W, ldw, n, "mxlo_potrf"));
-  MXLO_REQUIRE(info, MXLO_EINVAL, "mxlo_potrf: null info");
+namespace {
+// mxlo_potrf (d == NULL) and mxlo_ldlt: the checks, the chain of launches, the one copy of the info word
+int32_t factor(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_rowmajor, void *W, int64_t ldw, int64_t n,
+               double *dinv, double *d, int32_t *info_dev, int32_t *info, const char *what) {
+  MXLO_TRY(check_common(ctx, dtype, W, ldw, n, what));
+  MXLO_REQUIRE(info, MXLO_EINVAL, "%s: null info", what);
   *info = 0;
   if (n == 0) return MXLO_OK;
-  MXLO_REQUIRE(dinv && info_dev, MXLO_EINVAL, "mxlo_potrf: null storage for the block inverses / the info word");
-  MXLO_REQUIRE(n < (1LL << 31) - NB, MXLO_ESHAPE, "mxlo_potrf: n = %lld is too large", (long long)n);
+  MXLO_REQUIRE(dinv && info_dev, MXLO_EINVAL, "%s: null storage for the block inverses / the info word", what);
+  MXLO_REQUIRE(n < (1LL << 31) - NB, MXLO_ESHAPE, "%s: n = %lld is too large", what, (long long)n);
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4, wb = ((n - 1) * ldw + n) * es;
   if (M) {
-    MXLO_REQUIRE(ldm >= (n > 1 ? n : 1), MXLO_ESHAPE, "mxlo_potrf: ldm = %lld < n", (long long)ldm);
-    const int64_t es = dtype == MXLO_F64 ? 8 : 4;
-    MXLO_REQUIRE(!bytes_overlap(M, ((n - 1) * ldm + n) * es, W, ((n - 1) * ldw + n) * es), MXLO_EINVAL,
-                 "mxlo_potrf: the factor's storage overlaps M");
+    MXLO_REQUIRE(ldm >= (n > 1 ? n : 1), MXLO_ESHAPE, "%s: ldm = %lld < n", what, (long long)ldm);
+    MXLO_REQUIRE(!bytes_overlap(M, ((n - 1) * ldm + n) * es, W, wb), MXLO_EINVAL, "%s: the factor's storage overlaps M", what);
   }
-  MXLO_REQUIRE(!ctx->capturing, MXLO_ESTATE, "mxlo_potrf: reads its info word back, which a graph capture cannot hold");
+  if (d) MXLO_REQUIRE(!bytes_overlap(d, n * 8, W, wb) && !bytes_overlap(d, n * 8, dinv, (n + NB - 1) / NB * NB2 * 8), MXLO_EINVAL,
+                      "%s: the pivots' storage overlaps the factor or the block inverses", what);
+  MXLO_REQUIRE(!ctx->capturing, MXLO_ESTATE, "%s: reads its info word back, which a graph capture cannot hold", what);
   MXLO_DEVICE_GUARD(ctx);
-  if (dtype == MXLO_F64) MXLO_TRY(potrf_t<double>(ctx, (const double *)M, ldm, m_rowmajor, (double *)W, ldw, n, dinv, info_dev));
-  else MXLO_TRY(potrf_t<float>(ctx, (const float *)M, ldm, m_rowmajor, (float *)W, ldw, n, dinv, info_dev));
+  if (d) {
+    if (dtype == MXLO_F64) MXLO_TRY((potrf_t<double, true>(ctx, (const double *)M, ldm, m_rowmajor, (double *)W, ldw, n, dinv, d, info_dev)));
+    else MXLO_TRY((potrf_t<float, true>(ctx, (const float *)M, ldm, m_rowmajor, (float *)W, ldw, n, dinv, d, info_dev)));
+  } else {
+    if (dtype == MXLO_F64) MXLO_TRY((potrf_t<double, false>(ctx, (const double *)M, ldm, m_rowmajor, (double *)W, ldw, n, dinv, d, info_dev)));
+    else MXLO_TRY((potrf_t<float, false>(ctx, (const float *)M, ldm, m_rowmajor, (float *)W, ldw, n, dinv, d, info_dev)));
+  }
   MXLO_HIP(hipMemcpyAsync(info, info_dev, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   MXLO_HIP(hipStreamSynchronize(ctx->stream));
   return MXLO_OK;
+}
+}  // namespace
+
+MXLO_API int32_t mxlo_potrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_rowmajor, void *W, int64_t ldw,
+                            int64_t n, double *dinv, int32_t *info_dev, int32_t *info) {
+  return factor(ctx, dtype, M, ldm, m_rowmajor, W, ldw, n, dinv, nullptr, info_dev, info, "mxlo_potrf");
+}
+
+MXLO_API int32_t mxlo_ldlt(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_rowmajor, void *W, int64_t ldw,
+                           int64_t n, double *dinv, double *d, int32_t *info_dev, int32_t *info) {
+  MXLO_REQUIRE(d || n == 0, MXLO_EINVAL, "mxlo_ldlt: null storage for the pivots");
+  return factor(ctx, dtype, M, ldm, m_rowmajor, W, ldw, n, dinv, d, info_dev, info, "mxlo_ldlt");
 }
 
 MXLO_API int32_t mxlo_trisolve_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *Tm, int64_t ld, int64_t n, int32_t upper,
@@ -524,4 +612,29 @@ MXLO_API int32_t mxlo_chol_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const vo
   MXLO_DEVICE_GUARD(ctx);
   if (dtype == MXLO_F64) return chol_mul_t<double>(ctx, (double *)res, (const double *)L, ld, n, dinv, work, (const double *)v, alpha, beta);
   return chol_mul_t<float>(ctx, (float *)res, (const float *)L, ld, n, dinv, work, (const float *)v, alpha, beta);
+}
+
+namespace {
+// x = Lt^{-T} (d .* (Lt^{-1} v)) with Lt = L D: the two sweeps of chol_mul_t; where the pivots come in is said at sweep()
+template <typename T>
+int32_t ldl_mul_t(mxlo_ctx *ctx, T *res, const T *L, int64_t ld, int64_t n, const double *dinv, const double *d, double *work,
+                  const T *v, double alpha, double beta) {
+  const bool one = n <= NB;
+  MXLO_TRY((sweep<T, true>(ctx, L, ld, n, false, false, dinv, work, v, true, true, one, res, alpha, beta, d)));
+  if (one) return MXLO_OK;
+  return sweep<T, true>(ctx, L, ld, n, false, true, dinv, work, (const T *)nullptr, false, false, true, res, alpha, beta, d);
+}
+}  // namespace
+
+MXLO_API int32_t mxlo_ldl_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *L, int64_t ld, int64_t n, const double *dinv,
+                              const double *d, double *work, const void *v, double alpha, double beta) {
+  MXLO_TRY(check_apply(ctx, dtype, res, L, ld, n, dinv, work, v, "mxlo_ldl_mul"));
+  if (n == 0) return MXLO_OK;
+  MXLO_REQUIRE(d, MXLO_EINVAL, "mxlo_ldl_mul: null pivots");
+  const int64_t vb = n * (dtype == MXLO_F64 ? 8 : 4);
+  MXLO_REQUIRE(!bytes_overlap(res, vb, d, n * 8) && !bytes_overlap(v, vb, d, n * 8), MXLO_EINVAL,
+               "mxlo_ldl_mul: res / v overlap the pivots");
+  MXLO_DEVICE_GUARD(ctx);
+  if (dtype == MXLO_F64) return ldl_mul_t<double>(ctx, (double *)res, (const double *)L, ld, n, dinv, d, work, (const double *)v, alpha, beta);
+  return ldl_mul_t<float>(ctx, (float *)res, (const float *)L, ld, n, dinv, d, work, (const float *)v, alpha, beta);
 }

@@ -1,8 +1,10 @@
-"""opCholesky and triangular opInverse — src/linalg.jl:3-9 (mulFact!), :27-32 (opInverse), :44-58 (opCholesky).
+"""opCholesky, opLDL and triangular opInverse — src/linalg.jl:3-9 (mulFact!), :27-32 (opInverse), :44-58 (opCholesky),
+:60-75 with ext/LinearOperatorsLDLFactorizationsExt.jl:5-18 (opLDL of a dense matrix).
 
 The factorisation, the inverses of the diagonal blocks and the block substitution sweeps run in libmxlo.so
 (csrc/linalg.hip); this module is the host mirror: argument checks, the storage an operator owns, the closures.
-Real Float64 / Float32 only. A pivoted LU for general dense `opInverse` and `opLDL` are not provided.
+Real Float64 / Float32 only. A pivoted LU for general dense `opInverse`, a pivoted (Bunch–Kaufman) or sparse LDLᵀ are not
+provided.
 """
 from __future__ import annotations
 
@@ -23,6 +25,16 @@ class PosDefException(Exception):
 
     def __init__(self, info: int):
         super().__init__(f"matrix is not positive definite; Factorization failed (leading minor of order {info}).")
+        self.info = int(info)
+
+
+class ZeroPivotException(Exception):
+    """LinearAlgebra.ZeroPivotException(info): the unpivoted LDLᵀ met a pivot that is exactly zero or not finite at the
+    1-based index `info`, counted from the start of the matrix."""
+
+    def __init__(self, info: int):
+        super().__init__(f"ZeroPivotException: factorization encountered one or more zero pivots. Consider switching "
+                         f"to a pivoted factorization (first zero or non-finite pivot: {info}).")
         self.info = int(info)
 
 
@@ -90,6 +102,59 @@ def opCholesky(M: torch.Tensor, check: bool = False):
     op = LinearOperator(T, n, n, True, True, prod, prod, prod, S=Storage(T, M.device))      # isreal(M), hermitian = true
     op._deps = (W,)
     op._factor = (W, dinv, work)                        # owned storage (kept alive with the operator)
+    return op
+
+
+def opLDL(M: torch.Tensor, check: bool = False):
+    """opLDL(M; check=false) — ext/LinearOperatorsLDLFactorizationsExt.jl:5-18 (docstring: src/linalg.jl:60-73) for a DENSE
+    symmetric M: its inverse through M = L D Lᵀ (L unit lower triangular, D diagonal), computed ONCE here, on the device,
+    into storage the operator owns (M is not modified). Only the UPPER triangle of M is read (`Symmetric(M, :U)`);
+    column-major and row-major M are read in place, anything else is copied to column-major first. `check=True` runs
+    `check_hermitian` first; there is no definiteness check.
+
+    There is NO pivoting: no symmetric permutation and no 2 x 2 (Bunch–Kaufman) pivots. The factorisation is taken "if it
+    exists", in the order the rows come, which keeps it a fixed chain of launches without a host round trip. Negative
+    pivots and tiny non-zero pivots are legitimate and are used as they come; a pivot that is exactly zero or not finite
+    raises `ZeroPivotException(info)` with its 1-based index. The solve is backward stable when
+    ‖ |L||D||Lᵀ| ‖ / ‖M‖ is modest, which holds for symmetric quasi-definite matrices [A Bᵀ; B −C] (A, C positive
+    definite) in any symmetric permutation, and for definite ones; for a general indefinite M it need not be.
+
+    prod! = tprod! = ctprod!: res = α (M⁻¹ v) + β res; with β == 0 res is not read; res may be v. An apply allocates
+    nothing and never synchronises, so it can be captured (`capture_mul`). `op._d` is a Float64 device tensor with the n
+    pivots (the diagonal of D): by Sylvester's law of inertia their signs are the inertia of M."""
+    n = _check_matrix(M, "opLDL")
+    T = M.dtype
+    if check:
+        from .utilities import check_hermitian
+        if not check_hermitian(M):
+            raise LinearOperatorException("matrix is not Hermitian")
+    St, tr = _stored_colmajor(M)
+    ldm = max(1, St.stride(1)) if n > 1 else 1
+    ctx = get_ctx(M.device)
+    W = torch.zeros((n, n), dtype=T, device=M.device).t()            # column-major, ld = n; the lower triangle is L D
+    ldw = max(1, n)
+    nblk = (n + BLOCK - 1) // BLOCK
+    dinv = torch.empty(max(1, nblk) * BLOCK * BLOCK, dtype=torch.float64, device=M.device)
+    d = torch.empty(n, dtype=torch.float64, device=M.device)
+    work = torch.empty(max(1, n), dtype=torch.float64, device=M.device)
+    info_dev = torch.zeros(1, dtype=torch.int32, device=M.device)
+    info = C.c_int32(0)
+    code = dtype_code(T)
+    _lib.call("mxlo_ldlt", ctx.handle, code, St.data_ptr(), ldm, 1 if tr else 0, W.data_ptr(), ldw, n, dinv.data_ptr(),
+              d.data_ptr(), info_dev.data_ptr(), C.byref(info))
+    if info.value != 0:
+        raise ZeroPivotException(info.value)
+    pW, pD, pd, pZ = W.data_ptr(), dinv.data_ptr(), d.data_ptr(), work.data_ptr()
+
+    def prod(res, v, a, b):                             # mulFact!(res, LDL, v, α, β) — src/linalg.jl:3-9
+        _check_operands(res, v, T)
+        _lib.call("mxlo_ldl_mul", ctx_of(res).handle, code, res.data_ptr(), pW, ldw, n, pD, pd, pZ, v.data_ptr(), float(a), float(b))
+
+    columnwise(prod)
+    op = LinearOperator(T, n, n, True, True, prod, prod, prod, S=Storage(T, M.device))      # isreal(M), hermitian = true
+    op._deps = (W,)
+    op._d = d                                           # the pivots; their signs are the inertia of M
+    op._factor = (W, dinv, d, work)
     return op
 
 
