@@ -827,6 +827,34 @@ int32_t mxlo_chol_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *L, in
 int32_t mxlo_ldl_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *L, int64_t ld, int64_t n, const double *dinv,
                      const double *d, double *work, const void *v, double alpha, double beta);
 
+/* `lu(M)`, the factorisation behind `M \ v` of a general square M (src/linalg.jl:27-32; test/test_linop.jl:471-479): P A = L U
+ * with PARTIAL PIVOTING, right-looking in block columns of 64, in the operator's own column-major W (n x n, ldw). M != NULL:
+ * W is first filled from M (column-major, ldm; M is not modified); M == NULL: W is factored in place. L is unit lower
+ * triangular below the diagonal of W, U on and above it. Per block column: (a) ONE workgroup factors the whole panel — for
+ * each column the pivot is the first row i >= j with the largest |a_ij| over the WHOLE remaining height (a NaN wins), the two
+ * rows change places inside the panel, the multipliers are f64 quotients stored in the element type — so the
+ * data-dependent decision never leaves the device and the number of launches depends on n only; (b) the inverses of the
+ * unit lower and of the upper triangle of the diagonal block go to dinv_l / dinv_u (each ceil(n/64) blocks of 64 x 64
+ * doubles, identity-padded); (c) the panel's interchanges are applied to the columns left and right of it (rows are
+ * swapped physically, LAPACK's convention); (d) U12 = inv(L11) A12 with the stored inverse; (e) A22 -= L21 U12 with
+ * v_mfma_f64_16x16x4_f64 (f32 data: the f32 MFMA). perm is 2 n int32 on the device: perm[0 .. n) is the permutation,
+ * A[perm[i], :] = (L U)[i, :], 0-based; perm[n .. 2 n) is LAPACK's ipiv, 0-based (row i changed places with row ipiv[i]).
+ * A pivot that is exactly zero or not finite stores its 1-BASED index, counted from the start of the matrix
+ * (LinearAlgebra.SingularException(info)), in *info_dev; every later launch returns at once; *info (host) = that word,
+ * copied once after the last launch — the only synchronisation. Not capturable (MXLO_ESTATE). */
+int32_t mxlo_getrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, void *W, int64_t ldw, int64_t n, double *dinv_l,
+                   double *dinv_u, int32_t *perm, int32_t *info_dev, int32_t *info);
+/* mulFact!(res, lu(M), v, α, β): res = alpha * op(A)^{-1} v + beta * res with W, dinv_l, dinv_u and perm (its first n
+ * entries) from mxlo_getrf. MXLO_OP_N: the first launch gathers v[perm[i]] into the f64 work vector, the unit lower sweep
+ * ascends, its last block is multiplied by inv(U) of that block in the same launch, the upper sweep descends with the
+ * epilogue fused into its last launch. MXLO_OP_T (MXLO_OP_C == T): the U' sweep ascends with row panels, the turn-around
+ * applies inv(L)' of the last block, the L' sweep descends, the epilogue scatters, res[perm[i]] = alpha z[i] + beta
+ * res[perm[i]]. 2 ceil(n/64) - 1 launches (one for n <= 64) and nothing else. res == v is allowed; res / v may not
+ * overlap W, either set of block inverses, perm or work. */
+int32_t mxlo_lu_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t n, const double *dinv_l,
+                    const double *dinv_u, const int32_t *perm, double *work, const void *v, int32_t op_mode, double alpha,
+                    double beta);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,7 +33,7 @@ from .diagqn import DiagonalAndrei, DiagonalBFGS, DiagonalPSB, SpectralGradient
 from .graph import CapturedSequence, capture_mul
 from .utilities import check_ctranspose, check_hermitian, check_positive_definite, normest
 from .opnorm import estimate_opnorm
-from .linalg import PosDefException, ZeroPivotException, opCholesky, opInverse, opLDL
+from .linalg import PosDefException, SingularException, ZeroPivotException, opCholesky, opInverse, opLDL, opLU
 
 try:
     from . import sharded

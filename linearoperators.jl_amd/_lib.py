@@ -185,6 +185,8 @@ _PROTOS = {
     "mxlo_chol_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _dbl, _dbl],
     "mxlo_ldlt": [_vp, _i32, _vp, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _vp, C.POINTER(_i32)],
     "mxlo_ldl_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _dbl, _dbl],
+    "mxlo_getrf": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i32)],
+    "mxlo_lu_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl],
 }
 
 

@@ -1,4 +1,4 @@
-// linalg.hip — opCholesky, opLDL (dense) and triangular opInverse (src/linalg.jl:3-9, 27-32, 44-58, 60-75): the factorisations, the
+// linalg.hip — opCholesky, opLDL (dense), opLU and triangular opInverse (src/linalg.jl:3-9, 27-32, 44-58, 60-75): the factorisations, the
 // inverses of the diagonal blocks and the block substitution sweeps. Everything is cut into block columns of NB = 64.
 //
 // The only dependency mechanism is the LAUNCH BOUNDARY: no workgroup waits for another one. A sweep is a chain of launches,
@@ -288,6 +288,217 @@ __global__ void __launch_bounds__(kBlock) potrf_syrk_kernel(T *__restrict__ C, c
       }
 }
 
+// ---------------------------------------------------------------------------------------------- getrf
+// P A = L U with partial pivoting, right-looking in block columns of NB. Per block column: (a) ONE workgroup factors the
+// whole panel (all rows below, in global memory: the panel of a large matrix does not fit a CU), searching each pivot
+// over the full remaining height, so the data-dependent decision never leaves the device and the chain of launches
+// depends on n only; (b) the inverses of both triangles of the diagonal block; (c) the panel's interchanges applied to
+// the columns left and right of it; (d) U12 = inv(L11) A12; (e) A22 -= L21 U12 on MFMA.
+constexpr int PT = 1024;             // threads of the panel workgroup: 16 waves hide the latency of one CU's loads
+
+// is the candidate (|a|, ia) a better pivot than (|b|, ib)? The larger one, a NaN before any number, the first row on a tie
+__device__ __forceinline__ bool pivot_better(double a, int ia, double b, int ib) {
+  const bool an = a != a, bn = b != b;
+  if (an || bn) return an && (!bn || ia < ib);
+  return a > b || (a == b && ia < ib);
+}
+
+// W = M and perm = ipiv = 0 .. n - 1 (M == NULL: only the latter)
+template <typename T>
+__global__ void __launch_bounds__(kBlock) getrf_copy_kernel(T *__restrict__ W, int64_t ldw, const T *__restrict__ M, int64_t ldm,
+                                                            int64_t n, int *__restrict__ perm) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  if (blockIdx.y == 0) perm[i] = perm[n + i] = (int)i;
+  if (M)
+    for (int64_t c = blockIdx.y; c < n; c += gridDim.y) W[i + c * ldw] = M[i + c * ldm];
+}
+
+// phase (a): columns j0 .. j0 + jb of rows j0 .. n. For each column: the pivot search, the interchange inside the panel,
+// the multipliers (f64 quotient, stored in T) and the rank-1 update of the panel's remaining columns.
+template <typename T>
+__global__ void __launch_bounds__(PT) getrf_panel_kernel(T *W, int64_t ldw, int64_t n, int64_t j0, int jb, int *perm, int *info) {
+  __shared__ double s_val[PT / 64], s_u[NB], s_pv;
+  __shared__ int s_idx[PT / 64], s_row, s_bad;
+  if (*info != 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int *ipiv = perm + n;
+  for (int p = 0; p < jb; ++p) {
+    const int64_t jp = j0 + p;
+    T *col = W + jp * ldw;
+    double best = -1.0;                                  // below every |a|: the first candidate is always taken
+    int bi = 0x7fffffff;
+    for (int64_t i = jp + tid; i < n; i += PT) {
+      const double a = fabs((double)col[i]);
+      if (!(a <= best) && best == best) { best = a; bi = (int)i; }      // a NaN is taken and then kept
+    }
+    for (int o = 32; o; o >>= 1) {
+      const double ob = __shfl_xor(best, o);
+      const int oi = __shfl_xor(bi, o);
+      if (pivot_better(ob, oi, best, bi)) { best = ob; bi = oi; }
+    }
+    if (lane == 0) { s_val[wave] = best; s_idx[wave] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < PT / 64; ++w)
+        if (pivot_better(s_val[w], s_idx[w], best, bi)) { best = s_val[w]; bi = s_idx[w]; }
+      const double pv = (double)col[bi];
+      const int bad = pv == 0.0 || !(fabs(pv) < __builtin_inf());
+      if (bad) *info = (int)(jp + 1);
+      else {
+        ipiv[jp] = bi;
+        const int t = perm[jp];
+        perm[jp] = perm[bi];
+        perm[bi] = t;
+      }
+      s_row = bi; s_pv = pv; s_bad = bad;
+    }
+    __syncthreads();
+    if (s_bad) return;
+    const int64_t r = s_row;
+    const double pv = s_pv;
+    if (tid < jb) {                                      // rows jp and r change places inside the panel; row p of U to LDS
+      T *c = W + (j0 + tid) * ldw;
+      const T x = c[r];
+      if (r != jp) { c[r] = c[jp]; c[jp] = x; }
+      s_u[tid] = (double)x;
+    }
+    __syncthreads();
+    const int64_t rows = n - jp - 1, rch = (rows + 63) / 64;
+    for (int64_t rc = wave; rc < rch; rc += PT / 64) {    // 64 rows a wave: the multiplier, then its row of the update
+      const int64_t i = jp + 1 + rc * 64 + lane;
+      if (i < n) {
+        const T lt = (T)((double)col[i] / pv);
+        col[i] = lt;
+        const double l = (double)lt;
+        for (int c = p + 1; c < jb; ++c) {
+          T *e = W + i + (j0 + c) * ldw;
+          *e = (T)fma(-l, s_u[c], (double)*e);
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// phase (b): inv(L11) of the unit lower triangle (workgroup 0) and inv(U11) (workgroup 1) of the factored diagonal block;
+// the upper one is inverted as its transpose, as in tri_prepare_kernel
+template <typename T>
+__global__ void __launch_bounds__(kBlock) getrf_inv_kernel(const T *__restrict__ W, int64_t ldw, int64_t n, int64_t j0,
+                                                           double *__restrict__ dl, double *__restrict__ du, const int *info) {
+  __shared__ double sL[NB2], sX[NB2];
+  if (*info != 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int upper = blockIdx.x;
+  const int jb = (int)(n - j0 < NB ? n - j0 : NB);
+  for (int c = q; c < NB; c += 4) {
+    double x = lane == c ? 1.0 : 0.0;
+    if (lane < jb) {
+      if (upper && lane >= c) x = (double)W[(j0 + c) + (j0 + lane) * ldw];
+      if (!upper && lane > c) x = (double)W[(j0 + lane) + (j0 + c) * ldw];
+    }
+    sL[c * NB + lane] = x;
+  }
+  __syncthreads();
+  invert_block(sL, sX, tid, lane, q);
+  double *out = upper ? du : dl;
+  for (int c = q; c < NB; c += 4) out[upper ? lane * NB + c : c * NB + lane] = sX[c * NB + lane];
+}
+
+// phase (c): the panel's jb interchanges, in order, on every column outside the panel; one thread a column
+template <typename T>
+__global__ void __launch_bounds__(kBlock) getrf_swap_kernel(T *W, int64_t ldw, int64_t n, int64_t j0, int jb, const int *perm,
+                                                            const int *info) {
+  __shared__ int sp[NB];
+  if (*info != 0) return;
+  if (threadIdx.x < jb) sp[threadIdx.x] = perm[n + j0 + threadIdx.x];
+  __syncthreads();
+  const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (idx >= n - jb) return;
+  T *col = W + (idx < j0 ? idx : idx + jb) * ldw;
+  for (int p = 0; p < jb; ++p) {
+    const int64_t r = sp[p];
+    if (r != j0 + p) {
+      const T x = col[j0 + p];
+      col[j0 + p] = col[r];
+      col[r] = x;
+    }
+  }
+}
+
+// phase (d): U12 = inv(L11) A12 with the stored inverse, 64 columns a workgroup, the lanes down the rows
+template <typename T>
+__global__ void __launch_bounds__(kBlock) getrf_row_kernel(T *__restrict__ W, int64_t ldw, int64_t n, int64_t j0, int jb,
+                                                           const double *__restrict__ dinv, const int *info) {
+  __shared__ double sP[NB2], sD[NB2];
+  if (*info != 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int64_t c0 = j0 + jb + (int64_t)blockIdx.x * NB;
+  for (int e = tid; e < NB2; e += kBlock) sD[e] = dinv[e];
+  for (int c = q; c < NB; c += 4) sP[c * NB + lane] = (lane < jb && c0 + c < n) ? (double)W[(j0 + lane) + (c0 + c) * ldw] : 0.0;
+  __syncthreads();
+  for (int c = q; c < NB; c += 4) {
+    double acc = 0.0;
+    for (int p = 0; p < jb; ++p) {
+      const double t = fma(sD[p * NB + lane], sP[c * NB + p], acc);
+      acc = p <= lane ? t : acc;
+    }
+    if (lane < jb && c0 + c < n) W[(j0 + lane) + (c0 + c) * ldw] = (T)acc;
+  }
+}
+
+// phase (e): C -= A B, C the M x M trailing matrix, A = L21 (M x K, column-major) and B = U12 (K x M): potrf_syrk_kernel with
+// two different operands and every tile
+template <typename T>
+__global__ void __launch_bounds__(kBlock) getrf_gemm_kernel(T *__restrict__ C, const T *__restrict__ A, const T *__restrict__ B,
+                                                            int64_t ld, int M, int K, const int *info) {
+  if (*info != 0) return;
+  __shared__ T sA[SK][SLD], sB[SK][SLD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bm = blockIdx.x * NB, bn = blockIdx.y * NB;
+  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
+  using Acc = typename Mfma<T>::Acc;
+  Acc acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[a][b][r] = 0;
+  for (int k0 = 0; k0 < K; k0 += SK) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int e = tid + t * kBlock, i = e & 63, k = e >> 6, kb = e & 15, jn = e >> 4;
+      sA[k][i] = (bm + i < M && k0 + k < K) ? A[(bm + i) + (int64_t)(k0 + k) * ld] : T(0);
+      sB[kb][jn] = (bn + jn < M && k0 + kb < K) ? B[(k0 + kb) + (int64_t)(bn + jn) * ld] : T(0);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < SK; kk += 4) {
+      const int kr = kk + (lane >> 4);
+      const T a0 = sA[kr][wm + (lane & 15)], a1 = sA[kr][wm + 16 + (lane & 15)];
+      const T b0 = sB[kr][wn + (lane & 15)], b1 = sB[kr][wn + 16 + (lane & 15)];
+      acc[0][0] = Mfma<T>::run(a0, b0, acc[0][0]);
+      acc[0][1] = Mfma<T>::run(a0, b1, acc[0][1]);
+      acc[1][0] = Mfma<T>::run(a1, b0, acc[1][0]);
+      acc[1][1] = Mfma<T>::run(a1, b1, acc[1][1]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int gi = bm + wm + a * 16 + Mfma<T>::row(lane, r), gj = bn + wn + b * 16 + (lane & 15);
+        if (gi < M && gj < M) {
+          T *p = C + gi + (int64_t)gj * ld;
+          *p = *p - acc[a][b][r];
+        }
+      }
+}
+
 // ---------------------------------------------------------------------------------------------- substitution sweeps
 struct SweepArgs {
   const void *Tm;        // the triangle, column-major
@@ -302,12 +513,15 @@ struct SweepArgs {
   int gd;                // the chunk that is the next diagonal block (-1: none) ...
   const double *dinv;    // ... its stored inverse, applied transposed if dinv_t
   int dinv_t;
-  const double *dinv2;   // Cholesky turn-around: a second product with this block (transposed), or NULL
+  const double *dinv2;   // turn-around: a second product, with this block (Cholesky: the same one), transposed if dinv2_t, or NULL
+  int dinv2_t;
   int epi;               // last launch: res = alpha x + beta res — chunk gd for its own block, the further workgroups for the rest
   void *res;
   double alpha, beta;
   const double *dsc;     // opLDL: the pivots d. The turn-around block is multiplied by them between its two products, and ...
   int zscale;            // ... in the first launch of the back sweep every right-hand side block is, as it is read
+  const int *gather;     // opLU: entry i of the right-hand side is v[gather[i]] (first launch), or NULL
+  const int *scatter;    // opLU: the epilogue writes entry i of the solution to res[scatter[i]], or NULL
 };
 
 __device__ __forceinline__ double block_gemv(const double *__restrict__ D, bool trans, const double *sb, double (*spart)[NB],
@@ -342,7 +556,7 @@ __global__ void __launch_bounds__(kBlock) sweep_kernel(SweepArgs a) {
     const int64_t idx = (int64_t)(g - a.nchunks) * kBlock + tid;
     if (idx < a.n - dl) {
       const int64_t i = idx < d_lo ? idx : idx + dl;
-      store_res<T, BETA0>(res, i, a.z[i], a.alpha, a.beta);
+      store_res<T, BETA0>(res, a.scatter ? a.scatter[i] : i, a.z[i], a.alpha, a.beta);
     }
     return;
   }
@@ -381,7 +595,7 @@ __global__ void __launch_bounds__(kBlock) sweep_kernel(SweepArgs a) {
   }
   double b = 0.0;
   if (tid < cl) {
-    b = a.v ? (double)((const T *)a.v)[c_lo + tid] : a.z[c_lo + tid];
+    b = a.v ? (double)((const T *)a.v)[a.gather ? a.gather[c_lo + tid] : c_lo + tid] : a.z[c_lo + tid];
     if constexpr (LDL) {
       if (a.zscale) b *= a.dsc[c_lo + tid];
     }
@@ -401,11 +615,11 @@ __global__ void __launch_bounds__(kBlock) sweep_kernel(SweepArgs a) {
     }
     if (tid < NB) sb[tid] = x;
     __syncthreads();
-    x = block_gemv(a.dinv2, true, sb, spart, lane, q);
+    x = block_gemv(a.dinv2, a.dinv2_t != 0, sb, spart, lane, q);
   }
   if (tid < cl) {
     a.z[c_lo + tid] = x;
-    if (a.epi) store_res<T, BETA0>(res, c_lo + tid, x, a.alpha, a.beta);
+    if (a.epi) store_res<T, BETA0>(res, a.scatter ? a.scatter[c_lo + tid] : c_lo + tid, x, a.alpha, a.beta);
   }
 }
 
@@ -427,20 +641,24 @@ int32_t launch_sweep(mxlo_ctx *ctx, const SweepArgs &a) {
 // first: the right-hand side comes from v (else z holds it and its first block is already solved). turn: after the last
 // block, multiply it by its transposed inverse once more (the first block of the Cholesky back sweep). epi: fuse the
 // alpha/beta epilogue into the last launch. dsc (opLDL): the pivots; they multiply the turn-around block between its two
-// products and, in a sweep that continues (!first), every other block as the first launch reads it.
+// products and, in a sweep that continues (!first), every other block as the first launch reads it. tdinv (opLU): the
+// turn-around multiplies by the last block of THESE inverses, transposed like the sweep itself, instead. gather / scatter
+// (opLU): the permutation the first launch reads v through / the epilogue writes res through.
 template <typename T, bool LDL = false>
 int32_t sweep(mxlo_ctx *ctx, const T *Tm, int64_t ld, int64_t n, bool upper, bool trans, const double *dinv, double *z,
-              const T *v, bool first, bool turn, bool epi, T *res, double alpha, double beta, const double *dsc = nullptr) {
+              const T *v, bool first, bool turn, bool epi, T *res, double alpha, double beta, const double *dsc = nullptr,
+              const double *tdinv = nullptr, const int *gather = nullptr, const int *scatter = nullptr) {
   const int64_t nb = (n + NB - 1) / NB;
   const bool asc = upper == trans;
   SweepArgs a{};
   a.Tm = Tm; a.ld = ld; a.n = n; a.z = z; a.rowpanel = trans; a.dinv_t = trans; a.res = res; a.alpha = alpha; a.beta = beta;
-  a.dsc = dsc;
+  a.dsc = dsc; a.gather = gather; a.scatter = scatter; a.dinv2_t = tdinv ? trans : 1;
   const int64_t kfirst = asc ? 0 : nb - 1, klast = asc ? nb - 1 : 0, step = asc ? 1 : -1;
+  const double *tblock = (tdinv ? tdinv : dinv) + klast * NB2;
   if (first) {                                            // z = v, and the first block solved
     a.v = v; a.xl = 0; a.r0 = 0; a.r1 = n; a.nchunks = (int)nb; a.gd = (int)kfirst;
     a.dinv = dinv + kfirst * NB2;
-    a.dinv2 = (turn && nb == 1) ? a.dinv : nullptr;
+    a.dinv2 = (turn && nb == 1) ? tblock : nullptr;
     a.epi = epi && nb == 1;
     MXLO_TRY((launch_sweep<T, LDL>(ctx, a)));
     a.v = nullptr;
@@ -453,7 +671,7 @@ int32_t sweep(mxlo_ctx *ctx, const T *Tm, int64_t ld, int64_t n, bool upper, boo
     else { a.r0 = 0; a.r1 = k * NB; a.gd = (int)(k - 1); }
     a.nchunks = (int)((a.r1 - a.r0 + NB - 1) / NB);
     a.dinv = dinv + kn * NB2;
-    a.dinv2 = (turn && kn == klast) ? a.dinv : nullptr;
+    a.dinv2 = (turn && kn == klast) ? tblock : nullptr;
     a.epi = epi && kn == klast;
     a.zscale = LDL && !first && k == kfirst;
     MXLO_TRY((launch_sweep<T, LDL>(ctx, a)));
@@ -481,6 +699,65 @@ int32_t check_apply(mxlo_ctx *ctx, int32_t dtype, const void *res, const void *A
     MXLO_REQUIRE(!bytes_overlap(p, vb, A, ab) && !bytes_overlap(p, vb, dinv, db) && !bytes_overlap(p, vb, work, n * 8), MXLO_EINVAL,
                  "%s: res / v overlap the matrix, the block inverses or the work vector", what);
   return MXLO_OK;
+}
+
+// mxlo_lu_mul: check_apply's rules, extended to the second set of block inverses and to the permutation
+int32_t check_lu_apply(mxlo_ctx *ctx, int32_t dtype, const void *res, const void *W, int64_t ld, int64_t n, const double *dinv_l,
+                       const double *dinv_u, const int32_t *perm, const double *work, const void *v) {
+  MXLO_TRY(check_apply(ctx, dtype, res, W, ld, n, dinv_l, work, v, "mxlo_lu_mul"));
+  if (n == 0) return MXLO_OK;
+  MXLO_REQUIRE(dinv_u && perm, MXLO_EINVAL, "mxlo_lu_mul: null operand");
+  const int64_t vb = n * (dtype == MXLO_F64 ? 8 : 4), db = (n + NB - 1) / NB * NB2 * 8;
+  for (const void *p : {res, v})
+    MXLO_REQUIRE(!bytes_overlap(p, vb, dinv_u, db) && !bytes_overlap(p, vb, perm, n * 4), MXLO_EINVAL,
+                 "mxlo_lu_mul: res / v overlap the block inverses or the permutation");
+  return MXLO_OK;
+}
+
+template <typename T>
+int32_t getrf_t(mxlo_ctx *ctx, const T *M, int64_t ldm, T *W, int64_t ldw, int64_t n, double *dinv_l, double *dinv_u, int *perm,
+                int *info_dev) {
+  const int64_t nb = (n + NB - 1) / NB;
+  MXLO_HIP(hipMemsetAsync(info_dev, 0, sizeof(int), ctx->stream));
+  hipLaunchKernelGGL((getrf_copy_kernel<T>), dim3((unsigned)((n + kBlock - 1) / kBlock), (unsigned)(n < 1024 ? n : 1024)), dim3(kBlock),
+                     0, ctx->stream, W, ldw, M, ldm, n, perm);
+  MXLO_LAUNCH_CHECK();
+  for (int64_t k = 0; k < nb; ++k) {
+    const int64_t j0 = k * NB, jb = n - j0 < NB ? n - j0 : NB, j1 = j0 + jb, m = n - j1;
+    hipLaunchKernelGGL((getrf_panel_kernel<T>), dim3(1), dim3(PT), 0, ctx->stream, W, ldw, n, j0, (int)jb, perm, info_dev);
+    MXLO_LAUNCH_CHECK();
+    hipLaunchKernelGGL((getrf_inv_kernel<T>), dim3(2), dim3(kBlock), 0, ctx->stream, (const T *)W, ldw, n, j0, dinv_l + k * NB2,
+                       dinv_u + k * NB2, (const int *)info_dev);
+    MXLO_LAUNCH_CHECK();
+    if (n > jb) {
+      hipLaunchKernelGGL((getrf_swap_kernel<T>), dim3((unsigned)((n - jb + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, W, ldw,
+                         n, j0, (int)jb, (const int *)perm, (const int *)info_dev);
+      MXLO_LAUNCH_CHECK();
+    }
+    if (m <= 0) break;
+    const unsigned tiles = (unsigned)((m + NB - 1) / NB);
+    hipLaunchKernelGGL((getrf_row_kernel<T>), dim3(tiles), dim3(kBlock), 0, ctx->stream, W, ldw, n, j0, (int)jb,
+                       (const double *)(dinv_l + k * NB2), (const int *)info_dev);
+    MXLO_LAUNCH_CHECK();
+    hipLaunchKernelGGL((getrf_gemm_kernel<T>), dim3(tiles, tiles), dim3(kBlock), 0, ctx->stream, W + j1 + j1 * ldw,
+                       (const T *)(W + j1 + j0 * ldw), (const T *)(W + j0 + j1 * ldw), ldw, (int)m, (int)jb, (const int *)info_dev);
+    MXLO_LAUNCH_CHECK();
+  }
+  return MXLO_OK;
+}
+
+// A = P' L U. N: x = inv(U) inv(L) (P v) — v gathered, the unit lower sweep, the upper one. T: A' = U' L' P, x = P' inv(L') inv(U') v —
+// the U' sweep, the L' sweep, the epilogue scattered.
+template <typename T>
+int32_t lu_mul_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t n, const double *dinv_l, const double *dinv_u, const int *perm,
+                 double *work, const T *v, bool trans, double alpha, double beta) {
+  const bool one = n <= NB;
+  const double *d1 = trans ? dinv_u : dinv_l, *d2 = trans ? dinv_l : dinv_u;
+  const int *gather = trans ? nullptr : perm, *scatter = trans ? perm : nullptr;
+  MXLO_TRY(sweep<T>(ctx, W, ld, n, trans, trans, d1, work, v, true, true, one, res, alpha, beta, nullptr, d2, gather, scatter));
+  if (one) return MXLO_OK;
+  return sweep<T>(ctx, W, ld, n, !trans, trans, d2, work, (const T *)nullptr, false, false, true, res, alpha, beta, nullptr, nullptr,
+                  nullptr, scatter);
 }
 
 // LDL: the chain of mxlo_ldlt — the same launches with the LDL' diagonal step and the pivots d handed to phases (b) and (c)
@@ -637,4 +914,47 @@ MXLO_API int32_t mxlo_ldl_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const voi
   MXLO_DEVICE_GUARD(ctx);
   if (dtype == MXLO_F64) return ldl_mul_t<double>(ctx, (double *)res, (const double *)L, ld, n, dinv, d, work, (const double *)v, alpha, beta);
   return ldl_mul_t<float>(ctx, (float *)res, (const float *)L, ld, n, dinv, d, work, (const float *)v, alpha, beta);
+}
+
+MXLO_API int32_t mxlo_getrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, void *W, int64_t ldw, int64_t n, double *dinv_l,
+                            double *dinv_u, int32_t *perm, int32_t *info_dev, int32_t *info) {
+  const char *what = "mxlo_getrf";
+  MXLO_TRY(check_common(ctx, dtype, W, ldw, n, what));
+  MXLO_REQUIRE(info, MXLO_EINVAL, "%s: null info", what);
+  *info = 0;
+  if (n == 0) return MXLO_OK;
+  MXLO_REQUIRE(dinv_l && dinv_u && perm && info_dev, MXLO_EINVAL, "%s: null storage for the block inverses / the permutation / the info word", what);
+  MXLO_REQUIRE(n < (1LL << 31) - NB, MXLO_ESHAPE, "%s: n = %lld is too large", what, (long long)n);
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4, wb = ((n - 1) * ldw + n) * es, db = (n + NB - 1) / NB * NB2 * 8;
+  if (M) {
+    MXLO_REQUIRE(ldm >= (n > 1 ? n : 1), MXLO_ESHAPE, "%s: ldm = %lld < n", what, (long long)ldm);
+    const int64_t mb = ((n - 1) * ldm + n) * es;
+    MXLO_REQUIRE(!bytes_overlap(M, mb, W, wb), MXLO_EINVAL, "%s: the factor's storage overlaps M", what);
+    MXLO_REQUIRE(!bytes_overlap(M, mb, dinv_l, db) && !bytes_overlap(M, mb, dinv_u, db) && !bytes_overlap(M, mb, perm, 8 * n) &&
+                     !bytes_overlap(M, mb, info_dev, 4),
+                 MXLO_EINVAL, "%s: the block inverses, the permutation or the info word overlap M", what);
+  }
+  MXLO_REQUIRE(!bytes_overlap(perm, 8 * n, W, wb) && !bytes_overlap(perm, 8 * n, dinv_l, db) && !bytes_overlap(perm, 8 * n, dinv_u, db) &&
+                   !bytes_overlap(dinv_l, db, dinv_u, db) && !bytes_overlap(dinv_l, db, W, wb) && !bytes_overlap(dinv_u, db, W, wb),
+               MXLO_EINVAL, "%s: the factor, the block inverses and the permutation overlap", what);
+  MXLO_REQUIRE(!ctx->capturing, MXLO_ESTATE, "%s: reads its info word back, which a graph capture cannot hold", what);
+  MXLO_DEVICE_GUARD(ctx);
+  if (dtype == MXLO_F64) MXLO_TRY(getrf_t<double>(ctx, (const double *)M, ldm, (double *)W, ldw, n, dinv_l, dinv_u, perm, info_dev));
+  else MXLO_TRY(getrf_t<float>(ctx, (const float *)M, ldm, (float *)W, ldw, n, dinv_l, dinv_u, perm, info_dev));
+  MXLO_HIP(hipMemcpyAsync(info, info_dev, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MXLO_HIP(hipStreamSynchronize(ctx->stream));
+  return MXLO_OK;
+}
+
+MXLO_API int32_t mxlo_lu_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t n, const double *dinv_l,
+                             const double *dinv_u, const int32_t *perm, double *work, const void *v, int32_t op_mode, double alpha,
+                             double beta) {
+  MXLO_TRY(check_lu_apply(ctx, dtype, res, W, ldw, n, dinv_l, dinv_u, perm, work, v));
+  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "mxlo_lu_mul: op_mode %d", op_mode);
+  if (n == 0) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  const bool tr = op_mode != MXLO_OP_N;
+  if (dtype == MXLO_F64)
+    return lu_mul_t<double>(ctx, (double *)res, (const double *)W, ldw, n, dinv_l, dinv_u, perm, work, (const double *)v, tr, alpha, beta);
+  return lu_mul_t<float>(ctx, (float *)res, (const float *)W, ldw, n, dinv_l, dinv_u, perm, work, (const float *)v, tr, alpha, beta);
 }

@@ -1,10 +1,10 @@
-"""opCholesky, opLDL and triangular opInverse — src/linalg.jl:3-9 (mulFact!), :27-32 (opInverse), :44-58 (opCholesky),
+"""opCholesky, opLDL, opLU and triangular opInverse — src/linalg.jl:3-9 (mulFact!), :27-32 (opInverse), :44-58 (opCholesky),
 :60-75 with ext/LinearOperatorsLDLFactorizationsExt.jl:5-18 (opLDL of a dense matrix).
 
 The factorisation, the inverses of the diagonal blocks and the block substitution sweeps run in libmxlo.so
 (csrc/linalg.hip); this module is the host mirror: argument checks, the storage an operator owns, the closures.
-Real Float64 / Float32 only. A pivoted LU for general dense `opInverse`, a pivoted (Bunch–Kaufman) or sparse LDLᵀ are not
-provided.
+Real Float64 / Float32 only. The inverse of a general dense matrix is `opLU` (partially pivoted LU); `opInverse` itself
+stays triangular-only. A pivoted (Bunch–Kaufman) or sparse LDLᵀ are not provided.
 """
 from __future__ import annotations
 
@@ -35,6 +35,16 @@ class ZeroPivotException(Exception):
     def __init__(self, info: int):
         super().__init__(f"ZeroPivotException: factorization encountered one or more zero pivots. Consider switching "
                          f"to a pivoted factorization (first zero or non-finite pivot: {info}).")
+        self.info = int(info)
+
+
+class SingularException(Exception):
+    """LinearAlgebra.SingularException(info): the pivoted LU met a pivot that is exactly zero or not finite in column
+    `info` (1-based, counted from the start of the matrix), so U is singular."""
+
+    def __init__(self, info: int):
+        super().__init__(f"SingularException({info}): matrix is singular to working precision; the pivot of column {info} "
+                         f"is zero or not finite.")
         self.info = int(info)
 
 
@@ -163,7 +173,7 @@ def opInverse(M: torch.Tensor, symm: bool = False, herm: bool = False):
 
     Whether M is lower or upper triangular is decided here, once, on the device (strict upper / strict lower part
     exactly zero — the test dense `\\` makes; a diagonal M counts as lower). A square M that is neither raises: general
-    dense opInverse needs a pivoted LU, which this package does not have. M is ALIASED (column-major or row-major
+    dense opInverse needs a pivoted LU, which is `opLU(M)`, not this constructor. M is ALIASED (column-major or row-major
     storage; any other striding is copied once): a later in-place change of its values is seen by the next apply — the
     inverses of its 64 x 64 diagonal blocks are cached under `state_version(M)` and rebuilt (one launch) when it
     changes. The triangle kind stays what it was at construction. prod! solves with M, tprod! / ctprod! with Mᵀ.
@@ -179,8 +189,8 @@ def opInverse(M: torch.Tensor, symm: bool = False, herm: bool = False):
     _lib.call("mxlo_tri_kind", ctx.handle, code, St.data_ptr(), ld, n, kind_dev.data_ptr())
     bits = int(kind_dev.item())                         # the one read of the device word
     if bits == 3:
-        raise LinearOperatorException("opInverse: M is neither lower nor upper triangular; general dense opInverse needs a "
-                                      "pivoted LU, which this package does not have")
+        raise LinearOperatorException("opInverse: M is neither lower nor upper triangular; a general dense inverse needs a "
+                                      "pivoted LU: use opLU(M); opInverse is triangular-only")
     st_upper = bits == 1                                # of the stored matrix; bits == 0 (diagonal) counts as lower
     nblk = (n + BLOCK - 1) // BLOCK
     dinv = torch.empty(max(1, nblk) * BLOCK * BLOCK, dtype=torch.float64, device=M.device)
@@ -205,4 +215,56 @@ def opInverse(M: torch.Tensor, symm: bool = False, herm: bool = False):
     op._deps = (M,)
     op._triangle = "lower" if (bits == 0 or st_upper == tr) else "upper"   # of M itself
     op._factor = (St, dinv, work)
+    return op
+
+
+def opLU(M: torch.Tensor, symm: bool = False, herm: bool = False):
+    """opLU(M; symm=false, herm=false): the inverse of a GENERAL square dense M, what `opInverse(M)` = `M \\ v` of
+    src/linalg.jl:27-32 is for a full matrix — through P M = L U with partial pivoting, computed ONCE here, on the device,
+    into storage the operator owns (M is not modified; a later change of M is not seen).
+
+    The pivot of column j is the first row i >= j with the largest |a_ij| over the whole remaining column, found on the
+    device inside the chain of launches: no host round trip, and |L_ij| <= 1. Column-major M is read as it lies; a
+    row-major M is the column-major storage of Mᵀ, which is factored as it lies with prod! and tprod! exchanged; any other
+    striding is copied once. A pivot that is exactly zero or not finite raises `SingularException(info)` with its
+    1-based column HERE, at construction; the reference factors inside `\\` and so raises it at the first apply.
+    symm / herm are taken as given, as `opInverse` takes them.
+
+    prod!: res = α (M⁻¹ v) + β res; tprod! = ctprod!: with Mᵀ. With β == 0 res is not read; res may be v. An apply is
+    2⌈n/64⌉ − 1 launches and nothing else, so it can be captured (`capture_mul`). `op._perm` is the int32 device
+    permutation, M[op._perm[i], :] = (L U)[i, :] for the stored matrix; `op._factor[0]` holds L (unit, strictly below the
+    diagonal) and U."""
+    n = _check_matrix(M, "opLU")
+    T = M.dtype
+    St, tr = _stored_colmajor(M)                       # tr: St is the column-major storage of Mᵀ
+    ldm = max(1, St.stride(1)) if n > 1 else 1
+    ctx = get_ctx(M.device)
+    W = torch.empty((n, n), dtype=T, device=M.device).t()            # column-major, ld = n: L below the diagonal, U on and above
+    ldw = max(1, n)
+    nblk = (n + BLOCK - 1) // BLOCK
+    dinv_l = torch.empty(max(1, nblk) * BLOCK * BLOCK, dtype=torch.float64, device=M.device)
+    dinv_u = torch.empty_like(dinv_l)
+    pbuf = torch.empty(max(1, 2 * n), dtype=torch.int32, device=M.device)     # the permutation, then LAPACK's ipiv (0-based)
+    work = torch.empty(max(1, n), dtype=torch.float64, device=M.device)
+    info_dev = torch.zeros(1, dtype=torch.int32, device=M.device)
+    info = C.c_int32(0)
+    code = dtype_code(T)
+    _lib.call("mxlo_getrf", ctx.handle, code, St.data_ptr(), ldm, W.data_ptr(), ldw, n, dinv_l.data_ptr(), dinv_u.data_ptr(),
+              pbuf.data_ptr(), info_dev.data_ptr(), C.byref(info))
+    if info.value != 0:
+        raise SingularException(info.value)
+    pW, pL, pU, pP, pZ = W.data_ptr(), dinv_l.data_ptr(), dinv_u.data_ptr(), pbuf.data_ptr(), work.data_ptr()
+
+    def solve(res, v, a, b, mode):                      # mulFact!(res, lu(M), v, α, β) — src/linalg.jl:3-9
+        _check_operands(res, v, T)
+        _lib.call("mxlo_lu_mul", ctx_of(res).handle, code, res.data_ptr(), pW, ldw, n, pL, pU, pP, pZ, v.data_ptr(), mode,
+                  float(a), float(b))
+
+    fwd, bwd = (_lib.OP_T, _lib.OP_N) if tr else (_lib.OP_N, _lib.OP_T)
+    prod = columnwise(lambda res, v, a, b: solve(res, v, a, b, fwd))
+    tprod = columnwise(lambda res, u, a, b: solve(res, u, a, b, bwd))
+    op = LinearOperator(T, n, n, bool(symm), bool(herm), prod, tprod, tprod, S=Storage(T, M.device))
+    op._deps = (W,)
+    op._perm = pbuf[:n]
+    op._factor = (W, dinv_l, dinv_u, pbuf, work)        # owned storage (kept alive with the operator)
     return op

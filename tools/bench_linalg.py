@@ -1,11 +1,13 @@
 #!/usr/bin/env python
-"""opCholesky / opLDL / triangular opInverse on one MI355X: factorisation and apply times (HIP events after a warm-up), bytes
+"""opCholesky / opLDL / opLU / triangular opInverse on one MI355X: factorisation and apply times (HIP events after a warm-up), bytes
 by the model of DESIGN.md §4 (one triangular solve reads the triangle once, n (n + 1) / 2 elements; a Cholesky or LDLᵀ apply
 reads it twice, the latter 8 n bytes of pivots more), the fraction of the 8 TB/s peak, launches per apply — and next to
 them the same solve through torch.cholesky_solve / torch.linalg.solve_triangular on the same device, which is what a
 caller had to use before. The opLDL rows follow the opCholesky rows of the same n: the yardstick of opLDL is opCholesky in
 the same run (torch column: torch.linalg.ldl_factor / ldl_solve, which pivot). Each time is the median of 3 windows; the
-spread column is (max − min) / median of the three.
+spread column is (max − min) / median of the three. The opLU rows (the simple_matrix of tests/test_gpu_lu.py at the same n,
+U S V' with singular values 1 .. 2) have the opCholesky rows of the same n as their yardstick — the two applies are
+the same number of launches over the same n² elements; torch column: torch.linalg.lu_factor / lu_solve.
 
     python tools/bench_linalg.py [n ...] > profiles/linalg_solve.txt
 """
@@ -69,6 +71,15 @@ def spd(n, dtype):
     return ((M + M.t()) / 2).to(dtype).t().contiguous().t()          # column-major
 
 
+def simple_matrix(n, dtype):
+    """the matrix of tests/test_gpu_lu.py (the reference's test/test_aux.jl:3-17): U S V' with singular values 1 .. 2"""
+    gen = torch.Generator(device=dev).manual_seed(6200 + n)
+    U = torch.linalg.qr(torch.rand(n, n, dtype=torch.float64, device=dev, generator=gen))[0]
+    V = torch.linalg.qr(torch.rand(n, n, dtype=torch.float64, device=dev, generator=gen))[0]
+    s = 1 + torch.arange(n, dtype=torch.float64, device=dev) / max(n - 1, 1)
+    return ((U * s) @ V.t()).to(dtype).t().contiguous().t()
+
+
 print(f"# {torch.cuda.get_device_name(0)}; times: ms per call, median of 3 event-timed windows; GB/s by the byte model; peak {PEAK:.0f} GB/s")
 print(f"{'case':34s} {'n':>6s} {'ms':>9s} {'spread':>6s} {'GB/s':>8s} {'%peak':>6s} {'launch':>6s} | {'torch ms':>9s} {'ratio':>6s}")
 for dtype, tag in ((torch.float64, "f64"), (torch.float32, "f32")):
@@ -119,5 +130,14 @@ for dtype, tag in ((torch.float64, "f64"), (torch.float32, "f32")):
         row("opCholesky apply (graph replay)", gr.replay, reps, 2 * tri + vec, 0, lambda: torch.cholesky_solve(vt, Lt))
         gl = lo.capture_mul(res, ldl, v, 1.0, 0.0)
         row("opLDL apply (graph replay)", gl.replay, reps, 2 * tri + vec + 8 * n, 0, t_solve)
-        del op, ldl, inv, gr, gl, M, K, Lt, Lc, LD, piv
+        A = simple_matrix(n, dtype)                                                   # general, column-major, condition number 2
+        LUt, pivt = torch.linalg.lu_factor(A)
+        row("opLU(A) factorisation", lambda: lo.opLU(A), freps, 0, 0, lambda: torch.linalg.lu_factor(A))
+        lu = lo.opLU(A)
+        full = n * n * es + 4 * n + (n + 63) // 64 * 4096 * 8                         # both triangles once each, perm, the second inverses
+        row("opLU apply", lambda: lo.mul(res, lu, v, 1.0, 0.0), reps, full + vec,
+            launches(lambda: lo.mul(res, lu, v, 1.0, 0.0)), lambda: torch.linalg.lu_solve(LUt, pivt, vt))
+        row("transpose(opLU) apply", lambda: lo.mul(res, lu.T, v, 1.0, 0.0), reps, full + vec,
+            launches(lambda: lo.mul(res, lu.T, v, 1.0, 0.0)), lambda: torch.linalg.lu_solve(LUt, pivt, vt, adjoint=True))
+        del op, ldl, inv, gr, gl, M, K, Lt, Lc, LD, piv, A, LUt, pivt, lu
         torch.cuda.empty_cache()
