@@ -522,6 +522,10 @@ struct SweepArgs {
   int zscale;            // ... in the first launch of the back sweep every right-hand side block is, as it is read
   const int *gather;     // opLU: entry i of the right-hand side is v[gather[i]] (first launch), or NULL
   const int *scatter;    // opLU: the epilogue writes entry i of the solution to res[scatter[i]], or NULL
+  int tri_upper;         // the diagonal block as the triangle stores it: in its upper part (else the lower one) ...
+  int tri_unit;          // ... with an implicit unit diagonal (opLU's L); read by the refinement step of the block solve
+  int tri2_upper;        // the same for the block of the turn-around product
+  int tri2_unit;
 };
 
 __device__ __forceinline__ double block_gemv(const double *__restrict__ D, bool trans, const double *sb, double (*spart)[NB],
@@ -537,6 +541,41 @@ __device__ __forceinline__ double block_gemv(const double *__restrict__ D, bool 
   const double x = (spart[0][lane] + spart[1][lane]) + (spart[2][lane] + spart[3][lane]);
   __syncthreads();
   return x;
+}
+
+// One step of iterative refinement of a block solve, x += inv(M) (b - M x), all in f64. M = S or S' (trans) is the diagonal
+// block, S read from the triangle itself (blk, its valid part only; unit: an implicit 1 on the diagonal), inv(M) the stored
+// inverse D (applied transposed if trans). The product with an explicit inverse alone has a residual of the order of
+// eps |M| |inv(M)| |b|, which on an ill-conditioned block is far from backward stable; the inverse computed column by column
+// has a small right residual |M X - I| <= gamma |M| |X|, so one step brings the residual down to the size substitution
+// leaves, eps (|M| |x| + |b|). b is in sb, rows past cl hold b = x = 0. sx is scratch; every thread returns x of row `lane`.
+template <typename T>
+__device__ __forceinline__ double block_refine(const T *__restrict__ blk, int64_t ld, int cl, bool trans, bool upper, bool unit,
+                                               const double *__restrict__ D, double x, const double *sb, double *sx,
+                                               double (*spart)[NB], int tid, int lane, int q) {
+  if (tid < NB) sx[tid] = x;
+  __syncthreads();
+  double part = 0.0;
+  if (lane < cl) {
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      const int c = q * 16 + t;
+      if (c < cl) {
+        const int r = trans ? c : lane, s = trans ? lane : c;              // M[lane, c] = S[r, s]
+        double m = 0.0;
+        if (r == s && unit) m = 1.0;
+        else if (upper ? r <= s : r >= s) m = (double)blk[r + (int64_t)s * ld];
+        part = fma(m, sx[c], part);
+      }
+    }
+  }
+  spart[q][lane] = part;
+  __syncthreads();
+  const double res = sb[lane] - ((spart[0][lane] + spart[1][lane]) + (spart[2][lane] + spart[3][lane]));
+  __syncthreads();
+  if (tid < NB) sx[tid] = res;
+  __syncthreads();
+  return x + block_gemv(D, trans, sx, spart, lane, q);
 }
 
 template <typename T, bool BETA0>
@@ -608,7 +647,9 @@ __global__ void __launch_bounds__(kBlock) sweep_kernel(SweepArgs a) {
   __syncthreads();                                       // spart is reused below
   if (tid < NB) sb[tid] = b;
   __syncthreads();
+  const T *blk = Tm + c_lo + c_lo * a.ld;                // the diagonal block in the triangle
   double x = block_gemv(a.dinv, a.dinv_t != 0, sb, spart, lane, q);
+  x = block_refine<T>(blk, a.ld, cl, a.dinv_t != 0, a.tri_upper != 0, a.tri_unit != 0, a.dinv, x, sb, sx, spart, tid, lane, q);
   if (a.dinv2) {
     if constexpr (LDL) {
       if (tid < cl) x *= a.dsc[c_lo + tid];
@@ -616,6 +657,7 @@ __global__ void __launch_bounds__(kBlock) sweep_kernel(SweepArgs a) {
     if (tid < NB) sb[tid] = x;
     __syncthreads();
     x = block_gemv(a.dinv2, a.dinv2_t != 0, sb, spart, lane, q);
+    x = block_refine<T>(blk, a.ld, cl, a.dinv2_t != 0, a.tri2_upper != 0, a.tri2_unit != 0, a.dinv2, x, sb, sx, spart, tid, lane, q);
   }
   if (tid < cl) {
     a.z[c_lo + tid] = x;
@@ -643,16 +685,19 @@ int32_t launch_sweep(mxlo_ctx *ctx, const SweepArgs &a) {
 // alpha/beta epilogue into the last launch. dsc (opLDL): the pivots; they multiply the turn-around block between its two
 // products and, in a sweep that continues (!first), every other block as the first launch reads it. tdinv (opLU): the
 // turn-around multiplies by the last block of THESE inverses, transposed like the sweep itself, instead. gather / scatter
-// (opLU): the permutation the first launch reads v through / the epilogue writes res through.
+// (opLU): the permutation the first launch reads v through / the epilogue writes res through. unit_lower (opLU): a lower
+// triangle is L, with an implicit unit diagonal, and the turn-around block is the OTHER triangle of the same storage.
 template <typename T, bool LDL = false>
 int32_t sweep(mxlo_ctx *ctx, const T *Tm, int64_t ld, int64_t n, bool upper, bool trans, const double *dinv, double *z,
               const T *v, bool first, bool turn, bool epi, T *res, double alpha, double beta, const double *dsc = nullptr,
-              const double *tdinv = nullptr, const int *gather = nullptr, const int *scatter = nullptr) {
+              const double *tdinv = nullptr, const int *gather = nullptr, const int *scatter = nullptr, bool unit_lower = false) {
   const int64_t nb = (n + NB - 1) / NB;
   const bool asc = upper == trans;
   SweepArgs a{};
   a.Tm = Tm; a.ld = ld; a.n = n; a.z = z; a.rowpanel = trans; a.dinv_t = trans; a.res = res; a.alpha = alpha; a.beta = beta;
   a.dsc = dsc; a.gather = gather; a.scatter = scatter; a.dinv2_t = tdinv ? trans : 1;
+  const bool upper2 = tdinv ? !upper : upper;
+  a.tri_upper = upper; a.tri_unit = unit_lower && !upper; a.tri2_upper = upper2; a.tri2_unit = unit_lower && !upper2;
   const int64_t kfirst = asc ? 0 : nb - 1, klast = asc ? nb - 1 : 0, step = asc ? 1 : -1;
   const double *tblock = (tdinv ? tdinv : dinv) + klast * NB2;
   if (first) {                                            // z = v, and the first block solved
@@ -754,10 +799,10 @@ int32_t lu_mul_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t n, const
   const bool one = n <= NB;
   const double *d1 = trans ? dinv_u : dinv_l, *d2 = trans ? dinv_l : dinv_u;
   const int *gather = trans ? nullptr : perm, *scatter = trans ? perm : nullptr;
-  MXLO_TRY(sweep<T>(ctx, W, ld, n, trans, trans, d1, work, v, true, true, one, res, alpha, beta, nullptr, d2, gather, scatter));
+  MXLO_TRY(sweep<T>(ctx, W, ld, n, trans, trans, d1, work, v, true, true, one, res, alpha, beta, nullptr, d2, gather, scatter, true));
   if (one) return MXLO_OK;
   return sweep<T>(ctx, W, ld, n, !trans, trans, d2, work, (const T *)nullptr, false, false, true, res, alpha, beta, nullptr, nullptr,
-                  nullptr, scatter);
+                  nullptr, scatter, true);
 }
 
 // LDL: the chain of mxlo_ldlt — the same launches with the LDL' diagonal step and the pivots d handed to phases (b) and (c)
