@@ -855,6 +855,39 @@ int32_t mxlo_lu_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int6
                     const double *dinv_u, const int32_t *perm, double *work, const void *v, int32_t op_mode, double alpha,
                     double beta);
 
+/* Block right-hand sides — mul!(res::AbstractMatrix, op, V::AbstractMatrix, α, β) of src/operations.jl:34-36 for the four
+ * solves above (`F \ V`): res (n x k, leading dimension ldr) = alpha * (F \ V) (n x k, ldv) + beta * res, the operand
+ * convention of mxlo_gemv_block; the other arguments are those of the vector entry point of the same name. Columns have
+ * unit stride, ldr, ldv >= max(1, n). The k columns go through the vector entry point's chain of launches in groups of up
+ * to 8 (a compile-time constant, the grouping of mxlo_gemv_block): per group the launches of ONE vector apply, and every
+ * element of the factor, of the block inverses and of the diagonal blocks is loaded once and used for all columns of the
+ * group. So per group the factor is read once — n (n + 1) / 2 elements for mxlo_trisolve_mul_block, twice that for
+ * mxlo_chol_mul_block / mxlo_ldl_mul_block, n^2 for mxlo_lu_mul_block —, next to O(n k) for V, res, the work matrix and
+ * d / perm (perm[i] is read once per row). Launches: ceil(k/8) times those of the vector apply. Column j of the result
+ * equals the vector apply of column j BIT FOR BIT (per column the same operations in the same order), for every k and
+ * every position in a group. `work` holds at least n * min(k, 8) doubles (an n x 8 matrix with column stride n). A group
+ * with fewer than 8 columns reads and writes its own columns only; rows >= n of res and V are never touched; with
+ * beta == 0 res is not read. k == 0 or n == 0: MXLO_OK, nothing is launched. res == V is allowed with the same pointer
+ * AND the same leading dimension (a group's columns are read completely by its first launch and written only by its
+ * last); any other overlap of res and V, and any overlap of either with the factor, the block inverses, the
+ * permutation, d or work, is MXLO_EINVAL before anything is launched. */
+int32_t mxlo_trisolve_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *T, int64_t ld, int64_t n,
+                                int32_t upper, int32_t op_mode, const double *dinv, double *work, const void *V, int64_t ldv,
+                                int64_t k, double alpha, double beta);
+/* mxlo_chol_mul on k columns: ceil(k/8) (2 ceil(n/64) - 1) launches, the triangle read twice per group of 8. */
+int32_t mxlo_chol_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *L, int64_t ld, int64_t n,
+                            const double *dinv, double *work, const void *V, int64_t ldv, int64_t k, double alpha, double beta);
+/* mxlo_ldl_mul on k columns: the launches and bytes of mxlo_chol_mul_block and 8 n bytes of pivots per group; d[i] is
+ * read once per row where the vector apply reads it. */
+int32_t mxlo_ldl_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *L, int64_t ld, int64_t n,
+                           const double *dinv, const double *d, double *work, const void *V, int64_t ldv, int64_t k,
+                           double alpha, double beta);
+/* mxlo_lu_mul on k columns: ceil(k/8) (2 ceil(n/64) - 1) launches, W read once per group of 8 (both triangles once
+ * each); the first launch of a group gathers V[perm[i], j], the epilogue of MXLO_OP_T scatters res[perm[i], j]. */
+int32_t mxlo_lu_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t n,
+                          const double *dinv_l, const double *dinv_u, const int32_t *perm, double *work, const void *V,
+                          int64_t ldv, int64_t k, int32_t op_mode, double alpha, double beta);
+
 #ifdef __cplusplus
 }
 #endif

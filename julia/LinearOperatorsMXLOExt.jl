@@ -954,7 +954,7 @@ function opCholesky(M::MXMatrix{T}; check::Bool = false) where {T <: RealT}
   end
   L = MXMatrix{T}(MXVector{T}(undef, n * n), n, n)                  # the factor: storage the operator owns, M is only read
   dinv = MXVector{Float64}(undef, ((n + 63) ÷ 64) * 4096)
-  work = MXVector{Float64}(undef, n)
+  work = MXVector{Float64}(undef, 8 * n)                           # n x 8: the work matrix of the block sweeps
   infod = MXVector{Int32}(undef, 1)
   info = Ref{Int32}(0)
   chk(ccall((:mxlo_potrf, lib), Int32, (P, Int32, P, Int64, Int32, P, Int64, Int64, P, P, Ptr{Int32}),
@@ -987,10 +987,32 @@ function opInverse(M::MXMatrix{T}; symm = false, herm = false) where {T <: RealT
   bits == 3 && throw(LinearOperatorException("opInverse: M is neither lower nor upper triangular; general dense opInverse needs a pivoted LU, which this package does not have"))
   upper = Int32(bits == 1 ? 1 : 0)                                  # a diagonal M counts as lower
   dinv = MXVector{Float64}(undef, ((n + 63) ÷ 64) * 4096)
-  work = MXVector{Float64}(undef, n)
+  work = MXVector{Float64}(undef, 8 * n)                           # n x 8: the work matrix of the block sweeps
   solve = TriSolve{T}(M, dinv, work, upper, Int32(0))
   tsolve = TriSolve{T}(M, dinv, work, upper, Int32(1))
   LinearOperator{T, MXVector{T}}(n, n, symm, herm, solve, tsolve, tsolve)
+end
+
+
+# The matrix methods of the two solve functors, beside DenseApply's in kind: `F \ V` (src/operations.jl:34-36) through the block
+# sweeps, one chain of launches and one read of the factor per 8 columns; the work buffers above are n x 8 for them.
+(f::CholSolve{T})(res::MXMatrix{T}, V::MXMatrix{T}, α, β) where {T <: RealT} = chk(ccall((:mxlo_chol_mul_block, lib), Int32,
+    (P, Int32, P, Int64, P, Int64, Int64, P, P, P, Int64, Int64, Float64, Float64),
+    ctx(), dt(T), res.data.ptr, res.m, f.L.data.ptr, f.L.m, f.L.n, f.dinv.ptr, f.work.ptr, V.data.ptr, V.m, size(V, 2), α, β))
+function (f::TriSolve{T})(res::MXMatrix{T}, V::MXMatrix{T}, α, β) where {T <: RealT}
+  chk(ccall((:mxlo_tri_prepare, lib), Int32, (P, Int32, P, Int64, Int64, Int32, P),
+            ctx(), dt(T), f.A.data.ptr, f.A.m, f.A.n, f.upper, f.dinv.ptr))
+  chk(ccall((:mxlo_trisolve_mul_block, lib), Int32,
+            (P, Int32, P, Int64, P, Int64, Int64, Int32, Int32, P, P, P, Int64, Int64, Float64, Float64),
+            ctx(), dt(T), res.data.ptr, res.m, f.A.data.ptr, f.A.m, f.A.n, f.upper, f.mode, f.dinv.ptr, f.work.ptr, V.data.ptr, V.m,
+            size(V, 2), α, β))
+end
+# `mul!(res::MXMatrix, op, m::MXMatrix, α, β)` routes here through `op.prod!` / `tprod!` / `ctprod!`: the whole block in one call,
+# as for DenseApply (the generic apply_columns would run the vector method, and the whole chain, once per column)
+function apply_columns(f::Union{CholSolve{T}, TriSolve{T}}, res::MXMatrix{T}, m::MXMatrix{T}, α, β) where {T <: RealT}
+  size(res, 2) == size(m, 2) || throw(LinearOperatorException("shape mismatch"))
+  f(res, m, α, β)
+  res
 end
 
 end # module

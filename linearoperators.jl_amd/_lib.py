@@ -187,6 +187,11 @@ _PROTOS = {
     "mxlo_ldl_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _dbl, _dbl],
     "mxlo_getrf": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i32)],
     "mxlo_lu_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl],
+    # the block forms: the vector prototype with ldr after res, and ldv, k after V
+    "mxlo_trisolve_mul_block": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _dbl, _dbl],
+    "mxlo_chol_mul_block": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _dbl, _dbl],
+    "mxlo_ldl_mul_block": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _dbl, _dbl],
+    "mxlo_lu_mul_block": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _dbl, _dbl],
 }
 
 

@@ -7,6 +7,7 @@
 // workgroup whose 64 entries are the next diagonal block goes on and solves it, x_{k+1} = inv(T_{k+1,k+1}) b_{k+1}, with the
 // stored inverse. The right-hand side lives in one f64 work vector z whose blocks turn into the solution one by one, so the
 // data a launch reads (x_k) and writes (entries not solved yet) never meet. All sums run in a fixed order in f64.
+// Matrix operands (the mxlo_*_mul_block entry points) run the same chain with up to KB = 8 right-hand sides per launch.
 #include "common.h"
 
 using namespace mxlo;
@@ -526,6 +527,8 @@ struct SweepArgs {
   int tri_unit;          // ... with an implicit unit diagonal (opLU's L); read by the refinement step of the block solve
   int tri2_upper;        // the same for the block of the turn-around product
   int tri2_unit;
+  int kb;                // block form (sweep_block_kernel): the group's right-hand sides, 1 .. KB; 0: the vector kernel. v and res
+  int64_t ldr, ldv;      // are then n x kb matrices with these leading dimensions, z is n x kb with column stride n
 };
 
 __device__ __forceinline__ double block_gemv(const double *__restrict__ D, bool trans, const double *sb, double (*spart)[NB],
@@ -665,6 +668,226 @@ __global__ void __launch_bounds__(kBlock) sweep_kernel(SweepArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------- block right-hand sides
+// The same chain of launches carrying a group of kb <= KB right-hand sides: every element of the panel, of the stored
+// inverse and of the diagonal block is loaded ONCE and used for all of them. Per right-hand side the operations and their
+// order are those of sweep_kernel (the 16-term fma chains per quarter, (p0 + p1) + (p2 + p3), wave_sum's tree, the
+// refinement), so column j of a block apply is the single-vector apply of that column bit for bit. The loops over j are
+// unrolled over KB with a wave-uniform guard j < kb, so x[], part[] stay in registers.
+constexpr int KB = 8;                // right-hand sides per pass, the grouping of mxlo_gemv_block; 24 KiB of LDS
+
+// block_gemv for kb vectors: x[j] = row `lane` of D sb[j] (D' if trans)
+__device__ __forceinline__ void block_gemv_k(const double *__restrict__ D, bool trans, const double (*sb)[NB],
+                                             double (*spart)[4][NB], int kb, int lane, int q, double *x) {
+  double part[KB];
+#pragma unroll
+  for (int j = 0; j < KB; ++j) part[j] = 0.0;
+#pragma unroll
+  for (int t = 0; t < 16; ++t) {
+    const int c = q * 16 + t;
+    const double d = trans ? D[lane * NB + c] : D[c * NB + lane];
+#pragma unroll
+    for (int j = 0; j < KB; ++j)
+      if (j < kb) part[j] = fma(d, sb[j][c], part[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < KB; ++j)
+    if (j < kb) spart[j][q][lane] = part[j];
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < KB; ++j)
+    if (j < kb) x[j] = (spart[j][0][lane] + spart[j][1][lane]) + (spart[j][2][lane] + spart[j][3][lane]);
+  __syncthreads();
+}
+
+// block_refine for kb vectors: x[j] += inv(M) (sb[j] - M x[j]); each element of the diagonal block is read once
+template <typename T>
+__device__ __forceinline__ void block_refine_k(const T *__restrict__ blk, int64_t ld, int cl, bool trans, bool upper, bool unit,
+                                               const double *__restrict__ D, double *x, const double (*sb)[NB], double (*sx)[NB],
+                                               double (*spart)[4][NB], int kb, int lane, int q) {
+#pragma unroll
+  for (int j = 0; j < KB; ++j)
+    if (j < kb && (j & 3) == q) sx[j][lane] = x[j];      // every wave holds x of all 64 rows: wave q stores columns j = q, q + 4
+  __syncthreads();
+  double part[KB];
+#pragma unroll
+  for (int j = 0; j < KB; ++j) part[j] = 0.0;
+  if (lane < cl) {
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      const int c = q * 16 + t;
+      if (c < cl) {
+        const int r = trans ? c : lane, s = trans ? lane : c;              // M[lane, c] = S[r, s]
+        double m = 0.0;
+        if (r == s && unit) m = 1.0;
+        else if (upper ? r <= s : r >= s) m = (double)blk[r + (int64_t)s * ld];
+#pragma unroll
+        for (int j = 0; j < KB; ++j)
+          if (j < kb) part[j] = fma(m, sx[j][c], part[j]);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < KB; ++j)
+    if (j < kb) spart[j][q][lane] = part[j];
+  __syncthreads();
+  double r[KB];
+#pragma unroll
+  for (int j = 0; j < KB; ++j)
+    if (j < kb) r[j] = sb[j][lane] - ((spart[j][0][lane] + spart[j][1][lane]) + (spart[j][2][lane] + spart[j][3][lane]));
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < KB; ++j)
+    if (j < kb && (j & 3) == q) sx[j][lane] = r[j];
+  __syncthreads();
+  double y[KB];
+  block_gemv_k(D, trans, sx, spart, kb, lane, q, y);
+#pragma unroll
+  for (int j = 0; j < KB; ++j)
+    if (j < kb) x[j] = x[j] + y[j];
+}
+
+template <typename T, bool BETA0, bool LDL>
+__global__ void __launch_bounds__(kBlock) sweep_block_kernel(SweepArgs a) {
+  __shared__ double sx[KB][NB], sb[KB][NB], spart[KB][4][NB];
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int g = blockIdx.x, kb = a.kb;
+  T *res = (T *)a.res;
+  if (g >= a.nchunks) {                                  // epilogue of everything outside the block chunk gd solves
+    const int64_t d_lo = a.r0 + (int64_t)a.gd * NB;
+    const int64_t dl = a.r1 - d_lo < NB ? a.r1 - d_lo : NB;
+    const int64_t idx = (int64_t)(g - a.nchunks) * kBlock + tid;
+    if (idx < a.n - dl) {
+      const int64_t i = idx < d_lo ? idx : idx + dl;
+      const int64_t o = a.scatter ? a.scatter[i] : i;
+#pragma unroll
+      for (int j = 0; j < KB; ++j)
+        if (j < kb) store_res<T, BETA0>(res + (int64_t)j * a.ldr, o, a.z[i + (int64_t)j * a.n], a.alpha, a.beta);
+    }
+    return;
+  }
+  const T *Tm = (const T *)a.Tm;
+  const int64_t c_lo = a.r0 + (int64_t)g * NB;
+  const int cl = (int)(a.r1 - c_lo < NB ? a.r1 - c_lo : NB);
+  if (a.xl > 0) {
+    for (int e = tid; e < kb * NB; e += kBlock) {
+      const int j = e >> 6, r = e & 63;
+      sx[j][r] = r < a.xl ? a.z[a.xs + r + (int64_t)j * a.n] : 0.0;
+    }
+    __syncthreads();
+    if (!a.rowpanel) {                                   // the thread's panel element stays in a register for the kb columns
+      double acc[KB];
+#pragma unroll
+      for (int j = 0; j < KB; ++j) acc[j] = 0.0;
+      if (lane < cl) {
+        const T *row = Tm + (c_lo + lane) + a.xs * a.ld;
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+          const int c = q * 16 + t;
+          if (c < a.xl) {
+            const double tv = ld_stream(row + (int64_t)c * a.ld);
+#pragma unroll
+            for (int j = 0; j < KB; ++j)
+              if (j < kb) acc[j] = fma(tv, sx[j][c], acc[j]);
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < KB; ++j)
+        if (j < kb) spart[j][q][lane] = acc[j];
+    } else {                                             // the 16 loaded elements are kept; one wave_sum per (panel column, rhs)
+      double tv[16];
+#pragma unroll
+      for (int t = 0; t < 16; ++t) {
+        const int c = q * 16 + t;
+        tv[t] = (c < cl && lane < a.xl) ? ld_stream(Tm + (a.xs + lane) + (c_lo + c) * a.ld) : 0.0;
+      }
+#pragma unroll
+      for (int j = 0; j < KB; ++j) {
+        if (j < kb) {
+          const double xi = sx[j][lane];
+#pragma unroll
+          for (int t = 0; t < 16; ++t) {
+            const int c = q * 16 + t;
+            const double s = wave_sum((c < cl && lane < a.xl) ? tv[t] * xi : 0.0);
+            if (lane == 0) spart[j][0][c] = s;
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  double b[KB];
+#pragma unroll
+  for (int j = 0; j < KB; ++j) b[j] = 0.0;
+  if (tid < cl) {
+    const int64_t i = c_lo + tid;
+    const int64_t src = (a.v && a.gather) ? a.gather[i] : i;     // perm[i] is read once per row
+    double dsc = 1.0;
+    if constexpr (LDL) {
+      if (a.zscale) dsc = a.dsc[i];
+    }
+#pragma unroll
+    for (int j = 0; j < KB; ++j) {
+      if (j < kb) {
+        double bj = a.v ? (double)((const T *)a.v)[src + (int64_t)j * a.ldv] : a.z[i + (int64_t)j * a.n];
+        if constexpr (LDL) {
+          if (a.zscale) bj *= dsc;
+        }
+        if (a.xl > 0)
+          bj -= a.rowpanel ? spart[j][0][tid] : (spart[j][0][tid] + spart[j][1][tid]) + (spart[j][2][tid] + spart[j][3][tid]);
+        b[j] = bj;
+      }
+    }
+  }
+  if (g != a.gd) {
+    if (tid < cl) {
+#pragma unroll
+      for (int j = 0; j < KB; ++j)
+        if (j < kb) a.z[c_lo + tid + (int64_t)j * a.n] = b[j];
+    }
+    return;
+  }
+  __syncthreads();                                       // spart is reused below
+  if (tid < NB) {
+#pragma unroll
+    for (int j = 0; j < KB; ++j)
+      if (j < kb) sb[j][tid] = b[j];
+  }
+  __syncthreads();
+  const T *blk = Tm + c_lo + c_lo * a.ld;                // the diagonal block in the triangle
+  double x[KB];
+  block_gemv_k(a.dinv, a.dinv_t != 0, sb, spart, kb, lane, q, x);
+  block_refine_k<T>(blk, a.ld, cl, a.dinv_t != 0, a.tri_upper != 0, a.tri_unit != 0, a.dinv, x, sb, sx, spart, kb, lane, q);
+  if (a.dinv2) {
+    if constexpr (LDL) {
+      if (lane < cl) {
+        const double dsc = a.dsc[c_lo + lane];
+#pragma unroll
+        for (int j = 0; j < KB; ++j)
+          if (j < kb) x[j] *= dsc;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < KB; ++j)
+      if (j < kb && (j & 3) == q) sb[j][lane] = x[j];
+    __syncthreads();
+    block_gemv_k(a.dinv2, a.dinv2_t != 0, sb, spart, kb, lane, q, x);
+    block_refine_k<T>(blk, a.ld, cl, a.dinv2_t != 0, a.tri2_upper != 0, a.tri2_unit != 0, a.dinv2, x, sb, sx, spart, kb, lane, q);
+  }
+  if (tid < cl) {
+    const int64_t i = c_lo + tid;
+    const int64_t o = (a.epi && a.scatter) ? a.scatter[i] : i;
+#pragma unroll
+    for (int j = 0; j < KB; ++j) {
+      if (j < kb) {
+        a.z[i + (int64_t)j * a.n] = x[j];
+        if (a.epi) store_res<T, BETA0>(res + (int64_t)j * a.ldr, o, x[j], a.alpha, a.beta);
+      }
+    }
+  }
+}
+
 template <typename T, bool LDL>
 int32_t launch_sweep(mxlo_ctx *ctx, const SweepArgs &a) {
   int64_t grid = a.nchunks;
@@ -673,7 +896,10 @@ int32_t launch_sweep(mxlo_ctx *ctx, const SweepArgs &a) {
     grid += (a.n - dl + kBlock - 1) / kBlock;
   }
   MXLO_REQUIRE(grid < (1LL << 31), MXLO_ESHAPE, "triangular solve: n = %lld is too large", (long long)a.n);
-  if (a.beta == 0.0) hipLaunchKernelGGL((sweep_kernel<T, true, LDL>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
+  if (a.kb > 0) {                                        // a group of right-hand sides: the same grid, the block kernel
+    if (a.beta == 0.0) hipLaunchKernelGGL((sweep_block_kernel<T, true, LDL>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((sweep_block_kernel<T, false, LDL>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
+  } else if (a.beta == 0.0) hipLaunchKernelGGL((sweep_kernel<T, true, LDL>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
   else hipLaunchKernelGGL((sweep_kernel<T, false, LDL>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
   MXLO_LAUNCH_CHECK();
   return MXLO_OK;
@@ -687,15 +913,23 @@ int32_t launch_sweep(mxlo_ctx *ctx, const SweepArgs &a) {
 // turn-around multiplies by the last block of THESE inverses, transposed like the sweep itself, instead. gather / scatter
 // (opLU): the permutation the first launch reads v through / the epilogue writes res through. unit_lower (opLU): a lower
 // triangle is L, with an implicit unit diagonal, and the turn-around block is the OTHER triangle of the same storage.
+// grp.kb > 0: the block form — v and res are n x kb (ldv, ldr), z is n x kb with column stride n; the same launches.
+struct Group {
+  int kb = 0;
+  int64_t ldr = 0, ldv = 0;
+};
+
 template <typename T, bool LDL = false>
 int32_t sweep(mxlo_ctx *ctx, const T *Tm, int64_t ld, int64_t n, bool upper, bool trans, const double *dinv, double *z,
               const T *v, bool first, bool turn, bool epi, T *res, double alpha, double beta, const double *dsc = nullptr,
-              const double *tdinv = nullptr, const int *gather = nullptr, const int *scatter = nullptr, bool unit_lower = false) {
+              const double *tdinv = nullptr, const int *gather = nullptr, const int *scatter = nullptr, bool unit_lower = false,
+              Group grp = {}) {
   const int64_t nb = (n + NB - 1) / NB;
   const bool asc = upper == trans;
   SweepArgs a{};
   a.Tm = Tm; a.ld = ld; a.n = n; a.z = z; a.rowpanel = trans; a.dinv_t = trans; a.res = res; a.alpha = alpha; a.beta = beta;
   a.dsc = dsc; a.gather = gather; a.scatter = scatter; a.dinv2_t = tdinv ? trans : 1;
+  a.kb = grp.kb; a.ldr = grp.ldr; a.ldv = grp.ldv;
   const bool upper2 = tdinv ? !upper : upper;
   a.tri_upper = upper; a.tri_unit = unit_lower && !upper; a.tri2_upper = upper2; a.tri2_unit = unit_lower && !upper2;
   const int64_t kfirst = asc ? 0 : nb - 1, klast = asc ? nb - 1 : 0, step = asc ? 1 : -1;
@@ -732,31 +966,51 @@ int32_t check_common(mxlo_ctx *ctx, int32_t dtype, const void *A, int64_t ld, in
   return MXLO_OK;
 }
 
-int32_t check_apply(mxlo_ctx *ctx, int32_t dtype, const void *res, const void *A, int64_t ld, int64_t n, const double *dinv,
-                    const double *work, const void *v, const char *what) {
+// res and v of an apply: n x k, columns of unit stride, with leading dimensions ldr, ldv. A vector entry point passes
+// vectors(res, v, n): one column in a leading dimension of max(1, n).
+struct Operands {
+  const void *res, *v;
+  int64_t k, ldr, ldv;
+  int64_t res_bytes(int64_t n, int64_t es) const { return ((k - 1) * ldr + n) * es; }
+  int64_t v_bytes(int64_t n, int64_t es) const { return ((k - 1) * ldv + n) * es; }
+};
+inline Operands vectors(const void *res, const void *v, int64_t n) { return {res, v, 1, n > 1 ? n : 1, n > 1 ? n : 1}; }
+
+// work is n * min(k, KB) doubles. res may be v, as the same matrix: the same pointer and the same leading dimension.
+int32_t check_apply(mxlo_ctx *ctx, int32_t dtype, const Operands &o, const void *A, int64_t ld, int64_t n, const double *dinv,
+                    const double *work, const char *what) {
   MXLO_TRY(check_common(ctx, dtype, A, ld, n, what));
-  if (n == 0) return MXLO_OK;
-  MXLO_REQUIRE(res && v && dinv && work, MXLO_EINVAL, "%s: null operand", what);
-  const int64_t es = dtype == MXLO_F64 ? 8 : 4, vb = n * es, ab = ((n - 1) * ld + n) * es, db = (n + NB - 1) / NB * NB2 * 8;
-  MXLO_REQUIRE(res == v || !bytes_overlap(res, vb, v, vb), MXLO_EINVAL,
+  const int64_t ldmin = n > 1 ? n : 1;
+  MXLO_REQUIRE(o.k >= 0 && o.ldr >= ldmin && o.ldv >= ldmin, MXLO_ESHAPE, "%s: k = %lld, ldr = %lld, ldv = %lld for n = %lld", what,
+               (long long)o.k, (long long)o.ldr, (long long)o.ldv, (long long)n);
+  if (n == 0 || o.k == 0) return MXLO_OK;
+  MXLO_REQUIRE(o.res && o.v && dinv && work, MXLO_EINVAL, "%s: null operand", what);
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4, rb = o.res_bytes(n, es), vb = o.v_bytes(n, es);
+  const int64_t ab = ((n - 1) * ld + n) * es, db = (n + NB - 1) / NB * NB2 * 8, wb = n * (o.k < KB ? o.k : KB) * 8;
+  MXLO_REQUIRE((o.res == o.v && o.ldr == o.ldv) || !bytes_overlap(o.res, rb, o.v, vb), MXLO_EINVAL,
                "%s: res overlaps v without being v (only mul!(x, op, x) is defined)", what);
-  for (const void *p : {res, v})
-    MXLO_REQUIRE(!bytes_overlap(p, vb, A, ab) && !bytes_overlap(p, vb, dinv, db) && !bytes_overlap(p, vb, work, n * 8), MXLO_EINVAL,
+  for (const auto &[p, pb] : {std::pair<const void *, int64_t>{o.res, rb}, {o.v, vb}})
+    MXLO_REQUIRE(!bytes_overlap(p, pb, A, ab) && !bytes_overlap(p, pb, dinv, db) && !bytes_overlap(p, pb, work, wb), MXLO_EINVAL,
                  "%s: res / v overlap the matrix, the block inverses or the work vector", what);
   return MXLO_OK;
 }
 
-// mxlo_lu_mul: check_apply's rules, extended to the second set of block inverses and to the permutation
-int32_t check_lu_apply(mxlo_ctx *ctx, int32_t dtype, const void *res, const void *W, int64_t ld, int64_t n, const double *dinv_l,
-                       const double *dinv_u, const int32_t *perm, const double *work, const void *v) {
-  MXLO_TRY(check_apply(ctx, dtype, res, W, ld, n, dinv_l, work, v, "mxlo_lu_mul"));
-  if (n == 0) return MXLO_OK;
-  MXLO_REQUIRE(dinv_u && perm, MXLO_EINVAL, "mxlo_lu_mul: null operand");
-  const int64_t vb = n * (dtype == MXLO_F64 ? 8 : 4), db = (n + NB - 1) / NB * NB2 * 8;
-  for (const void *p : {res, v})
-    MXLO_REQUIRE(!bytes_overlap(p, vb, dinv_u, db) && !bytes_overlap(p, vb, perm, n * 4), MXLO_EINVAL,
-                 "mxlo_lu_mul: res / v overlap the block inverses or the permutation");
+// the further operand `x` of an apply (xb bytes: the pivots, the second block inverses, the permutation) against res and v
+int32_t check_extra(int32_t dtype, const Operands &o, int64_t n, const void *x, int64_t xb, const char *what, const char *name) {
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4;
+  MXLO_REQUIRE(!bytes_overlap(o.res, o.res_bytes(n, es), x, xb) && !bytes_overlap(o.v, o.v_bytes(n, es), x, xb), MXLO_EINVAL,
+               "%s: res / v overlap %s", what, name);
   return MXLO_OK;
+}
+
+// mxlo_lu_mul: check_apply's rules, extended to the second set of block inverses and to the permutation
+int32_t check_lu_apply(mxlo_ctx *ctx, int32_t dtype, const Operands &o, const void *W, int64_t ld, int64_t n, const double *dinv_l,
+                       const double *dinv_u, const int32_t *perm, const double *work, const char *what) {
+  MXLO_TRY(check_apply(ctx, dtype, o, W, ld, n, dinv_l, work, what));
+  if (n == 0 || o.k == 0) return MXLO_OK;
+  MXLO_REQUIRE(dinv_u && perm, MXLO_EINVAL, "%s: null operand", what);
+  MXLO_TRY(check_extra(dtype, o, n, dinv_u, (n + NB - 1) / NB * NB2 * 8, what, "the block inverses"));
+  return check_extra(dtype, o, n, perm, n * 4, what, "the permutation");
 }
 
 template <typename T>
@@ -795,14 +1049,14 @@ int32_t getrf_t(mxlo_ctx *ctx, const T *M, int64_t ldm, T *W, int64_t ldw, int64
 // the U' sweep, the L' sweep, the epilogue scattered.
 template <typename T>
 int32_t lu_mul_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t n, const double *dinv_l, const double *dinv_u, const int *perm,
-                 double *work, const T *v, bool trans, double alpha, double beta) {
+                 double *work, const T *v, bool trans, double alpha, double beta, Group grp = {}) {
   const bool one = n <= NB;
   const double *d1 = trans ? dinv_u : dinv_l, *d2 = trans ? dinv_l : dinv_u;
   const int *gather = trans ? nullptr : perm, *scatter = trans ? perm : nullptr;
-  MXLO_TRY(sweep<T>(ctx, W, ld, n, trans, trans, d1, work, v, true, true, one, res, alpha, beta, nullptr, d2, gather, scatter, true));
+  MXLO_TRY(sweep<T>(ctx, W, ld, n, trans, trans, d1, work, v, true, true, one, res, alpha, beta, nullptr, d2, gather, scatter, true, grp));
   if (one) return MXLO_OK;
   return sweep<T>(ctx, W, ld, n, !trans, trans, d2, work, (const T *)nullptr, false, false, true, res, alpha, beta, nullptr, nullptr,
-                  nullptr, scatter, true);
+                  nullptr, scatter, true, grp);
 }
 
 // LDL: the chain of mxlo_ldlt — the same launches with the LDL' diagonal step and the pivots d handed to phases (b) and (c)
@@ -906,7 +1160,7 @@ MXLO_API int32_t mxlo_ldlt(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t 
 
 MXLO_API int32_t mxlo_trisolve_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *Tm, int64_t ld, int64_t n, int32_t upper,
                                    int32_t op_mode, const double *dinv, double *work, const void *v, double alpha, double beta) {
-  MXLO_TRY(check_apply(ctx, dtype, res, Tm, ld, n, dinv, work, v, "mxlo_trisolve_mul"));
+  MXLO_TRY(check_apply(ctx, dtype, vectors(res, v, n), Tm, ld, n, dinv, work, "mxlo_trisolve_mul"));
   MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "mxlo_trisolve_mul: op_mode %d", op_mode);
   if (n == 0) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
@@ -919,17 +1173,19 @@ MXLO_API int32_t mxlo_trisolve_mul(mxlo_ctx *ctx, int32_t dtype, void *res, cons
 namespace {
 template <typename T>
 int32_t chol_mul_t(mxlo_ctx *ctx, T *res, const T *L, int64_t ld, int64_t n, const double *dinv, double *work, const T *v, double alpha,
-                   double beta) {
+                   double beta, Group grp = {}) {
   const bool one = n <= NB;                              // a single block: both products and the epilogue in one launch
-  MXLO_TRY(sweep<T>(ctx, L, ld, n, false, false, dinv, work, v, true, true, one, res, alpha, beta));
+  MXLO_TRY(sweep<T>(ctx, L, ld, n, false, false, dinv, work, v, true, true, one, res, alpha, beta, nullptr, nullptr, nullptr, nullptr,
+                    false, grp));
   if (one) return MXLO_OK;
-  return sweep<T>(ctx, L, ld, n, false, true, dinv, work, (const T *)nullptr, false, false, true, res, alpha, beta);
+  return sweep<T>(ctx, L, ld, n, false, true, dinv, work, (const T *)nullptr, false, false, true, res, alpha, beta, nullptr, nullptr,
+                  nullptr, nullptr, false, grp);
 }
 }  // namespace
 
 MXLO_API int32_t mxlo_chol_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *L, int64_t ld, int64_t n, const double *dinv,
                                double *work, const void *v, double alpha, double beta) {
-  MXLO_TRY(check_apply(ctx, dtype, res, L, ld, n, dinv, work, v, "mxlo_chol_mul"));
+  MXLO_TRY(check_apply(ctx, dtype, vectors(res, v, n), L, ld, n, dinv, work, "mxlo_chol_mul"));
   if (n == 0) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
   if (dtype == MXLO_F64) return chol_mul_t<double>(ctx, (double *)res, (const double *)L, ld, n, dinv, work, (const double *)v, alpha, beta);
@@ -940,17 +1196,19 @@ namespace {
 // x = Lt^{-T} (d .* (Lt^{-1} v)) with Lt = L D: the two sweeps of chol_mul_t; where the pivots come in is said at sweep()
 template <typename T>
 int32_t ldl_mul_t(mxlo_ctx *ctx, T *res, const T *L, int64_t ld, int64_t n, const double *dinv, const double *d, double *work,
-                  const T *v, double alpha, double beta) {
+                  const T *v, double alpha, double beta, Group grp = {}) {
   const bool one = n <= NB;
-  MXLO_TRY((sweep<T, true>(ctx, L, ld, n, false, false, dinv, work, v, true, true, one, res, alpha, beta, d)));
+  MXLO_TRY((sweep<T, true>(ctx, L, ld, n, false, false, dinv, work, v, true, true, one, res, alpha, beta, d, nullptr, nullptr, nullptr,
+                           false, grp)));
   if (one) return MXLO_OK;
-  return sweep<T, true>(ctx, L, ld, n, false, true, dinv, work, (const T *)nullptr, false, false, true, res, alpha, beta, d);
+  return sweep<T, true>(ctx, L, ld, n, false, true, dinv, work, (const T *)nullptr, false, false, true, res, alpha, beta, d, nullptr,
+                        nullptr, nullptr, false, grp);
 }
 }  // namespace
 
 MXLO_API int32_t mxlo_ldl_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *L, int64_t ld, int64_t n, const double *dinv,
                               const double *d, double *work, const void *v, double alpha, double beta) {
-  MXLO_TRY(check_apply(ctx, dtype, res, L, ld, n, dinv, work, v, "mxlo_ldl_mul"));
+  MXLO_TRY(check_apply(ctx, dtype, vectors(res, v, n), L, ld, n, dinv, work, "mxlo_ldl_mul"));
   if (n == 0) return MXLO_OK;
   MXLO_REQUIRE(d, MXLO_EINVAL, "mxlo_ldl_mul: null pivots");
   const int64_t vb = n * (dtype == MXLO_F64 ? 8 : 4);
@@ -994,7 +1252,7 @@ MXLO_API int32_t mxlo_getrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t
 MXLO_API int32_t mxlo_lu_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t n, const double *dinv_l,
                              const double *dinv_u, const int32_t *perm, double *work, const void *v, int32_t op_mode, double alpha,
                              double beta) {
-  MXLO_TRY(check_lu_apply(ctx, dtype, res, W, ldw, n, dinv_l, dinv_u, perm, work, v));
+  MXLO_TRY(check_lu_apply(ctx, dtype, vectors(res, v, n), W, ldw, n, dinv_l, dinv_u, perm, work, "mxlo_lu_mul"));
   MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "mxlo_lu_mul: op_mode %d", op_mode);
   if (n == 0) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
@@ -1002,4 +1260,90 @@ MXLO_API int32_t mxlo_lu_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void
   if (dtype == MXLO_F64)
     return lu_mul_t<double>(ctx, (double *)res, (const double *)W, ldw, n, dinv_l, dinv_u, perm, work, (const double *)v, tr, alpha, beta);
   return lu_mul_t<float>(ctx, (float *)res, (const float *)W, ldw, n, dinv_l, dinv_u, perm, work, (const float *)v, tr, alpha, beta);
+}
+
+// ---------------------------------------------------------------------------------------------- block entry points
+// The n x k operands go through the chain in groups of KB columns: one chain of launches and one read of the factor per
+// group. A group's columns of V are read completely by its first launch and its columns of res written only by its last,
+// and the groups are different columns, so res may be V (the same pointer and leading dimension).
+namespace {
+template <typename T, typename F>
+int32_t for_groups(T *res, int64_t ldr, const T *V, int64_t ldv, int64_t k, F &&apply) {
+  for (int64_t j0 = 0; j0 < k; j0 += KB) {
+    Group grp;
+    grp.kb = (int)(k - j0 < KB ? k - j0 : KB);
+    grp.ldr = ldr;
+    grp.ldv = ldv;
+    MXLO_TRY(apply(res + j0 * ldr, V + j0 * ldv, grp));
+  }
+  return MXLO_OK;
+}
+}  // namespace
+
+MXLO_API int32_t mxlo_trisolve_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *Tm, int64_t ld, int64_t n,
+                                         int32_t upper, int32_t op_mode, const double *dinv, double *work, const void *V, int64_t ldv,
+                                         int64_t k, double alpha, double beta) {
+  MXLO_TRY(check_apply(ctx, dtype, Operands{res, V, k, ldr, ldv}, Tm, ld, n, dinv, work, "mxlo_trisolve_mul_block"));
+  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "mxlo_trisolve_mul_block: op_mode %d", op_mode);
+  if (n == 0 || k == 0) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  const bool tr = op_mode != MXLO_OP_N, up = upper != 0;
+  if (dtype == MXLO_F64)
+    return for_groups((double *)res, ldr, (const double *)V, ldv, k, [&](double *r, const double *v, Group grp) {
+      return sweep<double>(ctx, (const double *)Tm, ld, n, up, tr, dinv, work, v, true, false, true, r, alpha, beta, nullptr, nullptr,
+                           nullptr, nullptr, false, grp);
+    });
+  return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
+    return sweep<float>(ctx, (const float *)Tm, ld, n, up, tr, dinv, work, v, true, false, true, r, alpha, beta, nullptr, nullptr, nullptr,
+                        nullptr, false, grp);
+  });
+}
+
+MXLO_API int32_t mxlo_chol_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *L, int64_t ld, int64_t n,
+                                     const double *dinv, double *work, const void *V, int64_t ldv, int64_t k, double alpha,
+                                     double beta) {
+  MXLO_TRY(check_apply(ctx, dtype, Operands{res, V, k, ldr, ldv}, L, ld, n, dinv, work, "mxlo_chol_mul_block"));
+  if (n == 0 || k == 0) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  if (dtype == MXLO_F64)
+    return for_groups((double *)res, ldr, (const double *)V, ldv, k, [&](double *r, const double *v, Group grp) {
+      return chol_mul_t<double>(ctx, r, (const double *)L, ld, n, dinv, work, v, alpha, beta, grp);
+    });
+  return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
+    return chol_mul_t<float>(ctx, r, (const float *)L, ld, n, dinv, work, v, alpha, beta, grp);
+  });
+}
+
+MXLO_API int32_t mxlo_ldl_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *L, int64_t ld, int64_t n,
+                                    const double *dinv, const double *d, double *work, const void *V, int64_t ldv, int64_t k,
+                                    double alpha, double beta) {
+  MXLO_TRY(check_apply(ctx, dtype, Operands{res, V, k, ldr, ldv}, L, ld, n, dinv, work, "mxlo_ldl_mul_block"));
+  if (n == 0 || k == 0) return MXLO_OK;
+  MXLO_REQUIRE(d, MXLO_EINVAL, "mxlo_ldl_mul_block: null pivots");
+  MXLO_TRY(check_extra(dtype, Operands{res, V, k, ldr, ldv}, n, d, n * 8, "mxlo_ldl_mul_block", "the pivots"));
+  MXLO_DEVICE_GUARD(ctx);
+  if (dtype == MXLO_F64)
+    return for_groups((double *)res, ldr, (const double *)V, ldv, k, [&](double *r, const double *v, Group grp) {
+      return ldl_mul_t<double>(ctx, r, (const double *)L, ld, n, dinv, d, work, v, alpha, beta, grp);
+    });
+  return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
+    return ldl_mul_t<float>(ctx, r, (const float *)L, ld, n, dinv, d, work, v, alpha, beta, grp);
+  });
+}
+
+MXLO_API int32_t mxlo_lu_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t n,
+                                   const double *dinv_l, const double *dinv_u, const int32_t *perm, double *work, const void *V,
+                                   int64_t ldv, int64_t k, int32_t op_mode, double alpha, double beta) {
+  MXLO_TRY(check_lu_apply(ctx, dtype, Operands{res, V, k, ldr, ldv}, W, ldw, n, dinv_l, dinv_u, perm, work, "mxlo_lu_mul_block"));
+  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "mxlo_lu_mul_block: op_mode %d", op_mode);
+  if (n == 0 || k == 0) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  const bool tr = op_mode != MXLO_OP_N;
+  if (dtype == MXLO_F64)
+    return for_groups((double *)res, ldr, (const double *)V, ldv, k, [&](double *r, const double *v, Group grp) {
+      return lu_mul_t<double>(ctx, r, (const double *)W, ldw, n, dinv_l, dinv_u, perm, work, v, tr, alpha, beta, grp);
+    });
+  return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
+    return lu_mul_t<float>(ctx, r, (const float *)W, ldw, n, dinv_l, dinv_u, perm, work, v, tr, alpha, beta, grp);
+  });
 }

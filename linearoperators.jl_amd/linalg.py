@@ -3,7 +3,9 @@
 
 The factorisation, the inverses of the diagonal blocks and the block substitution sweeps run in libmxlo.so
 (csrc/linalg.hip); this module is the host mirror: argument checks, the storage an operator owns, the closures.
-Real Float64 / Float32 only. The inverse of a general dense matrix is `opLU` (partially pivoted LU); `opInverse` itself
+Real Float64 / Float32 only. `mul!` on an n x k matrix (`F \\ V`, src/operations.jl:34-36) takes the block form of the sweeps for k > 1
+(`mxlo_*_mul_block`): the chain of launches of one vector apply and one read of the factor per GROUP = 8 columns, each column
+bit-identical to its vector apply. The inverse of a general dense matrix is `opLU` (partially pivoted LU); `opInverse` itself
 stays triangular-only. A pivoted (Bunch–Kaufman) or sparse LDLᵀ are not provided.
 """
 from __future__ import annotations
@@ -18,6 +20,7 @@ from .leaves import _stored_colmajor
 from .operators import LinearOperator, LinearOperatorException, columnwise, state_version
 
 BLOCK = 64            # block column width of csrc/linalg.hip (NB)
+GROUP = 8             # right-hand sides per pass of the block sweeps (KB): the work matrix is n x GROUP doubles
 
 
 class PosDefException(Exception):
@@ -70,6 +73,30 @@ def _check_operands(res, v, T):
         raise ValueError("mul!: res and v must have unit stride")
 
 
+def _check_block_operands(res, m, T, n):
+    """The n x k operands of a block apply, as `_apply_closure_to_matrix` hands them over (column-major, any leading
+    dimension): returns (ldr, ldv, k)."""
+    if res.dtype is not T or m.dtype is not T:
+        raise TypeError(f"mul!: {res.dtype} / {m.dtype} operands next to a {T} factorisation")
+    if res.dim() != 2 or m.dim() != 2 or m.shape[0] != n or res.shape[0] != n or res.shape[1] != m.shape[1]:
+        raise LinearOperatorException("shape mismatch")
+    k = m.shape[1]
+    lds = []
+    for X in (res, m):
+        if n > 1 and X.stride(0) != 1:
+            raise ValueError("mul!: the columns of res and V must have unit stride")
+        ldx = X.stride(1) if k > 1 else max(1, n)
+        if ldx < max(1, n):
+            raise ValueError("mul!: res and V must be column-major (leading dimension >= n)")
+        lds.append(ldx)
+    return lds[0], lds[1], k
+
+
+def _work(n, device):
+    """The f64 work matrix of the sweeps, n x GROUP with column stride n: allocated once, at construction."""
+    return torch.empty(max(1, n) * GROUP, dtype=torch.float64, device=device)
+
+
 def opCholesky(M: torch.Tensor, check: bool = False):
     """opCholesky(M; check=false) — src/linalg.jl:44-58: the inverse of a symmetric positive definite matrix through its
     Cholesky factorisation, computed ONCE here, on the device, into storage the operator owns (M is not modified).
@@ -78,7 +105,8 @@ def opCholesky(M: torch.Tensor, check: bool = False):
     M are read in place, anything else is copied to column-major first. A pivot that is not positive and finite raises
     `PosDefException(info)` with the 1-based order of the failing leading minor. `check=True` runs `check_hermitian`
     and `check_positive_definite` first. prod! = tprod! = ctprod!: res = α (M⁻¹ v) + β res; with β == 0 res is not
-    read; res may be v. An apply allocates nothing and never synchronises, so it can be captured (`capture_mul`)."""
+    read; res may be v. An apply allocates nothing and never synchronises, so it can be captured (`capture_mul`). Matrix
+    operands (n x k, k > 1) go through `mxlo_chol_mul_block`: 8 columns per chain of launches; res may be V."""
     n = _check_matrix(M, "opCholesky")
     T = M.dtype
     if check:
@@ -94,7 +122,7 @@ def opCholesky(M: torch.Tensor, check: bool = False):
     ldw = max(1, n)
     nblk = (n + BLOCK - 1) // BLOCK
     dinv = torch.empty(max(1, nblk) * BLOCK * BLOCK, dtype=torch.float64, device=M.device)
-    work = torch.empty(max(1, n), dtype=torch.float64, device=M.device)
+    work = _work(n, M.device)
     info_dev = torch.zeros(1, dtype=torch.int32, device=M.device)
     info = C.c_int32(0)
     code = dtype_code(T)
@@ -108,7 +136,13 @@ def opCholesky(M: torch.Tensor, check: bool = False):
         _check_operands(res, v, T)
         _lib.call("mxlo_chol_mul", ctx_of(res).handle, code, res.data_ptr(), pW, ldw, n, pD, pZ, v.data_ptr(), float(a), float(b))
 
-    columnwise(prod)                                    # `F \ V` takes matrices: column by column
+    def block(res, m, a, b):                            # `F \ V`: one chain of launches and one read of L per 8 columns
+        ldr, ldv, k = _check_block_operands(res, m, T, n)
+        _lib.call("mxlo_chol_mul_block", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, n, pD, pZ, m.data_ptr(), ldv, k,
+                  float(a), float(b))
+
+    columnwise(prod)                                    # `F \ V` takes matrices: k == 1 column by column, else the block form
+    prod._matrix = block
     op = LinearOperator(T, n, n, True, True, prod, prod, prod, S=Storage(T, M.device))      # isreal(M), hermitian = true
     op._deps = (W,)
     op._factor = (W, dinv, work)                        # owned storage (kept alive with the operator)
@@ -146,7 +180,7 @@ def opLDL(M: torch.Tensor, check: bool = False):
     nblk = (n + BLOCK - 1) // BLOCK
     dinv = torch.empty(max(1, nblk) * BLOCK * BLOCK, dtype=torch.float64, device=M.device)
     d = torch.empty(n, dtype=torch.float64, device=M.device)
-    work = torch.empty(max(1, n), dtype=torch.float64, device=M.device)
+    work = _work(n, M.device)
     info_dev = torch.zeros(1, dtype=torch.int32, device=M.device)
     info = C.c_int32(0)
     code = dtype_code(T)
@@ -160,7 +194,13 @@ def opLDL(M: torch.Tensor, check: bool = False):
         _check_operands(res, v, T)
         _lib.call("mxlo_ldl_mul", ctx_of(res).handle, code, res.data_ptr(), pW, ldw, n, pD, pd, pZ, v.data_ptr(), float(a), float(b))
 
+    def block(res, m, a, b):
+        ldr, ldv, k = _check_block_operands(res, m, T, n)
+        _lib.call("mxlo_ldl_mul_block", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, n, pD, pd, pZ, m.data_ptr(), ldv, k,
+                  float(a), float(b))
+
     columnwise(prod)
+    prod._matrix = block
     op = LinearOperator(T, n, n, True, True, prod, prod, prod, S=Storage(T, M.device))      # isreal(M), hermitian = true
     op._deps = (W,)
     op._d = d                                           # the pivots; their signs are the inertia of M
@@ -194,23 +234,35 @@ def opInverse(M: torch.Tensor, symm: bool = False, herm: bool = False):
     st_upper = bits == 1                                # of the stored matrix; bits == 0 (diagonal) counts as lower
     nblk = (n + BLOCK - 1) // BLOCK
     dinv = torch.empty(max(1, nblk) * BLOCK * BLOCK, dtype=torch.float64, device=M.device)
-    work = torch.empty(max(1, n), dtype=torch.float64, device=M.device)
+    work = _work(n, M.device)
     pT, pD, pZ = St.data_ptr(), dinv.data_ptr(), work.data_ptr()
     cache = {"version": None}
 
-    def solve(res, v, a, b, mode):
-        _check_operands(res, v, T)
-        h = ctx_of(res).handle
+    def prepare(h):
         ver = state_version(St)
         if ver != cache["version"]:                     # M changed in place: its diagonal blocks' inverses are stale
             _lib.call("mxlo_tri_prepare", h, code, pT, ld, n, 1 if st_upper else 0, pD)
             cache["version"] = ver
+
+    def solve(res, v, a, b, mode):
+        _check_operands(res, v, T)
+        h = ctx_of(res).handle
+        prepare(h)
         _lib.call("mxlo_trisolve_mul", h, code, res.data_ptr(), pT, ld, n, 1 if st_upper else 0, mode, pD, pZ, v.data_ptr(),
                   float(a), float(b))
+
+    def block(res, m, a, b, mode):
+        ldr, ldv, k = _check_block_operands(res, m, T, n)
+        h = ctx_of(res).handle
+        prepare(h)
+        _lib.call("mxlo_trisolve_mul_block", h, code, res.data_ptr(), ldr, pT, ld, n, 1 if st_upper else 0, mode, pD, pZ,
+                  m.data_ptr(), ldv, k, float(a), float(b))
 
     fwd, bwd = (_lib.OP_T, _lib.OP_N) if tr else (_lib.OP_N, _lib.OP_T)
     prod = columnwise(lambda res, v, a, b: solve(res, v, a, b, fwd))       # mulFact!(res, M, v, α, β)
     tprod = columnwise(lambda res, u, a, b: solve(res, u, a, b, bwd))      # mulFact!(res, transpose(M), u, α, β)
+    prod._matrix = lambda res, m, a, b: block(res, m, a, b, fwd)
+    tprod._matrix = lambda res, m, a, b: block(res, m, a, b, bwd)
     op = LinearOperator(T, n, n, bool(symm), bool(herm), prod, tprod, tprod, S=Storage(T, M.device))
     op._deps = (M,)
     op._triangle = "lower" if (bits == 0 or st_upper == tr) else "upper"   # of M itself
@@ -245,7 +297,7 @@ def opLU(M: torch.Tensor, symm: bool = False, herm: bool = False):
     dinv_l = torch.empty(max(1, nblk) * BLOCK * BLOCK, dtype=torch.float64, device=M.device)
     dinv_u = torch.empty_like(dinv_l)
     pbuf = torch.empty(max(1, 2 * n), dtype=torch.int32, device=M.device)     # the permutation, then LAPACK's ipiv (0-based)
-    work = torch.empty(max(1, n), dtype=torch.float64, device=M.device)
+    work = _work(n, M.device)
     info_dev = torch.zeros(1, dtype=torch.int32, device=M.device)
     info = C.c_int32(0)
     code = dtype_code(T)
@@ -260,9 +312,16 @@ def opLU(M: torch.Tensor, symm: bool = False, herm: bool = False):
         _lib.call("mxlo_lu_mul", ctx_of(res).handle, code, res.data_ptr(), pW, ldw, n, pL, pU, pP, pZ, v.data_ptr(), mode,
                   float(a), float(b))
 
+    def block(res, m, a, b, mode):
+        ldr, ldv, k = _check_block_operands(res, m, T, n)
+        _lib.call("mxlo_lu_mul_block", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, n, pL, pU, pP, pZ, m.data_ptr(), ldv,
+                  k, mode, float(a), float(b))
+
     fwd, bwd = (_lib.OP_T, _lib.OP_N) if tr else (_lib.OP_N, _lib.OP_T)
     prod = columnwise(lambda res, v, a, b: solve(res, v, a, b, fwd))
     tprod = columnwise(lambda res, u, a, b: solve(res, u, a, b, bwd))
+    prod._matrix = lambda res, m, a, b: block(res, m, a, b, fwd)
+    tprod._matrix = lambda res, m, a, b: block(res, m, a, b, bwd)
     op = LinearOperator(T, n, n, bool(symm), bool(herm), prod, tprod, tprod, S=Storage(T, M.device))
     op._deps = (W,)
     op._perm = pbuf[:n]

@@ -10,6 +10,16 @@ U S V' with singular values 1 .. 2) have the opCholesky rows of the same n as th
 the same number of launches over the same n² elements; torch column: torch.linalg.lu_factor / lu_solve.
 
     python tools/bench_linalg.py [n ...] > profiles/linalg_solve.txt
+
+--block: the block right-hand sides instead, `mul!(R, op, V)` with V n x k for k = 2, 8, 32 at n = 2048, 8192, 16384 — time,
+spread, launches and the model GB/s of FACTOR traffic (per group of 8 columns the factor is read once: n (n + 1) / 2 elements
+for a triangular solve, twice that for Cholesky / LDLᵀ, n² for LU) — and beside each the loop of k single-vector applies in the
+same run (the vector kernels, which the block form leaves untouched) and the vendor solve on the n x k block
+(torch.cholesky_solve / torch.linalg.lu_solve / torch.linalg.solve_triangular; opLDL has the Cholesky one as yardstick). The
+k = 1 rows are the single-vector applies. --mul-only prints the `mul!(R, op, V)` column alone (the protocol for a baseline
+run of the same shapes on another commit).
+
+    python tools/bench_linalg.py --block [n ...] > profiles/linalg_block.txt
 """
 import ctypes as C
 import os
@@ -27,7 +37,9 @@ dev = torch.device("cuda", 0)
 ctx = get_ctx(dev)
 tm = Timer(ctx)
 PEAK = 8000.0          # GB/s
-NS = [int(a) for a in sys.argv[1:]] or [1024, 4096, 16384]
+BLOCK = "--block" in sys.argv
+MUL_ONLY = "--mul-only" in sys.argv
+NS = [int(a) for a in sys.argv[1:] if not a.startswith("--")] or ([2048, 8192, 16384] if BLOCK else [1024, 4096, 16384])
 
 
 def timeit(fn, reps):
@@ -79,6 +91,67 @@ def simple_matrix(n, dtype):
     s = 1 + torch.arange(n, dtype=torch.float64, device=dev) / max(n - 1, 1)
     return ((U * s) @ V.t()).to(dtype).t().contiguous().t()
 
+
+def colmajor(n, k, dtype, seed):
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    return torch.randn(k, n, dtype=dtype, device=dev, generator=gen).t()
+
+
+def block_legs():
+    """mul!(R, op, V) on n x k blocks: see the module docstring"""
+    print(f"# {torch.cuda.get_device_name(0)}; block right-hand sides; ms per call, median of 3 event-timed windows, spread = (max - min) / median")
+    print(f"# GB/s: factor bytes of the model (one read per group of 8 columns) / time of mul!(R, op, V)")
+    print(f"{'case':30s} {'n':>6s} {'k':>3s} {'mul ms':>9s} {'spread':>6s} {'launch':>6s} {'GB/s':>8s} | {'k applies':>9s} {'spread':>6s} {'launch':>6s} {'ratio':>6s} | "
+          f"{'torch ms':>9s} {'ratio':>6s}", flush=True)
+    for dtype, tag in ((torch.float64, "f64"), (torch.float32, "f32")):
+        es = 8 if dtype is torch.float64 else 4
+        for n in NS:
+            M = spd(n, dtype)
+            tri, full = n * (n + 1) // 2 * es, n * n * es
+            reps = 20 if n <= 2048 else (5 if n <= 8192 else 3)
+            Lt = torch.linalg.cholesky(M)
+            Lc = Lt.t().contiguous().t()
+            A = simple_matrix(n, dtype)
+            LUt, pivt = torch.linalg.lu_factor(A)
+            inv = lo.opInverse(Lc)
+            lu = lo.opLU(A)
+            cases = [("opCholesky", lo.opCholesky(M), 2 * tri, lambda V: torch.cholesky_solve(V, Lt)),
+                     ("opLDL", lo.opLDL(quasi_definite(M)), 2 * tri, None),
+                     ("opInverse(L)", inv, tri, lambda V: torch.linalg.solve_triangular(Lc, V, upper=False)),
+                     ("transpose(opInverse(L))", inv.T, tri, lambda V: torch.linalg.solve_triangular(Lc.t(), V, upper=True)),
+                     ("opLU", lu, full, lambda V: torch.linalg.lu_solve(LUt, pivt, V)),
+                     ("transpose(opLU)", lu.T, full, lambda V: torch.linalg.lu_solve(LUt, pivt, V, adjoint=True))]
+            for name, op, fbytes, tfn in cases:
+                for k in (1, 2, 8, 32):
+                    V, R = colmajor(n, k, dtype, 10 * n + k), colmajor(n, k, dtype, 1)
+                    if k == 1:
+                        v, r = V[:, 0], R[:, 0]
+                        mul = lambda: lo.mul(r, op, v, 1.0, 0.0)
+                    else:
+                        mul = lambda: lo.mul(R, op, V, 1.0, 0.0)
+
+                    def loop():
+                        for j in range(k):
+                            lo.mul(R[:, j], op, V[:, j], 1.0, 0.0)
+
+                    ms = timeit(mul, reps)
+                    sp, nl = timeit.spread, launches(mul)
+                    gbs = -(-k // 8) * fbytes / ms / 1e6
+                    line = f"{name + ' ' + tag:30s} {n:6d} {k:3d} {ms:9.4f} {100 * sp:5.1f}% {nl:6d} {gbs:8.1f} | "
+                    if MUL_ONLY:
+                        print(line, flush=True)
+                        continue
+                    lms = timeit(loop, reps) if k > 1 else ms
+                    lsp, ll = timeit.spread, launches(loop)
+                    tms = timeit(lambda: tfn(V), reps) if tfn else float("nan")
+                    print(line + f"{lms:9.4f} {100 * lsp:5.1f}% {ll:6d} {lms / ms:6.2f} | {tms:9.4f} {tms / ms:6.2f}", flush=True)
+            del cases, inv, lu, M, Lt, Lc, A, LUt, pivt
+            torch.cuda.empty_cache()
+
+
+if BLOCK:
+    block_legs()
+    sys.exit(0)
 
 print(f"# {torch.cuda.get_device_name(0)}; times: ms per call, median of 3 event-timed windows; GB/s by the byte model; peak {PEAK:.0f} GB/s")
 print(f"{'case':34s} {'n':>6s} {'ms':>9s} {'spread':>6s} {'GB/s':>8s} {'%peak':>6s} {'launch':>6s} | {'torch ms':>9s} {'ratio':>6s}")
