@@ -888,6 +888,60 @@ int32_t mxlo_lu_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, 
                           const double *dinv_l, const double *dinv_u, const int32_t *perm, double *work, const void *V,
                           int64_t ldv, int64_t k, int32_t op_mode, double alpha, double beta);
 
+/* Iterative refinement of the three factorisation solves — the `#TODO: use iterative refinement.` of src/linalg.jl:57 and
+ * ext/LinearOperatorsLDLFactorizationsExt.jl:17. With steps = r every column computes x_0 = F \ v, then r times
+ * x += F \ (v - op(M) x), and res = alpha x_r + beta res. The residual and every x are DOUBLES for both element types; the
+ * one rounding to the element type is in the epilogue. r is fixed: no convergence test, nothing read back, no allocation,
+ * no synchronisation — capturable. The matrix the residual reads is a snapshot taken at construction (below).
+ * Launches per group of up to 8 columns: (r + 1) (2 ceil(n/64) - 1) + r, the r being one residual launch each
+ * (n <= 64: 2 r + 1). Bytes per group: (r + 1) times those of the plain block apply plus r n^2 elements for the residuals
+ * (the symmetric one reads each element of the strict upper triangle twice, once as a row and once as a column) and
+ * O(n k) doubles for x, the residual and V. Column j equals the k = 1 call of column j bit for bit; steps == 0 gives the
+ * bits of the plain block entry point. `work` is 2 n 8 doubles: the sweeps' matrix (n x 8, column stride n), then x.
+ * res == V is allowed (same pointer and leading dimension): V is read by the first launch and by every residual launch of
+ * its group, res is written by the group's last launch only; with beta == 0 res is not read. Any other overlap of res and V,
+ * and any overlap of either with W (which holds the symmetric snapshot), dg, A2, the block inverses, d, perm or either
+ * work matrix is MXLO_EINVAL before anything is launched; so is steps outside 0 .. 8.
+ *
+ * mxlo_sym_snapshot — one launch, issued AFTER mxlo_potrf / mxlo_ldlt: W[r, c] = M[r, c] for r < c and dg[i] = M[i, i]
+ * (element type of M), from the UPPER triangle of M, the one the factorisation read (m_rowmajor as there). The strict
+ * upper triangle of W is read and written by no factorisation or sweep kernel, so the snapshot needs no second n x n
+ * buffer. n (n + 1) / 2 elements read and written. M, W and dg may not overlap. */
+int32_t mxlo_sym_snapshot(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_rowmajor, void *W, int64_t ldw,
+                          int64_t n, void *dg);
+/* One launch, issued after mxlo_getrf: A2[i, c] = M[perm[i], c], the stored matrix with its rows in pivot order (n x n,
+ * lda; n^2 elements read and written). With A2 = P A the residual of a step comes out in the order the sweeps work in
+ * (N: P v - A2 x, T: v - A2' y with y = P x), so no vector is permuted in place between launches. */
+int32_t mxlo_lu_snapshot(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, const int32_t *perm, void *A2, int64_t lda,
+                         int64_t n);
+/* R[:, j] = V[:, j] - (dg .* X[:, j] + U X[:, j] + U' X[:, j]), j < k <= 8: U the STRICT upper triangle of a column-major
+ * matrix (ld; nothing on or below the diagonal is read), dg and V (ldv) of the element type, X and R n x k doubles with
+ * column stride n. ONE launch of ceil(n/64) workgroups, one per band of 64 rows: the band reads U[band, columns right of
+ * it] with unit stride and U[rows above it, band] turned through LDS, so every element is read by two workgroups, n^2
+ * elements in all, and no partial sums cross workgroups. f64 sums in a fixed order, no atomics: two calls give the same
+ * bits, and column j those of its k == 1 call. Rows >= n of the padded operands are never read. R may overlap no operand. */
+int32_t mxlo_sym_residual(mxlo_ctx *ctx, int32_t dtype, double *R, const void *U, int64_t ld, const void *dg, int64_t n,
+                          const void *V, int64_t ldv, const double *X, int64_t k);
+/* R = V - A X (MXLO_OP_N) or V - A' X (MXLO_OP_T; MXLO_OP_C == T) for a general column-major A (n x n, ld): the same
+ * kernel, operands, launch (one), bytes (n^2 elements) and determinism as mxlo_sym_residual. */
+int32_t mxlo_gen_residual(mxlo_ctx *ctx, int32_t dtype, double *R, const void *A, int64_t ld, int64_t n, const void *V,
+                          int64_t ldv, const double *X, int64_t k, int32_t op_mode);
+/* mxlo_chol_mul_block with `steps` refinement steps; W from mxlo_potrf and mxlo_sym_snapshot, dg from the latter. */
+int32_t mxlo_chol_mul_refine(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t n,
+                             const double *dinv, const void *dg, double *work, const void *V, int64_t ldv, int64_t k,
+                             int32_t steps, double alpha, double beta);
+/* mxlo_ldl_mul_block with `steps` refinement steps; W from mxlo_ldlt and mxlo_sym_snapshot. One step brings an unpivoted
+ * factorisation with element growth back to a backward error of the order of n eps, as long as growth * cond * eps < 1. */
+int32_t mxlo_ldl_mul_refine(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t n,
+                            const double *dinv, const double *d, const void *dg, double *work, const void *V, int64_t ldv,
+                            int64_t k, int32_t steps, double alpha, double beta);
+/* mxlo_lu_mul_block with `steps` refinement steps; A2 (n x n, lda) from mxlo_lu_snapshot. N: the first launch gathers
+ * V[perm[i], j] as before, every residual gathers it again; T: only the last epilogue scatters. */
+int32_t mxlo_lu_mul_refine(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t n,
+                           const double *dinv_l, const double *dinv_u, const int32_t *perm, const void *A2, int64_t lda,
+                           double *work, const void *V, int64_t ldv, int64_t k, int32_t steps, int32_t op_mode, double alpha,
+                           double beta);
+
 #ifdef __cplusplus
 }
 #endif

@@ -945,8 +945,8 @@ end
 (f::CholSolve{T})(res::MXVector{T}, v::MXVector{T}, α, β) where {T <: RealT} = chk(ccall((:mxlo_chol_mul, lib), Int32,
     (P, Int32, P, P, Int64, Int64, P, P, P, Float64, Float64),
     ctx(), dt(T), res.ptr, f.L.data.ptr, f.L.m, f.L.n, f.dinv.ptr, f.work.ptr, v.ptr, α, β))
-function opCholesky(M::MXMatrix{T}; check::Bool = false) where {T <: RealT}
-  m, n = size(M)
+function opCholesky(M::MXMatrix{T}; check::Bool = false, refine::Int = 0) where {T <: RealT}
+  check_refine(refine); m, n = size(M)                               # refine: CholRefine, at the end of this file
   m == n || throw(LinearOperatorException("shape mismatch"))
   if check
     check_hermitian(M) || throw(LinearOperatorException("matrix is not Hermitian"))
@@ -954,13 +954,13 @@ function opCholesky(M::MXMatrix{T}; check::Bool = false) where {T <: RealT}
   end
   L = MXMatrix{T}(MXVector{T}(undef, n * n), n, n)                  # the factor: storage the operator owns, M is only read
   dinv = MXVector{Float64}(undef, ((n + 63) ÷ 64) * 4096)
-  work = MXVector{Float64}(undef, 8 * n)                           # n x 8: the work matrix of the block sweeps
+  work = MXVector{Float64}(undef, (refine > 0 ? 16 : 8) * n)        # n x 8: the work matrix of the block sweeps; refine: and x
   infod = MXVector{Int32}(undef, 1)
   info = Ref{Int32}(0)
   chk(ccall((:mxlo_potrf, lib), Int32, (P, Int32, P, Int64, Int32, P, Int64, Int64, P, P, Ptr{Int32}),
             ctx(), dt(T), M.data.ptr, m, Int32(0), L.data.ptr, n, n, dinv.ptr, infod.ptr, info))
   info[] == 0 || throw(LinearAlgebra.PosDefException(info[]))       # test/test_linop.jl:498
-  f = CholSolve{T}(L, dinv, work)
+  f = refine > 0 ? chol_refine(M, L, dinv, work, refine) : CholSolve{T}(L, dinv, work)
   LinearOperator{T, MXVector{T}}(n, n, true, true, f, f, f)
 end
 
@@ -1010,6 +1010,40 @@ end
 # `mul!(res::MXMatrix, op, m::MXMatrix, α, β)` routes here through `op.prod!` / `tprod!` / `ctprod!`: the whole block in one call,
 # as for DenseApply (the generic apply_columns would run the vector method, and the whole chain, once per column)
 function apply_columns(f::Union{CholSolve{T}, TriSolve{T}}, res::MXMatrix{T}, m::MXMatrix{T}, α, β) where {T <: RealT}
+  size(res, 2) == size(m, 2) || throw(LinearOperatorException("shape mismatch"))
+  f(res, m, α, β)
+  res
+end
+
+
+# refine = r > 0 of opCholesky (the `#TODO: use iterative refinement.` of src/linalg.jl:57): every apply is x = F \ v, then r times
+# x += F \ (v - M x) with the residual and x in Float64 (mxlo_chol_mul_refine, k = 1 for a vector). The strict upper triangle of M
+# is kept in the strict upper triangle of L, which the factor does not use, and its diagonal in dg (mxlo_sym_snapshot, after the
+# factorisation); work is then 2 n x 8. opLDL and opLU have no glue here, so the keyword exists on opCholesky only.
+const MAX_REFINE = 8
+check_refine(r::Int) = 0 <= r <= MAX_REFINE || throw(ArgumentError("refine = $r outside 0 .. MAX_REFINE = $MAX_REFINE"))
+struct CholRefine{T}
+  L::MXMatrix{T}
+  dinv::MXVector{Float64}
+  work::MXVector{Float64}
+  dg::MXVector{T}
+  steps::Int32
+end
+function chol_refine(M::MXMatrix{T}, L::MXMatrix{T}, dinv, work, refine) where {T <: RealT}
+  n = L.n
+  dg = MXVector{T}(undef, max(1, n))
+  chk(ccall((:mxlo_sym_snapshot, lib), Int32, (P, Int32, P, Int64, Int32, P, Int64, Int64, P),
+            ctx(), dt(T), M.data.ptr, M.m, Int32(0), L.data.ptr, n, n, dg.ptr))
+  CholRefine{T}(L, dinv, work, dg, Int32(refine))
+end
+chol_refine_mul(f::CholRefine{T}, res, ldr, V, ldv, k, α, β) where {T <: RealT} = chk(ccall((:mxlo_chol_mul_refine, lib), Int32,
+    (P, Int32, P, Int64, P, Int64, Int64, P, P, P, P, Int64, Int64, Int32, Float64, Float64),
+    ctx(), dt(T), res, ldr, f.L.data.ptr, f.L.m, f.L.n, f.dinv.ptr, f.dg.ptr, f.work.ptr, V, ldv, k, f.steps, α, β))
+(f::CholRefine{T})(res::MXVector{T}, v::MXVector{T}, α, β) where {T <: RealT} =
+  chol_refine_mul(f, res.ptr, max(1, f.L.n), v.ptr, max(1, f.L.n), 1, α, β)
+(f::CholRefine{T})(res::MXMatrix{T}, V::MXMatrix{T}, α, β) where {T <: RealT} =
+  chol_refine_mul(f, res.data.ptr, res.m, V.data.ptr, V.m, size(V, 2), α, β)
+function apply_columns(f::CholRefine{T}, res::MXMatrix{T}, m::MXMatrix{T}, α, β) where {T <: RealT}
   size(res, 2) == size(m, 2) || throw(LinearOperatorException("shape mismatch"))
   f(res, m, α, β)
   res

@@ -192,6 +192,15 @@ _PROTOS = {
     "mxlo_chol_mul_block": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _dbl, _dbl],
     "mxlo_ldl_mul_block": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _dbl, _dbl],
     "mxlo_lu_mul_block": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _dbl, _dbl],
+    # iterative refinement: the snapshot helpers, the residuals on their own, the block forms with the snapshot and `steps`
+    "mxlo_sym_snapshot": [_vp, _i32, _vp, _i64, _i32, _vp, _i64, _i64, _vp],
+    "mxlo_lu_snapshot": [_vp, _i32, _vp, _i64, _vp, _vp, _i64, _i64],
+    "mxlo_sym_residual": [_vp, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64],
+    "mxlo_gen_residual": [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i32],
+    "mxlo_chol_mul_refine": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _dbl, _dbl],
+    "mxlo_ldl_mul_refine": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _dbl, _dbl],
+    "mxlo_lu_mul_refine": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32,
+                           _dbl, _dbl],
 }
 
 

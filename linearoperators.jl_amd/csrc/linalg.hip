@@ -529,7 +529,10 @@ struct SweepArgs {
   int tri2_unit;
   int kb;                // block form (sweep_block_kernel): the group's right-hand sides, 1 .. KB; 0: the vector kernel. v and res
   int64_t ldr, ldv;      // are then n x kb matrices with these leading dimensions, z is n x kb with column stride n
-};
+  double *xacc;          // refined apply (block form only), else NULL: the iterate x, n x kb f64 with column stride n, in the sweep's own
+  int xmode;             // order. The launch with epi does — 1: x = z   2: x += z   3: res = alpha (x + z) + beta res (scattered); res is
+};                       // touched by 3 only
+
 
 __device__ __forceinline__ double block_gemv(const double *__restrict__ D, bool trans, const double *sb, double (*spart)[NB],
                                              int lane, int q) {
@@ -747,7 +750,20 @@ __device__ __forceinline__ void block_refine_k(const T *__restrict__ blk, int64_
     if (j < kb) x[j] = x[j] + y[j];
 }
 
-template <typename T, bool BETA0, bool LDL>
+// The end of a sweep for entry i of column j, whose solution is x: the alpha/beta epilogue, or (RF, a.xacc) the step of a refined
+// apply. RF is a template parameter so that the kernel of the plain block apply stays the code it was.
+template <typename T, bool BETA0, bool RF>
+__device__ __forceinline__ void finish_entry(const SweepArgs &a, T *res, int64_t o, int64_t i, int j, double x) {
+  if constexpr (RF) {
+    double *xp = a.xacc + i + (int64_t)j * a.n;
+    if (a.xmode == 1) { *xp = x; return; }
+    x = *xp + x;
+    if (a.xmode == 2) { *xp = x; return; }
+  }
+  store_res<T, BETA0>(res + (int64_t)j * a.ldr, o, x, a.alpha, a.beta);
+}
+
+template <typename T, bool BETA0, bool LDL, bool RF>
 __global__ void __launch_bounds__(kBlock) sweep_block_kernel(SweepArgs a) {
   __shared__ double sx[KB][NB], sb[KB][NB], spart[KB][4][NB];
   const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
@@ -762,7 +778,7 @@ __global__ void __launch_bounds__(kBlock) sweep_block_kernel(SweepArgs a) {
       const int64_t o = a.scatter ? a.scatter[i] : i;
 #pragma unroll
       for (int j = 0; j < KB; ++j)
-        if (j < kb) store_res<T, BETA0>(res + (int64_t)j * a.ldr, o, a.z[i + (int64_t)j * a.n], a.alpha, a.beta);
+        if (j < kb) finish_entry<T, BETA0, RF>(a, res, o, i, j, a.z[i + (int64_t)j * a.n]);
     }
     return;
   }
@@ -882,7 +898,7 @@ __global__ void __launch_bounds__(kBlock) sweep_block_kernel(SweepArgs a) {
     for (int j = 0; j < KB; ++j) {
       if (j < kb) {
         a.z[i + (int64_t)j * a.n] = x[j];
-        if (a.epi) store_res<T, BETA0>(res + (int64_t)j * a.ldr, o, x[j], a.alpha, a.beta);
+        if (a.epi) finish_entry<T, BETA0, RF>(a, res, o, i, j, x[j]);
       }
     }
   }
@@ -896,9 +912,12 @@ int32_t launch_sweep(mxlo_ctx *ctx, const SweepArgs &a) {
     grid += (a.n - dl + kBlock - 1) / kBlock;
   }
   MXLO_REQUIRE(grid < (1LL << 31), MXLO_ESHAPE, "triangular solve: n = %lld is too large", (long long)a.n);
-  if (a.kb > 0) {                                        // a group of right-hand sides: the same grid, the block kernel
-    if (a.beta == 0.0) hipLaunchKernelGGL((sweep_block_kernel<T, true, LDL>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((sweep_block_kernel<T, false, LDL>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
+  if (a.kb > 0 && a.xacc) {                              // a refined apply: the block kernel with the iterate's epilogue
+    if (a.beta == 0.0) hipLaunchKernelGGL((sweep_block_kernel<T, true, LDL, true>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((sweep_block_kernel<T, false, LDL, true>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
+  } else if (a.kb > 0) {                                 // a group of right-hand sides: the same grid, the block kernel
+    if (a.beta == 0.0) hipLaunchKernelGGL((sweep_block_kernel<T, true, LDL, false>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((sweep_block_kernel<T, false, LDL, false>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
   } else if (a.beta == 0.0) hipLaunchKernelGGL((sweep_kernel<T, true, LDL>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
   else hipLaunchKernelGGL((sweep_kernel<T, false, LDL>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, a);
   MXLO_LAUNCH_CHECK();
@@ -914,6 +933,8 @@ int32_t launch_sweep(mxlo_ctx *ctx, const SweepArgs &a) {
 // (opLU): the permutation the first launch reads v through / the epilogue writes res through. unit_lower (opLU): a lower
 // triangle is L, with an implicit unit diagonal, and the turn-around block is the OTHER triangle of the same storage.
 // grp.kb > 0: the block form — v and res are n x kb (ldv, ldr), z is n x kb with column stride n; the same launches.
+// A refined apply (xacc, block form only): first with v == NULL takes the right-hand side z already holds (the residual),
+// and the launch with epi ends as xmode says (SweepArgs) instead of writing res.
 struct Group {
   int kb = 0;
   int64_t ldr = 0, ldv = 0;
@@ -923,13 +944,13 @@ template <typename T, bool LDL = false>
 int32_t sweep(mxlo_ctx *ctx, const T *Tm, int64_t ld, int64_t n, bool upper, bool trans, const double *dinv, double *z,
               const T *v, bool first, bool turn, bool epi, T *res, double alpha, double beta, const double *dsc = nullptr,
               const double *tdinv = nullptr, const int *gather = nullptr, const int *scatter = nullptr, bool unit_lower = false,
-              Group grp = {}) {
+              Group grp = {}, double *xacc = nullptr, int xmode = 0) {
   const int64_t nb = (n + NB - 1) / NB;
   const bool asc = upper == trans;
   SweepArgs a{};
   a.Tm = Tm; a.ld = ld; a.n = n; a.z = z; a.rowpanel = trans; a.dinv_t = trans; a.res = res; a.alpha = alpha; a.beta = beta;
   a.dsc = dsc; a.gather = gather; a.scatter = scatter; a.dinv2_t = tdinv ? trans : 1;
-  a.kb = grp.kb; a.ldr = grp.ldr; a.ldv = grp.ldv;
+  a.kb = grp.kb; a.ldr = grp.ldr; a.ldv = grp.ldv; a.xacc = xacc; a.xmode = xmode;
   const bool upper2 = tdinv ? !upper : upper;
   a.tri_upper = upper; a.tri_unit = unit_lower && !upper; a.tri2_upper = upper2; a.tri2_unit = unit_lower && !upper2;
   const int64_t kfirst = asc ? 0 : nb - 1, klast = asc ? nb - 1 : 0, step = asc ? 1 : -1;
@@ -1049,14 +1070,15 @@ int32_t getrf_t(mxlo_ctx *ctx, const T *M, int64_t ldm, T *W, int64_t ldw, int64
 // the U' sweep, the L' sweep, the epilogue scattered.
 template <typename T>
 int32_t lu_mul_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t n, const double *dinv_l, const double *dinv_u, const int *perm,
-                 double *work, const T *v, bool trans, double alpha, double beta, Group grp = {}) {
+                 double *work, const T *v, bool trans, double alpha, double beta, Group grp = {}, double *xacc = nullptr, int xmode = 0) {
   const bool one = n <= NB;
   const double *d1 = trans ? dinv_u : dinv_l, *d2 = trans ? dinv_l : dinv_u;
-  const int *gather = trans ? nullptr : perm, *scatter = trans ? perm : nullptr;
-  MXLO_TRY(sweep<T>(ctx, W, ld, n, trans, trans, d1, work, v, true, true, one, res, alpha, beta, nullptr, d2, gather, scatter, true, grp));
+  const int *gather = (trans || !v) ? nullptr : perm, *scatter = trans ? perm : nullptr;   // a residual (!v) is already in the sweep's order
+  MXLO_TRY(sweep<T>(ctx, W, ld, n, trans, trans, d1, work, v, true, true, one, res, alpha, beta, nullptr, d2, gather, scatter, true, grp,
+                    xacc, xmode));
   if (one) return MXLO_OK;
   return sweep<T>(ctx, W, ld, n, !trans, trans, d2, work, (const T *)nullptr, false, false, true, res, alpha, beta, nullptr, nullptr,
-                  nullptr, scatter, true, grp);
+                  nullptr, scatter, true, grp, xacc, xmode);
 }
 
 // LDL: the chain of mxlo_ldlt — the same launches with the LDL' diagonal step and the pivots d handed to phases (b) and (c)
@@ -1173,13 +1195,13 @@ MXLO_API int32_t mxlo_trisolve_mul(mxlo_ctx *ctx, int32_t dtype, void *res, cons
 namespace {
 template <typename T>
 int32_t chol_mul_t(mxlo_ctx *ctx, T *res, const T *L, int64_t ld, int64_t n, const double *dinv, double *work, const T *v, double alpha,
-                   double beta, Group grp = {}) {
+                   double beta, Group grp = {}, double *xacc = nullptr, int xmode = 0) {
   const bool one = n <= NB;                              // a single block: both products and the epilogue in one launch
   MXLO_TRY(sweep<T>(ctx, L, ld, n, false, false, dinv, work, v, true, true, one, res, alpha, beta, nullptr, nullptr, nullptr, nullptr,
-                    false, grp));
+                    false, grp, xacc, xmode));
   if (one) return MXLO_OK;
   return sweep<T>(ctx, L, ld, n, false, true, dinv, work, (const T *)nullptr, false, false, true, res, alpha, beta, nullptr, nullptr,
-                  nullptr, nullptr, false, grp);
+                  nullptr, nullptr, false, grp, xacc, xmode);
 }
 }  // namespace
 
@@ -1196,13 +1218,13 @@ namespace {
 // x = Lt^{-T} (d .* (Lt^{-1} v)) with Lt = L D: the two sweeps of chol_mul_t; where the pivots come in is said at sweep()
 template <typename T>
 int32_t ldl_mul_t(mxlo_ctx *ctx, T *res, const T *L, int64_t ld, int64_t n, const double *dinv, const double *d, double *work,
-                  const T *v, double alpha, double beta, Group grp = {}) {
+                  const T *v, double alpha, double beta, Group grp = {}, double *xacc = nullptr, int xmode = 0) {
   const bool one = n <= NB;
   MXLO_TRY((sweep<T, true>(ctx, L, ld, n, false, false, dinv, work, v, true, true, one, res, alpha, beta, d, nullptr, nullptr, nullptr,
-                           false, grp)));
+                           false, grp, xacc, xmode)));
   if (one) return MXLO_OK;
   return sweep<T, true>(ctx, L, ld, n, false, true, dinv, work, (const T *)nullptr, false, false, true, res, alpha, beta, d, nullptr,
-                        nullptr, nullptr, false, grp);
+                        nullptr, nullptr, false, grp, xacc, xmode);
 }
 }  // namespace
 
@@ -1346,4 +1368,320 @@ MXLO_API int32_t mxlo_lu_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int6
   return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
     return lu_mul_t<float>(ctx, r, (const float *)W, ldw, n, dinv_l, dinv_u, perm, work, v, tr, alpha, beta, grp);
   });
+}
+
+// ---------------------------------------------------------------------------------------------- iterative refinement
+// refine = r of opCholesky / opLDL / opLU: x_0 = F \ v, then r times x += F \ (v - op(M) x), with the residual and x in f64
+// for both element types and ONE rounding to T, in the epilogue. A step is the chain of sweeps once more plus one residual
+// launch; nothing is read back. The matrix the residual reads is a snapshot the operator took at construction: for the
+// symmetric operators the strict upper triangle of M, parked in the strict upper triangle of the factor's storage W (which
+// no factorisation or sweep kernel reads or writes: all of them guard with row >= column), and the diagonal in dg; for
+// opLU a second n x n matrix A2 = P A, the stored matrix with its rows in pivot order. With A2 the iterate and the residual
+// of a step live in the order the sweeps work in (N: A2 x = P v, only v is gathered; T: A' x = A2' y with y = P x the
+// unscattered solution), so no launch permutes a vector in place and only the last epilogue scatters.
+namespace {
+constexpr int RLD = NB + 1;          // padded row of the transposed tile in LDS
+
+// R[:, j] = V[:, j] - op(A) X[:, j], j < kb <= KB, in row bands of 64: workgroup b owns rows 64 b .. and walks the 64-wide
+// chunks of the other index in ascending order. MODE 1: op(A) = A, the lanes run down the band's rows (unit stride).
+// MODE 2: op(A) = A', the chunk's tile is loaded with unit stride and turned in LDS. MODE 0: A is the strict upper triangle
+// U of a symmetric matrix with diagonal dg: chunks right of the band are read as in MODE 1 (U[band, chunk]), chunks left of
+// it as in MODE 2 (U[chunk, band]'), the band's own tile both ways; only elements with row < column are loaded. Per (row,
+// column j) the sum is 16-term fma chains per quarter of a chunk, carried over the chunks in order, then (p0 + p1) + (p2 +
+// p3): fixed, independent of kb and of the other columns. Rows >= n and masked elements are never loaded.
+template <typename T, int MODE>
+__global__ void __launch_bounds__(kBlock) residual_kernel(const T *__restrict__ A, int64_t ld, const T *__restrict__ dg, int64_t n,
+                                                          const T *__restrict__ V, int64_t ldv, const int *__restrict__ vgather,
+                                                          const double *__restrict__ X, double *__restrict__ R, int kb) {
+  __shared__ double sx[KB][NB], spart[KB][4][NB];
+  __shared__ T st[NB][RLD];
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int b = blockIdx.x, nbk = gridDim.x;
+  const int64_t i0 = (int64_t)b * NB;
+  const int bl = (int)(n - i0 < NB ? n - i0 : NB);
+  double acc[KB];
+#pragma unroll
+  for (int j = 0; j < KB; ++j) acc[j] = 0.0;
+  for (int t = 0; t < nbk; ++t) {
+    const int64_t c0 = (int64_t)t * NB;
+    const int cl = (int)(n - c0 < NB ? n - c0 : NB);
+    const int kind = MODE == 1 ? 0 : (MODE == 2 ? 1 : (t > b ? 0 : (t < b ? 1 : 2)));   // 0: direct, 1: turned, 2: the diagonal tile
+    __syncthreads();                                     // the chunk before is consumed
+    for (int e = tid; e < kb * NB; e += kBlock) {
+      const int j = e >> 6, r = e & 63;
+      sx[j][r] = r < cl ? X[c0 + r + (int64_t)j * n] : 0.0;
+    }
+    if (kind != 0) {                                     // st[cc][r] = A[c0 + r, i0 + cc]: row r of the chunk, column cc of the band
+      for (int cc = q; cc < NB; cc += 4) {
+        T x = T(0);
+        if (lane < cl && cc < bl && (kind == 1 || lane < cc)) x = __builtin_nontemporal_load(A + (c0 + lane) + (i0 + cc) * ld);
+        st[cc][lane] = x;
+      }
+    }
+    __syncthreads();
+    if (lane < bl) {
+#pragma unroll
+      for (int tt = 0; tt < 16; ++tt) {
+        const int c = q * 16 + tt;
+        if (c < cl) {
+          double m;
+          if (kind == 0) m = ld_stream(A + (i0 + lane) + (c0 + c) * ld);
+          else if (kind == 1) m = (double)st[lane][c];
+          else m = c > lane ? (double)st[c][lane] : (c < lane ? (double)st[lane][c] : (double)dg[i0 + lane]);
+#pragma unroll
+          for (int j = 0; j < KB; ++j)
+            if (j < kb) acc[j] = fma(m, sx[j][c], acc[j]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < KB; ++j)
+    if (j < kb) spart[j][q][lane] = acc[j];
+  __syncthreads();
+  if (tid < bl) {
+    const int64_t i = i0 + tid;
+    const int64_t src = vgather ? vgather[i] : i;
+#pragma unroll
+    for (int j = 0; j < KB; ++j)
+      if (j < kb)
+        R[i + (int64_t)j * n] = (double)V[src + (int64_t)j * ldv] -
+                                ((spart[j][0][tid] + spart[j][1][tid]) + (spart[j][2][tid] + spart[j][3][tid]));
+  }
+}
+
+template <typename T>
+int32_t launch_residual(mxlo_ctx *ctx, int mode, const T *A, int64_t ld, const T *dg, int64_t n, const T *V, int64_t ldv,
+                        const int *vgather, const double *X, double *R, int kb) {
+  const dim3 grid((unsigned)((n + NB - 1) / NB)), blk(kBlock);
+  if (mode == 0) hipLaunchKernelGGL((residual_kernel<T, 0>), grid, blk, 0, ctx->stream, A, ld, dg, n, V, ldv, vgather, X, R, kb);
+  else if (mode == 1) hipLaunchKernelGGL((residual_kernel<T, 1>), grid, blk, 0, ctx->stream, A, ld, dg, n, V, ldv, vgather, X, R, kb);
+  else hipLaunchKernelGGL((residual_kernel<T, 2>), grid, blk, 0, ctx->stream, A, ld, dg, n, V, ldv, vgather, X, R, kb);
+  MXLO_LAUNCH_CHECK();
+  return MXLO_OK;
+}
+
+// W[r, c] = M[r, c] for r < c and dg[i] = M[i, i], from the upper triangle of M (the one pack_upper_kernel reads); tiles
+// below the diagonal return at once. A row-major M is turned through LDS so that both sides keep unit stride.
+template <typename T>
+__global__ void __launch_bounds__(kBlock) sym_snapshot_kernel(T *__restrict__ W, int64_t ldw, T *__restrict__ dg,
+                                                              const T *__restrict__ M, int64_t ldm, int rowmajor, int64_t n) {
+  if (blockIdx.x > blockIdx.y) return;                 // tile (br, bc) of W with br <= bc
+  __shared__ T s[NB * (NB + 1)];
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int64_t r0 = (int64_t)blockIdx.x * NB, c0 = (int64_t)blockIdx.y * NB;
+  if (rowmajor) {                                      // M[r, c] = M[r * ldm + c]: unit stride along c
+    for (int rl = q; rl < NB; rl += 4) {
+      const int64_t r = r0 + rl, c = c0 + lane;
+      s[rl * (NB + 1) + lane] = (r < n && c < n && r <= c) ? M[r * ldm + c] : T(0);
+    }
+    __syncthreads();
+  }
+  for (int cc = q; cc < NB; cc += 4) {
+    const int64_t r = r0 + lane, c = c0 + cc;
+    if (r < n && c < n && r <= c) {
+      const T x = rowmajor ? s[lane * (NB + 1) + cc] : M[r + c * ldm];
+      if (r < c) W[r + c * ldw] = x;
+      else dg[r] = x;
+    }
+  }
+}
+
+// A2[i, c] = M[perm[i], c]: the stored matrix with its rows in pivot order
+template <typename T>
+__global__ void __launch_bounds__(kBlock) lu_snapshot_kernel(T *__restrict__ A2, int64_t lda, const T *__restrict__ M, int64_t ldm,
+                                                             int64_t n, const int *__restrict__ perm) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const int64_t src = perm[i];
+  for (int64_t c = blockIdx.y; c < n; c += gridDim.y) A2[i + c * lda] = M[src + c * ldm];
+}
+
+constexpr int MAX_STEPS = 8;         // linalg.py's MAX_REFINE
+
+// the operands every refined apply adds to check_apply's: steps, the 2 n KB doubles of work, the snapshot's further storage
+int32_t check_refine(int32_t dtype, const Operands &o, int64_t n, int32_t steps, const double *work, const void *extra, int64_t eb,
+                     const char *what, const char *name) {
+  MXLO_REQUIRE(steps >= 0 && steps <= MAX_STEPS, MXLO_EINVAL, "%s: steps = %d outside 0 .. %d", what, steps, MAX_STEPS);
+  if (n == 0 || o.k == 0) return MXLO_OK;
+  MXLO_REQUIRE(extra, MXLO_EINVAL, "%s: null %s", what, name);
+  MXLO_TRY(check_extra(dtype, o, n, work, 2 * n * KB * 8, what, "the work matrices"));
+  return check_extra(dtype, o, n, extra, eb, what, name);
+}
+
+// one group of a refined apply: solve(v, xmode) runs the operator's chain of sweeps, resid() the residual launch
+template <typename T, typename S, typename R>
+int32_t refine_group(const T *v, int steps, S &&solve, R &&resid) {
+  MXLO_TRY(solve(v, steps > 0 ? 1 : 0));
+  for (int s = 1; s <= steps; ++s) {
+    MXLO_TRY(resid());
+    MXLO_TRY(solve((const T *)nullptr, s == steps ? 3 : 2));
+  }
+  return MXLO_OK;
+}
+
+template <typename T>
+int32_t chol_refine_t(mxlo_ctx *ctx, T *res, int64_t ldr, const T *W, int64_t ld, int64_t n, const double *dinv, const double *d,
+                      const T *dg, double *work, const T *V, int64_t ldv, int64_t k, int steps, double alpha, double beta) {
+  double *z = work, *x = work + n * KB;
+  return for_groups(res, ldr, V, ldv, k, [&](T *r, const T *v, Group grp) {
+    return refine_group<T>(
+        v, steps,
+        [&](const T *rhs, int xmode) {
+          if (d) return ldl_mul_t<T>(ctx, r, W, ld, n, dinv, d, z, rhs, alpha, beta, grp, xmode ? x : nullptr, xmode);
+          return chol_mul_t<T>(ctx, r, W, ld, n, dinv, z, rhs, alpha, beta, grp, xmode ? x : nullptr, xmode);
+        },
+        [&]() { return launch_residual<T>(ctx, 0, W, ld, dg, n, v, ldv, nullptr, x, z, grp.kb); });
+  });
+}
+
+template <typename T>
+int32_t lu_refine_t(mxlo_ctx *ctx, T *res, int64_t ldr, const T *W, int64_t ld, int64_t n, const double *dinv_l, const double *dinv_u,
+                    const int *perm, const T *A2, int64_t lda, double *work, const T *V, int64_t ldv, int64_t k, int steps, bool trans,
+                    double alpha, double beta) {
+  double *z = work, *x = work + n * KB;
+  return for_groups(res, ldr, V, ldv, k, [&](T *r, const T *v, Group grp) {
+    return refine_group<T>(
+        v, steps,
+        [&](const T *rhs, int xmode) {
+          return lu_mul_t<T>(ctx, r, W, ld, n, dinv_l, dinv_u, perm, z, rhs, trans, alpha, beta, grp, xmode ? x : nullptr, xmode);
+        },
+        [&]() { return launch_residual<T>(ctx, trans ? 2 : 1, A2, lda, (const T *)nullptr, n, v, ldv, trans ? nullptr : perm, x, z, grp.kb); });
+  });
+}
+
+int32_t sym_refine(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t n, const double *dinv,
+                   const double *d, const void *dg, double *work, const void *V, int64_t ldv, int64_t k, int32_t steps, double alpha,
+                   double beta, bool ldl, const char *what) {
+  const Operands o{res, V, k, ldr, ldv};
+  MXLO_TRY(check_apply(ctx, dtype, o, W, ldw, n, dinv, work, what));
+  if (ldl && n > 0 && k > 0) {
+    MXLO_REQUIRE(d, MXLO_EINVAL, "%s: null pivots", what);
+    MXLO_TRY(check_extra(dtype, o, n, d, n * 8, what, "the pivots"));
+  }
+  MXLO_TRY(check_refine(dtype, o, n, steps, work, dg, n * (dtype == MXLO_F64 ? 8 : 4), what, "the diagonal of the snapshot"));
+  if (n == 0 || k == 0) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  if (dtype == MXLO_F64)
+    return chol_refine_t<double>(ctx, (double *)res, ldr, (const double *)W, ldw, n, dinv, d, (const double *)dg, work, (const double *)V,
+                                 ldv, k, steps, alpha, beta);
+  return chol_refine_t<float>(ctx, (float *)res, ldr, (const float *)W, ldw, n, dinv, d, (const float *)dg, work, (const float *)V, ldv, k,
+                              steps, alpha, beta);
+}
+
+}  // namespace
+
+MXLO_API int32_t mxlo_sym_snapshot(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_rowmajor, void *W, int64_t ldw,
+                                   int64_t n, void *dg) {
+  const char *what = "mxlo_sym_snapshot";
+  MXLO_TRY(check_common(ctx, dtype, W, ldw, n, what));
+  if (n == 0) return MXLO_OK;
+  MXLO_REQUIRE(M && dg && ldm >= (n > 1 ? n : 1), MXLO_EINVAL, "%s: null operand or ldm = %lld < n", what, (long long)ldm);
+  MXLO_REQUIRE(n < (1LL << 31) - NB, MXLO_ESHAPE, "%s: n = %lld is too large", what, (long long)n);
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4, wb = ((n - 1) * ldw + n) * es, mb = ((n - 1) * ldm + n) * es;
+  MXLO_REQUIRE(!bytes_overlap(M, mb, W, wb) && !bytes_overlap(M, mb, dg, n * es) && !bytes_overlap(dg, n * es, W, wb), MXLO_EINVAL,
+               "%s: M, the factor's storage and the diagonal vector overlap", what);
+  MXLO_DEVICE_GUARD(ctx);
+  const unsigned nb = (unsigned)((n + NB - 1) / NB);
+  if (dtype == MXLO_F64)
+    hipLaunchKernelGGL((sym_snapshot_kernel<double>), dim3(nb, nb), dim3(kBlock), 0, ctx->stream, (double *)W, ldw, (double *)dg,
+                       (const double *)M, ldm, m_rowmajor ? 1 : 0, n);
+  else
+    hipLaunchKernelGGL((sym_snapshot_kernel<float>), dim3(nb, nb), dim3(kBlock), 0, ctx->stream, (float *)W, ldw, (float *)dg,
+                       (const float *)M, ldm, m_rowmajor ? 1 : 0, n);
+  MXLO_LAUNCH_CHECK();
+  return MXLO_OK;
+}
+
+MXLO_API int32_t mxlo_lu_snapshot(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, const int32_t *perm, void *A2, int64_t lda,
+                                  int64_t n) {
+  const char *what = "mxlo_lu_snapshot";
+  MXLO_TRY(check_common(ctx, dtype, A2, lda, n, what));
+  if (n == 0) return MXLO_OK;
+  MXLO_REQUIRE(M && perm && ldm >= (n > 1 ? n : 1), MXLO_EINVAL, "%s: null operand or ldm = %lld < n", what, (long long)ldm);
+  MXLO_REQUIRE(n < (1LL << 31) - NB, MXLO_ESHAPE, "%s: n = %lld is too large", what, (long long)n);
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4, ab = ((n - 1) * lda + n) * es, mb = ((n - 1) * ldm + n) * es;
+  MXLO_REQUIRE(!bytes_overlap(M, mb, A2, ab) && !bytes_overlap(perm, n * 4, A2, ab), MXLO_EINVAL,
+               "%s: the snapshot overlaps M or the permutation", what);
+  MXLO_DEVICE_GUARD(ctx);
+  const dim3 grid((unsigned)((n + kBlock - 1) / kBlock), (unsigned)(n < 1024 ? n : 1024));
+  if (dtype == MXLO_F64)
+    hipLaunchKernelGGL((lu_snapshot_kernel<double>), grid, dim3(kBlock), 0, ctx->stream, (double *)A2, lda, (const double *)M, ldm, n, perm);
+  else
+    hipLaunchKernelGGL((lu_snapshot_kernel<float>), grid, dim3(kBlock), 0, ctx->stream, (float *)A2, lda, (const float *)M, ldm, n, perm);
+  MXLO_LAUNCH_CHECK();
+  return MXLO_OK;
+}
+
+namespace {
+// R and X of a residual entry point: n x k doubles with column stride n, k <= KB; R may overlap nothing it reads
+int32_t check_residual(mxlo_ctx *ctx, int32_t dtype, const double *R, const void *A, int64_t ld, const void *dg, int64_t n, const void *V,
+                       int64_t ldv, const double *X, int64_t k, const char *what) {
+  MXLO_TRY(check_common(ctx, dtype, A, ld, n, what));
+  MXLO_REQUIRE(k >= 0 && k <= KB && ldv >= (n > 1 ? n : 1), MXLO_ESHAPE, "%s: k = %lld (at most %d), ldv = %lld", what, (long long)k, KB,
+               (long long)ldv);
+  if (n == 0 || k == 0) return MXLO_OK;
+  MXLO_REQUIRE(R && V && X, MXLO_EINVAL, "%s: null operand", what);
+  MXLO_REQUIRE(n < (1LL << 31) - NB, MXLO_ESHAPE, "%s: n = %lld is too large", what, (long long)n);
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4, rb = n * k * 8;
+  MXLO_REQUIRE(!bytes_overlap(R, rb, X, rb) && !bytes_overlap(R, rb, V, ((k - 1) * ldv + n) * es) &&
+                   !bytes_overlap(R, rb, A, ((n - 1) * ld + n) * es) && !(dg && bytes_overlap(R, rb, dg, n * es)),
+               MXLO_EINVAL, "%s: R overlaps an operand it reads", what);
+  return MXLO_OK;
+}
+}  // namespace
+
+MXLO_API int32_t mxlo_sym_residual(mxlo_ctx *ctx, int32_t dtype, double *R, const void *U, int64_t ld, const void *dg, int64_t n,
+                                   const void *V, int64_t ldv, const double *X, int64_t k) {
+  MXLO_TRY(check_residual(ctx, dtype, R, U, ld, dg, n, V, ldv, X, k, "mxlo_sym_residual"));
+  if (n == 0 || k == 0) return MXLO_OK;
+  MXLO_REQUIRE(dg, MXLO_EINVAL, "mxlo_sym_residual: null diagonal");
+  MXLO_DEVICE_GUARD(ctx);
+  if (dtype == MXLO_F64)
+    return launch_residual<double>(ctx, 0, (const double *)U, ld, (const double *)dg, n, (const double *)V, ldv, nullptr, X, R, (int)k);
+  return launch_residual<float>(ctx, 0, (const float *)U, ld, (const float *)dg, n, (const float *)V, ldv, nullptr, X, R, (int)k);
+}
+
+MXLO_API int32_t mxlo_gen_residual(mxlo_ctx *ctx, int32_t dtype, double *R, const void *A, int64_t ld, int64_t n, const void *V,
+                                   int64_t ldv, const double *X, int64_t k, int32_t op_mode) {
+  MXLO_TRY(check_residual(ctx, dtype, R, A, ld, nullptr, n, V, ldv, X, k, "mxlo_gen_residual"));
+  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "mxlo_gen_residual: op_mode %d", op_mode);
+  if (n == 0 || k == 0) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  const int mode = op_mode == MXLO_OP_N ? 1 : 2;
+  if (dtype == MXLO_F64)
+    return launch_residual<double>(ctx, mode, (const double *)A, ld, (const double *)nullptr, n, (const double *)V, ldv, nullptr, X, R, (int)k);
+  return launch_residual<float>(ctx, mode, (const float *)A, ld, (const float *)nullptr, n, (const float *)V, ldv, nullptr, X, R, (int)k);
+}
+
+MXLO_API int32_t mxlo_chol_mul_refine(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t n,
+                                      const double *dinv, const void *dg, double *work, const void *V, int64_t ldv, int64_t k,
+                                      int32_t steps, double alpha, double beta) {
+  return sym_refine(ctx, dtype, res, ldr, W, ldw, n, dinv, nullptr, dg, work, V, ldv, k, steps, alpha, beta, false, "mxlo_chol_mul_refine");
+}
+
+MXLO_API int32_t mxlo_ldl_mul_refine(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t n,
+                                     const double *dinv, const double *d, const void *dg, double *work, const void *V, int64_t ldv,
+                                     int64_t k, int32_t steps, double alpha, double beta) {
+  return sym_refine(ctx, dtype, res, ldr, W, ldw, n, dinv, d, dg, work, V, ldv, k, steps, alpha, beta, true, "mxlo_ldl_mul_refine");
+}
+
+MXLO_API int32_t mxlo_lu_mul_refine(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t n,
+                                    const double *dinv_l, const double *dinv_u, const int32_t *perm, const void *A2, int64_t lda,
+                                    double *work, const void *V, int64_t ldv, int64_t k, int32_t steps, int32_t op_mode, double alpha,
+                                    double beta) {
+  const char *what = "mxlo_lu_mul_refine";
+  const Operands o{res, V, k, ldr, ldv};
+  MXLO_TRY(check_lu_apply(ctx, dtype, o, W, ldw, n, dinv_l, dinv_u, perm, work, what));
+  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "%s: op_mode %d", what, op_mode);
+  MXLO_REQUIRE(lda >= (n > 1 ? n : 1), MXLO_ESHAPE, "%s: lda = %lld < n", what, (long long)lda);
+  MXLO_TRY(check_refine(dtype, o, n, steps, work, A2, ((n - 1) * lda + n) * (dtype == MXLO_F64 ? 8 : 4), what, "the snapshot"));
+  if (n == 0 || k == 0) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  const bool tr = op_mode != MXLO_OP_N;
+  if (dtype == MXLO_F64)
+    return lu_refine_t<double>(ctx, (double *)res, ldr, (const double *)W, ldw, n, dinv_l, dinv_u, perm, (const double *)A2, lda, work,
+                               (const double *)V, ldv, k, steps, tr, alpha, beta);
+  return lu_refine_t<float>(ctx, (float *)res, ldr, (const float *)W, ldw, n, dinv_l, dinv_u, perm, (const float *)A2, lda, work,
+                            (const float *)V, ldv, k, steps, tr, alpha, beta);
 }

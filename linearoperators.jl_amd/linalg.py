@@ -6,7 +6,9 @@ The factorisation, the inverses of the diagonal blocks and the block substitutio
 Real Float64 / Float32 only. `mul!` on an n x k matrix (`F \\ V`, src/operations.jl:34-36) takes the block form of the sweeps for k > 1
 (`mxlo_*_mul_block`): the chain of launches of one vector apply and one read of the factor per GROUP = 8 columns, each column
 bit-identical to its vector apply. The inverse of a general dense matrix is `opLU` (partially pivoted LU); `opInverse` itself
-stays triangular-only. A pivoted (Bunch–Kaufman) or sparse LDLᵀ are not provided.
+stays triangular-only. A pivoted (Bunch–Kaufman) or sparse LDLᵀ are not provided. `refine=r` on the three
+factorisation operators adds r steps of iterative refinement to every apply (`mxlo_*_mul_refine`), with the residual and the
+iterate in Float64 and a snapshot of M the operator keeps.
 """
 from __future__ import annotations
 
@@ -21,6 +23,8 @@ from .operators import LinearOperator, LinearOperatorException, columnwise, stat
 
 BLOCK = 64            # block column width of csrc/linalg.hip (NB)
 GROUP = 8             # right-hand sides per pass of the block sweeps (KB): the work matrix is n x GROUP doubles
+MAX_REFINE = 8        # largest `refine`: only there to stop a typo from queueing thousands of launches
+RESIDUAL_LAUNCHES = 1  # launches of one residual (row bands of 64, no partial sums), whatever n is
 
 
 class PosDefException(Exception):
@@ -92,12 +96,48 @@ def _check_block_operands(res, m, T, n):
     return lds[0], lds[1], k
 
 
-def _work(n, device):
-    """The f64 work matrix of the sweeps, n x GROUP with column stride n: allocated once, at construction."""
-    return torch.empty(max(1, n) * GROUP, dtype=torch.float64, device=device)
+def _work(n, device, refine=0):
+    """The f64 work matrix of the sweeps, n x GROUP with column stride n: allocated once, at construction. With refine > 0 a
+    second one follows it, the iterate x."""
+    return torch.empty((2 if refine else 1) * max(1, n) * GROUP, dtype=torch.float64, device=device)
 
 
-def opCholesky(M: torch.Tensor, check: bool = False):
+def _check_refine(refine, name: str) -> int:
+    """Runs before M is looked at. bool is an int to Python; it is not a step count."""
+    if isinstance(refine, bool) or not isinstance(refine, int):
+        raise TypeError(f"{name}: refine must be an int, got {type(refine).__name__}")
+    if not 0 <= refine <= MAX_REFINE:
+        raise ValueError(f"{name}: refine = {refine} outside 0 .. MAX_REFINE = {MAX_REFINE}")
+    return refine
+
+
+def _refined(vec_call):
+    """prod and its block form for refine > 0: `vec_call(res, ldr, V, ldv, k, a, b)` is the block-shaped entry point, k = 1
+    the vector apply."""
+    def prod(res, v, a, b, T, n):
+        _check_operands(res, v, T)
+        ld = max(1, n)
+        vec_call(res, ld, v, ld, 1, a, b)
+
+    def block(res, m, a, b, T, n):
+        ldr, ldv, k = _check_block_operands(res, m, T, n)
+        vec_call(res, ldr, m, ldv, k, a, b)
+    return prod, block
+
+
+_REFINE_DOC = """
+
+    refine = r (an int, 0 <= r <= MAX_REFINE; 0: the plain solve, launch for launch): every apply computes x₀ = F \\ v, then r
+    times x += F \\ (v − M x), and res = α x_r + β res. The residual and every x are Float64 for both element types; the
+    one rounding to the element type is in the epilogue. The step count is fixed: no convergence test, nothing is read
+    back, so the apply still allocates nothing, never synchronises and can be captured. Refinement converges when the
+    plain solve is contractive, roughly ρ·cond·eps(T) < 1 (ρ the growth of the factorisation); when it is not, the iterates
+    may not improve and nothing reports it. The exceptions of the factorisation are raised as before."""
+
+
+def opCholesky(M: torch.Tensor, check: bool = False, refine: int = 0):
+
+
     """opCholesky(M; check=false) — src/linalg.jl:44-58: the inverse of a symmetric positive definite matrix through its
     Cholesky factorisation, computed ONCE here, on the device, into storage the operator owns (M is not modified).
 
@@ -106,7 +146,12 @@ def opCholesky(M: torch.Tensor, check: bool = False):
     `PosDefException(info)` with the 1-based order of the failing leading minor. `check=True` runs `check_hermitian`
     and `check_positive_definite` first. prod! = tprod! = ctprod!: res = α (M⁻¹ v) + β res; with β == 0 res is not
     read; res may be v. An apply allocates nothing and never synchronises, so it can be captured (`capture_mul`). Matrix
-    operands (n x k, k > 1) go through `mxlo_chol_mul_block`: 8 columns per chain of launches; res may be V."""
+    operands (n x k, k > 1) go through `mxlo_chol_mul_block`: 8 columns per chain of launches; res may be V.
+
+    With refine > 0 the operator keeps a snapshot of M, taken here: its strict upper triangle in the unused strict upper
+    triangle of the factor's storage, its diagonal in n further elements — no second n x n buffer; the work space is 2 n x 8
+    doubles. A later change of M is not seen, as before."""
+    refine = _check_refine(refine, "opCholesky")
     n = _check_matrix(M, "opCholesky")
     T = M.dtype
     if check:
@@ -122,7 +167,7 @@ def opCholesky(M: torch.Tensor, check: bool = False):
     ldw = max(1, n)
     nblk = (n + BLOCK - 1) // BLOCK
     dinv = torch.empty(max(1, nblk) * BLOCK * BLOCK, dtype=torch.float64, device=M.device)
-    work = _work(n, M.device)
+    work = _work(n, M.device, refine)
     info_dev = torch.zeros(1, dtype=torch.int32, device=M.device)
     info = C.c_int32(0)
     code = dtype_code(T)
@@ -131,6 +176,10 @@ def opCholesky(M: torch.Tensor, check: bool = False):
     if info.value != 0:
         raise PosDefException(info.value)
     pW, pD, pZ = W.data_ptr(), dinv.data_ptr(), work.data_ptr()
+    if refine:                                          # the snapshot: after the chain, which leaves the strict upper triangle alone
+        dg = torch.empty(max(1, n), dtype=T, device=M.device)
+        _lib.call("mxlo_sym_snapshot", ctx.handle, code, St.data_ptr(), ldm, 1 if tr else 0, pW, ldw, n, dg.data_ptr())
+        pG = dg.data_ptr()
 
     def prod(res, v, a, b):                             # mulFact!(res, LL, v, α, β) — src/linalg.jl:3-9
         _check_operands(res, v, T)
@@ -141,15 +190,25 @@ def opCholesky(M: torch.Tensor, check: bool = False):
         _lib.call("mxlo_chol_mul_block", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, n, pD, pZ, m.data_ptr(), ldv, k,
                   float(a), float(b))
 
+    if refine:
+        rprod, rblock = _refined(lambda res, ldr, V, ldv, k, a, b: _lib.call(
+            "mxlo_chol_mul_refine", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, n, pD, pG, pZ, V.data_ptr(), ldv, k, refine,
+            float(a), float(b)))
+        prod = lambda res, v, a, b: rprod(res, v, a, b, T, n)                   # noqa: E731
+        block = lambda res, m, a, b: rblock(res, m, a, b, T, n)                 # noqa: E731
     columnwise(prod)                                    # `F \ V` takes matrices: k == 1 column by column, else the block form
     prod._matrix = block
     op = LinearOperator(T, n, n, True, True, prod, prod, prod, S=Storage(T, M.device))      # isreal(M), hermitian = true
     op._deps = (W,)
-    op._factor = (W, dinv, work)                        # owned storage (kept alive with the operator)
+    op._factor = (W, dinv, work) + ((dg,) if refine else ())     # owned storage (kept alive with the operator)
+    op._refine = refine
     return op
 
 
-def opLDL(M: torch.Tensor, check: bool = False):
+opCholesky.__doc__ += _REFINE_DOC
+
+
+def opLDL(M: torch.Tensor, check: bool = False, refine: int = 0):
     """opLDL(M; check=false) — ext/LinearOperatorsLDLFactorizationsExt.jl:5-18 (docstring: src/linalg.jl:60-73) for a DENSE
     symmetric M: its inverse through M = L D Lᵀ (L unit lower triangular, D diagonal), computed ONCE here, on the device,
     into storage the operator owns (M is not modified). Only the UPPER triangle of M is read (`Symmetric(M, :U)`);
@@ -165,7 +224,13 @@ def opLDL(M: torch.Tensor, check: bool = False):
 
     prod! = tprod! = ctprod!: res = α (M⁻¹ v) + β res; with β == 0 res is not read; res may be v. An apply allocates
     nothing and never synchronises, so it can be captured (`capture_mul`). `op._d` is a Float64 device tensor with the n
-    pivots (the diagonal of D): by Sylvester's law of inertia their signs are the inertia of M."""
+    pivots (the diagonal of D): by Sylvester's law of inertia their signs are the inertia of M.
+
+    refine > 0 is the cure for a general indefinite M that stays inside the fixed chain of launches: one step brings the
+    backward error from ρ·eps (ρ the growth of |L||D||Lᵀ|) back to the order of n·eps as long as ρ·cond·eps < 1. The
+    operator then keeps a snapshot of M, taken here: its strict upper triangle in the unused strict upper triangle of the
+    factor's storage, its diagonal in n further elements — no second n x n buffer; the work space is 2 n x 8 doubles."""
+    refine = _check_refine(refine, "opLDL")
     n = _check_matrix(M, "opLDL")
     T = M.dtype
     if check:
@@ -180,7 +245,7 @@ def opLDL(M: torch.Tensor, check: bool = False):
     nblk = (n + BLOCK - 1) // BLOCK
     dinv = torch.empty(max(1, nblk) * BLOCK * BLOCK, dtype=torch.float64, device=M.device)
     d = torch.empty(n, dtype=torch.float64, device=M.device)
-    work = _work(n, M.device)
+    work = _work(n, M.device, refine)
     info_dev = torch.zeros(1, dtype=torch.int32, device=M.device)
     info = C.c_int32(0)
     code = dtype_code(T)
@@ -189,6 +254,10 @@ def opLDL(M: torch.Tensor, check: bool = False):
     if info.value != 0:
         raise ZeroPivotException(info.value)
     pW, pD, pd, pZ = W.data_ptr(), dinv.data_ptr(), d.data_ptr(), work.data_ptr()
+    if refine:
+        dg = torch.empty(max(1, n), dtype=T, device=M.device)
+        _lib.call("mxlo_sym_snapshot", ctx.handle, code, St.data_ptr(), ldm, 1 if tr else 0, pW, ldw, n, dg.data_ptr())
+        pG = dg.data_ptr()
 
     def prod(res, v, a, b):                             # mulFact!(res, LDL, v, α, β) — src/linalg.jl:3-9
         _check_operands(res, v, T)
@@ -199,13 +268,23 @@ def opLDL(M: torch.Tensor, check: bool = False):
         _lib.call("mxlo_ldl_mul_block", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, n, pD, pd, pZ, m.data_ptr(), ldv, k,
                   float(a), float(b))
 
+    if refine:
+        rprod, rblock = _refined(lambda res, ldr, V, ldv, k, a, b: _lib.call(
+            "mxlo_ldl_mul_refine", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, n, pD, pd, pG, pZ, V.data_ptr(), ldv, k,
+            refine, float(a), float(b)))
+        prod = lambda res, v, a, b: rprod(res, v, a, b, T, n)                   # noqa: E731
+        block = lambda res, m, a, b: rblock(res, m, a, b, T, n)                 # noqa: E731
     columnwise(prod)
     prod._matrix = block
     op = LinearOperator(T, n, n, True, True, prod, prod, prod, S=Storage(T, M.device))      # isreal(M), hermitian = true
     op._deps = (W,)
     op._d = d                                           # the pivots; their signs are the inertia of M
-    op._factor = (W, dinv, d, work)
+    op._factor = (W, dinv, d, work) + ((dg,) if refine else ())
+    op._refine = refine
     return op
+
+
+opLDL.__doc__ += _REFINE_DOC
 
 
 def opInverse(M: torch.Tensor, symm: bool = False, herm: bool = False):
@@ -270,7 +349,7 @@ def opInverse(M: torch.Tensor, symm: bool = False, herm: bool = False):
     return op
 
 
-def opLU(M: torch.Tensor, symm: bool = False, herm: bool = False):
+def opLU(M: torch.Tensor, symm: bool = False, herm: bool = False, refine: int = 0):
     """opLU(M; symm=false, herm=false): the inverse of a GENERAL square dense M, what `opInverse(M)` = `M \\ v` of
     src/linalg.jl:27-32 is for a full matrix — through P M = L U with partial pivoting, computed ONCE here, on the device,
     into storage the operator owns (M is not modified; a later change of M is not seen).
@@ -285,7 +364,13 @@ def opLU(M: torch.Tensor, symm: bool = False, herm: bool = False):
     prod!: res = α (M⁻¹ v) + β res; tprod! = ctprod!: with Mᵀ. With β == 0 res is not read; res may be v. An apply is
     2⌈n/64⌉ − 1 launches and nothing else, so it can be captured (`capture_mul`). `op._perm` is the int32 device
     permutation, M[op._perm[i], :] = (L U)[i, :] for the stored matrix; `op._factor[0]` holds L (unit, strictly below the
-    diagonal) and U."""
+    diagonal) and U.
+
+    With refine > 0 the operator owns a SECOND n x n matrix, which doubles its memory: the factor's storage holds both L and
+    U, so the snapshot of the stored matrix the residual reads has no free triangle to live in. It is kept with its rows in
+    pivot order (P M), so that a step's residual comes out in the order the sweeps work in. The work space is 2 n x 8
+    doubles. prod!, tprod! and ctprod! all refine, each with its own op(M)."""
+    refine = _check_refine(refine, "opLU")
     n = _check_matrix(M, "opLU")
     T = M.dtype
     St, tr = _stored_colmajor(M)                       # tr: St is the column-major storage of Mᵀ
@@ -297,7 +382,7 @@ def opLU(M: torch.Tensor, symm: bool = False, herm: bool = False):
     dinv_l = torch.empty(max(1, nblk) * BLOCK * BLOCK, dtype=torch.float64, device=M.device)
     dinv_u = torch.empty_like(dinv_l)
     pbuf = torch.empty(max(1, 2 * n), dtype=torch.int32, device=M.device)     # the permutation, then LAPACK's ipiv (0-based)
-    work = _work(n, M.device)
+    work = _work(n, M.device, refine)
     info_dev = torch.zeros(1, dtype=torch.int32, device=M.device)
     info = C.c_int32(0)
     code = dtype_code(T)
@@ -306,6 +391,10 @@ def opLU(M: torch.Tensor, symm: bool = False, herm: bool = False):
     if info.value != 0:
         raise SingularException(info.value)
     pW, pL, pU, pP, pZ = W.data_ptr(), dinv_l.data_ptr(), dinv_u.data_ptr(), pbuf.data_ptr(), work.data_ptr()
+    if refine:                                          # the snapshot: the stored matrix, rows in pivot order
+        A2 = torch.empty((n, n), dtype=T, device=M.device).t()
+        _lib.call("mxlo_lu_snapshot", ctx.handle, code, St.data_ptr(), ldm, pP, A2.data_ptr(), ldw, n)
+        pA = A2.data_ptr()
 
     def solve(res, v, a, b, mode):                      # mulFact!(res, lu(M), v, α, β) — src/linalg.jl:3-9
         _check_operands(res, v, T)
@@ -317,6 +406,14 @@ def opLU(M: torch.Tensor, symm: bool = False, herm: bool = False):
         _lib.call("mxlo_lu_mul_block", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, n, pL, pU, pP, pZ, m.data_ptr(), ldv,
                   k, mode, float(a), float(b))
 
+    if refine:
+        def refined(mode):
+            return _refined(lambda res, ldr, V, ldv, k, a, b: _lib.call(
+                "mxlo_lu_mul_refine", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, n, pL, pU, pP, pA, ldw, pZ, V.data_ptr(),
+                ldv, k, refine, mode, float(a), float(b)))
+        rs = {_lib.OP_N: refined(_lib.OP_N), _lib.OP_T: refined(_lib.OP_T)}
+        solve = lambda res, v, a, b, mode: rs[mode][0](res, v, a, b, T, n)      # noqa: E731
+        block = lambda res, m, a, b, mode: rs[mode][1](res, m, a, b, T, n)      # noqa: E731
     fwd, bwd = (_lib.OP_T, _lib.OP_N) if tr else (_lib.OP_N, _lib.OP_T)
     prod = columnwise(lambda res, v, a, b: solve(res, v, a, b, fwd))
     tprod = columnwise(lambda res, u, a, b: solve(res, u, a, b, bwd))
@@ -325,5 +422,9 @@ def opLU(M: torch.Tensor, symm: bool = False, herm: bool = False):
     op = LinearOperator(T, n, n, bool(symm), bool(herm), prod, tprod, tprod, S=Storage(T, M.device))
     op._deps = (W,)
     op._perm = pbuf[:n]
-    op._factor = (W, dinv_l, dinv_u, pbuf, work)        # owned storage (kept alive with the operator)
+    op._factor = (W, dinv_l, dinv_u, pbuf, work) + ((A2,) if refine else ())    # owned storage (kept alive with the operator)
+    op._refine = refine
     return op
+
+
+opLU.__doc__ += _REFINE_DOC

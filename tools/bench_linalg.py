@@ -20,6 +20,14 @@ k = 1 rows are the single-vector applies. --mul-only prints the `mul!(R, op, V)`
 run of the same shapes on another commit).
 
     python tools/bench_linalg.py --block [n ...] > profiles/linalg_block.txt
+
+--refine: the apply of opCholesky, opLDL, opLU and transpose(opLU) built with refine = 0, 1, 2, at n = 2048, 8192, 16384 in both
+precisions, for k = 1 and k = 8: time, spread, launches, and the fraction of the 8 TB/s peak by the byte model of DESIGN.md §4
+((r + 1) reads of the factor and r n² elements for the residuals per group). `x r=0` is the time over the refine = 0 row;
+the expectation to hold it against is (r + 1) + r × (residual time / plain apply time). The refine = 0 rows are the plain apply;
+the same shapes on another commit come from `--block --mul-only` (its k = 1 and k = 8 rows), which is how a baseline is taken.
+
+    python tools/bench_linalg.py --refine [n ...] > profiles/linalg_refine.txt
 """
 import ctypes as C
 import os
@@ -39,7 +47,8 @@ tm = Timer(ctx)
 PEAK = 8000.0          # GB/s
 BLOCK = "--block" in sys.argv
 MUL_ONLY = "--mul-only" in sys.argv
-NS = [int(a) for a in sys.argv[1:] if not a.startswith("--")] or ([2048, 8192, 16384] if BLOCK else [1024, 4096, 16384])
+REFINE = "--refine" in sys.argv
+NS = [int(a) for a in sys.argv[1:] if not a.startswith("--")] or ([2048, 8192, 16384] if BLOCK or REFINE else [1024, 4096, 16384])
 
 
 def timeit(fn, reps):
@@ -149,8 +158,46 @@ def block_legs():
             torch.cuda.empty_cache()
 
 
+def refine_legs():
+    """the apply with refine = 0, 1, 2: see the module docstring"""
+    print(f"# {torch.cuda.get_device_name(0)}; iterative refinement; ms per call, median of 3 event-timed windows, spread = (max - min) / median")
+    print(f"# bytes: (r + 1) reads of the factor + r n^2 elements for the residuals, per group of 8 columns; peak {PEAK:.0f} GB/s")
+    print(f"{'case':26s} {'n':>6s} {'k':>2s} {'r':>2s} {'ms':>9s} {'spread':>6s} {'launch':>6s} {'GB/s':>8s} {'%peak':>6s} {'x r=0':>6s}", flush=True)
+    for dtype, tag in ((torch.float64, "f64"), (torch.float32, "f32")):
+        es = 8 if dtype is torch.float64 else 4
+        for n in NS:
+            M = spd(n, dtype)
+            K = quasi_definite(M)
+            A = simple_matrix(n, dtype)
+            tri, full = n * (n + 1) // 2 * es, n * n * es
+            reps = 20 if n <= 2048 else (5 if n <= 8192 else 3)
+            for name, make, X, fbytes, tr in (("opCholesky", lo.opCholesky, M, 2 * tri, False), ("opLDL", lo.opLDL, K, 2 * tri, False),
+                                              ("opLU", lo.opLU, A, full, False), ("transpose(opLU)", lo.opLU, A, full, True)):
+                base = {}
+                for r in (0, 1, 2):
+                    op = make(X, refine=r)
+                    op = op.T if tr else op
+                    for k in (1, 8):
+                        V, R = colmajor(n, k, dtype, 10 * n + k), colmajor(n, k, dtype, 1)
+                        v, res = (V[:, 0], R[:, 0]) if k == 1 else (V, R)
+                        mul = lambda: lo.mul(res, op, v, 1.0, 0.0)
+                        ms = timeit(mul, reps)
+                        sp, nl = timeit.spread, launches(mul)
+                        base.setdefault(k, ms)
+                        gbs = ((r + 1) * fbytes + r * full) / ms / 1e6
+                        print(f"{name + ' ' + tag:26s} {n:6d} {k:2d} {r:2d} {ms:9.4f} {100 * sp:5.1f}% {nl:6d} {gbs:8.1f} {100 * gbs / PEAK:6.2f} "
+                              f"{ms / base[k]:6.2f}", flush=True)
+                    del op
+                    torch.cuda.empty_cache()
+            del M, K, A
+            torch.cuda.empty_cache()
+
+
 if BLOCK:
     block_legs()
+    sys.exit(0)
+if REFINE:
+    refine_legs()
     sys.exit(0)
 
 print(f"# {torch.cuda.get_device_name(0)}; times: ms per call, median of 3 event-timed windows; GB/s by the byte model; peak {PEAK:.0f} GB/s")
