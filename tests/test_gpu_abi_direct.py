@@ -100,6 +100,9 @@ def test_tune_keys(lo, dev):
     d, v = rng.standard_normal(n), rng.standard_normal(n)
     D = lo.opDiagonal(torch.from_numpy(d).to(dev))
     want = oracle.diag_mul(np.empty(n), d, v, 1.5, 0.0)
+    # opDiagonal / opHouseholder consume only some of these keys: gemm_tile (kron GEMM), extend_tiles_per_block (sorted extension),
+    # combine_blocks_per_cu (quasi-Newton panel combine) and dots_max_nc (panels of more than one column) are set and must be
+    # harmless here; tests/test_gpu_forms.py (table: tests/forms_cases.py) runs each of them on the operator that reads it.
     for key, vals in (("blocks_per_cu", (0, 1, 8)), ("nt_min_bytes", (0, 1 << 40)), ("house_inline_n", (0, 1 << 40)), ("red_blocks_per_cu", (1, 16)),
                       ("house_reverse", (0, 1)), ("house_fused", (0, 1)), ("gemm_tile", (32, 64, 128, -1, 0)),
                       ("extend_tiles_per_block", (1, 8, 0)),
