@@ -607,7 +607,11 @@ int32_t mxlo_csc_mul(mxlo_csc *h, void *res, const void *v, double alpha, double
  * from `simple_sparse_matrix(ComplexF64, …)`): the same chunked sweep on 16- / 8-byte elements, component-wise complex
  * products accumulated in two doubles. op_mode MXLO_OP_N = A*v, _T = transpose(A)*v (values as stored), _C = A'*v (values
  * conjugated in the sweep). Scalars as (re, im) pairs with MXLO_ALPHA_REAL / MXLO_BETA_REAL and the width flags, like every
- * `_c` entry point. mxlo_csc_mul / mxlo_csc_mul_block refuse a complex handle and mxlo_csc_mul_c a real one (MXLO_EINVAL);
+ * `_c` entry point. Where alpha enters follows SparseArrays: MXLO_OP_N with a Complex alpha scales each gathered v[col] first
+ * (`αxj = B[col] * α; C[row] += nzv * αxj`), _T / _C scale the finished sum (`C[col] += tmp * α`) — with finite data the same
+ * to rounding, with an Inf in v or in a stored value the reference's NaN / ±Inf map in each mode; a Real alpha scales
+ * component by component in the closing step of every mode (same map either way).
+ * mxlo_csc_mul / mxlo_csc_mul_block refuse a complex handle and mxlo_csc_mul_c a real one (MXLO_EINVAL);
  * a complex handle cannot be a block of the (real) one-launch block-diagonal operator. */
 int32_t mxlo_csc_mul_c(mxlo_csc *h, void *res, const void *v, double alpha_re, double alpha_im, double beta_re, double beta_im,
                        int32_t op_mode, int32_t flags);

@@ -662,7 +662,9 @@ struct CHermCfg {
 // last row group; mode 2 (CT = 1): one tile of a diagonal block per workgroup.
 // DSEL (EDGE = false, CT = 1): a tile of the diagonal block of a FULL row group of an aligned matrix — unmasked loads,
 // then a select zeroes what is at or above the diagonal (dense.hip: herm_strip_body).
-template <typename R, int CT, bool EDGE, bool DSEL = false, bool NT = true>
+// DIAG: the tile straddles the diagonal (DSEL, and the masked mode-2 bodies) — a compile-time fact of the call site, so the
+// strips strictly below the diagonal (modes 0 and 1, whatever CT is) carry none of the diagonal selects.
+template <typename R, int CT, bool EDGE, bool DSEL = false, bool NT = true, bool DIAG = DSEL>
 __device__ __forceinline__ void
 cherm_strip_body(const C<R> *__restrict__ A, int64_t lda, const C<R> *__restrict__ v, int64_t n,
                  double *__restrict__ Prow, double *__restrict__ Pcol, int64_t ng, int qint, int mode, int64_t t,
@@ -670,7 +672,9 @@ cherm_strip_body(const C<R> *__restrict__ A, int64_t lda, const C<R> *__restrict
   constexpr int RPL = CHermCfg<R>::RPL, HR = CHermCfg<R>::HR, DT = CHermCfg<R>::DT;
   using V = typename Vec16<C<R>>::type;      // f64x2 / f32x4: RPL complex elements
   static_assert(!DSEL || (!EDGE && CT == 1), "DSEL: one unmasked-load tile of a diagonal block");
-  int64_t G, tile0, slot;                    // row group, first column tile, row-partial slot
+  static_assert(!DIAG || CT == 1, "a diagonal-block tile is a one-tile body");
+  static_assert(!DSEL || DIAG, "DSEL tiles straddle the diagonal");
+  int64_t G, tile0, slot;                   // row group, first column tile, row-partial slot
   if constexpr (DSEL) {                      // diagonal block of row group t/DT, tile t%DT
     G = t / DT;
     tile0 = DT * G + t % DT;
@@ -763,26 +767,42 @@ cherm_strip_body(const C<R> *__restrict__ A, int64_t lda, const C<R> *__restrict
       const double xar = ina ? (double)v[ca].re : 0.0, xai = ina ? (double)v[ca].im : 0.0;
       const double xbr = inb ? (double)v[cb].re : 0.0, xbi = inb ? (double)v[cb].im : 0.0;
       double par = 0.0, pai = 0.0, pbr = 0.0, pbi = 0.0;
+      int below = 0;                            // row - column of this lane's element (r = 0) of column k = 0 of the tile
+      if constexpr (DIAG) {
+        below = (int)(gr - (j0 + cg));
+        asm volatile("" : "+v"(below));         // (opaque to the optimiser, as in dense.hip: herm_strip_body)
+      }
 #pragma unroll
       for (int r = 0; r < RPL; ++r) {
         const double ar = (double)e[q][2 * r], ai = (double)e[q][2 * r + 1];
         const double br = (double)e[q + 8][2 * r], bi = (double)e[q + 8][2 * r + 1];
-        prr[r] = fma(ar, xar, prr[r]);       // L[r][c] * v[c]
-        prr[r] = fma(-ai, xai, prr[r]);
-        pri[r] = fma(ar, xai, pri[r]);
-        pri[r] = fma(ai, xar, pri[r]);
-        prr[r] = fma(br, xbr, prr[r]);
-        prr[r] = fma(-bi, xbi, prr[r]);
-        pri[r] = fma(br, xbi, pri[r]);
-        pri[r] = fma(bi, xbr, pri[r]);
-        par = fma(ar, vrr[r], par);          // conj(L[r][c]) * v[r]
-        par = fma(ai, vri[r], par);
-        pai = fma(ar, vri[r], pai);
-        pai = fma(-ai, vrr[r], pai);
-        pbr = fma(br, vrr[r], pbr);
-        pbr = fma(bi, vri[r], pbr);
-        pbi = fma(br, vri[r], pbi);
-        pbi = fma(-bi, vrr[r], pbi);
+        double car = xar, cai = xai, cbr = xbr, cbi = xbi;                 // v[column] of the two elements
+        double rar = vrr[r], rai = vri[r], rbr = vrr[r], rbi = vri[r];     // v[row] of the two elements
+        if constexpr (DIAG) {
+          // A tile of a diagonal block: an element at or above the diagonal takes no part — its (zeroed) value must not
+          // meet v either, or an Inf / NaN in v would come back as 0 * Inf = NaN in rows and columns the triangle never
+          // touches. The vector operands of those products are zeroed too (dense.hip: herm_strip_body): 0 * 0 adds
+          // nothing, finite results keep their bits.
+          const bool ka = below + r > 2 * q, kb = below + r > 2 * (q + 8);
+          car = ka ? car : 0.0, cai = ka ? cai : 0.0, rar = ka ? rar : 0.0, rai = ka ? rai : 0.0;
+          cbr = kb ? cbr : 0.0, cbi = kb ? cbi : 0.0, rbr = kb ? rbr : 0.0, rbi = kb ? rbi : 0.0;
+        }
+        prr[r] = fma(ar, car, prr[r]);       // L[r][c] * v[c]
+        prr[r] = fma(-ai, cai, prr[r]);
+        pri[r] = fma(ar, cai, pri[r]);
+        pri[r] = fma(ai, car, pri[r]);
+        prr[r] = fma(br, cbr, prr[r]);
+        prr[r] = fma(-bi, cbi, prr[r]);
+        pri[r] = fma(br, cbi, pri[r]);
+        pri[r] = fma(bi, cbr, pri[r]);
+        par = fma(ar, rar, par);             // conj(L[r][c]) * v[r]
+        par = fma(ai, rai, par);
+        pai = fma(ar, rai, pai);
+        pai = fma(-ai, rar, pai);
+        pbr = fma(br, rbr, pbr);
+        pbr = fma(bi, rbi, pbr);
+        pbi = fma(br, rbi, pbi);
+        pbi = fma(-bi, rbr, pbi);
       }
       w8r[q] = (hi ? pbr : par) + __shfl_xor(hi ? par : pbr, 32, 64);
       w8i[q] = (hi ? pbi : pai) + __shfl_xor(hi ? pai : pbi, 32, 64);
@@ -860,7 +880,7 @@ cherm_edge_kernel(const C<R> *__restrict__ A, int64_t lda, const C<R> *__restric
   t -= n_all;
   if (t < n_last) return cherm_strip_body<R, CT, true>(A, lda, v, n, Prow, Pcol, ng, qint, 1, t, rowred);
   t -= n_last;
-  cherm_strip_body<R, 1, true>(A, lda, v, n, Prow, Pcol, ng, qint, 2, t + CHermCfg<R>::DT * g0, rowred);
+  cherm_strip_body<R, 1, true, false, true, true>(A, lda, v, n, Prow, Pcol, ng, qint, 2, t + CHermCfg<R>::DT * g0, rowred);
 }
 
 // 32 rows per workgroup, 8 lanes per row, fixed-order sums (as herm_finish_kernel), then the sum of

@@ -149,6 +149,10 @@ int32_t csc_mul_c_t(mxlo_csc *h, cx<R> *res, const cx<R> *v, const ScalArgs &s, 
   const SpLaunch L = sp_launch_of(h, op_mode != MXLO_OP_N);
   if (L.nchunks == 0) return MXLO_OK;
   return dispatch_c<R>(s, [&]<typename RA, typename RB, bool B0>() -> int32_t {
+    if (op_mode == MXLO_OP_N && !s.a_real) {   // A*x with a Complex α: x is scaled at the gather (sparse_kernels.h: SpFinCplx)
+      const SpFinCplx<R, RA, RB, B0, true> pre{Sc<RA>{(RA)s.are, (RA)s.aim, false}, (RB)s.bre, (RB)s.bim, s.b_real};
+      return csc_launch<cx<R>, SpFinCplx<R, RA, RB, B0, true>, B0, false>(h, L, res, v, pre, 1, 0, 0);
+    }
     const SpFinCplx<R, RA, RB, B0> fin{Sc<RA>{(RA)s.are, (RA)s.aim, s.a_real}, (RB)s.bre, (RB)s.bim, s.b_real};
     if (op_mode == MXLO_OP_C) return csc_launch<cx<R>, SpFinCplx<R, RA, RB, B0>, B0, true>(h, L, res, v, fin, 1, 0, 0);
     return csc_launch<cx<R>, SpFinCplx<R, RA, RB, B0>, B0, false>(h, L, res, v, fin, 1, 0, 0);

@@ -95,6 +95,8 @@ struct SpNum {                     // Float64 / Float32
   __device__ static __forceinline__ Acc zero() { return Acc{0.0}; }
   template <bool CONJ>
   __device__ static __forceinline__ void madd(Acc &a, T val, T x) { a.v += (double)val * (double)x; }
+  template <bool CONJ, typename FIN>
+  __device__ static __forceinline__ void madd_pre(Acc &a, T val, T x, const FIN &) { madd<CONJ>(a, val, x); }   // (real: never PRE)
   __device__ static __forceinline__ void add(Acc &a, const Acc &b) { a.v += b.v; }
   __device__ static __forceinline__ Acc shfl_xor(const Acc &a, int off) { return Acc{__shfl_xor(a.v, off, 64)}; }
   __device__ static __forceinline__ void store(double *p, const Acc &a) { p[0] = a.v; }
@@ -113,6 +115,15 @@ struct SpNum<cx<R>> {              // ComplexF64 / ComplexF32: Julia's component
     a.re += (vr * xr) - (vi * xi);
     a.im += (vr * xi) + (vi * xr);
   }
+  // x scaled by the caller's Complex α BEFORE it meets the stored value (FIN::PRE: the A*x sweep, see SpFinCplx)
+  template <bool CONJ, typename FIN>
+  __device__ static __forceinline__ void madd_pre(Acc &a, cx<R> val, cx<R> x, const FIN &fin) {
+    const double vr = (double)val.re, vi = CONJ ? -(double)val.im : (double)val.im;
+    const double ar = (double)fin.alpha.re, ai = (double)fin.alpha.im, x0 = (double)x.re, x1 = (double)x.im;
+    const double xr = (x0 * ar) - (x1 * ai), xi = (x0 * ai) + (x1 * ar);          // αxj = x * α, component by component
+    a.re += (vr * xr) - (vi * xi);
+    a.im += (vr * xi) + (vi * xr);
+  }
   __device__ static __forceinline__ void add(Acc &a, const Acc &b) { a.re += b.re; a.im += b.im; }
   __device__ static __forceinline__ Acc shfl_xor(const Acc &a, int off) {
     return Acc{__shfl_xor(a.re, off, 64), __shfl_xor(a.im, off, 64)};
@@ -123,28 +134,40 @@ struct SpNum<cx<R>> {              // ComplexF64 / ComplexF32: Julia's component
 // ---- the closing step res = alpha * sum (+ beta * res): the scalars in the types the caller passed them in
 template <typename T, typename CA, typename CB, bool BETA0>
 struct SpFinReal {
+  static constexpr bool PRE = false;
   CA alpha;
   CB beta;
   __device__ __forceinline__ T operator()(const typename SpNum<T>::Acc &a, T old) const {
     return fin_ab<T, CA, CB, BETA0>(alpha * (CA)(T)a.v, beta, old);
   }
 };
-template <typename R, typename RA, typename RB, bool BETA0>
+// PRE_: a Complex α in the A*x sweep. SparseArrays' `_spmatmul!` scales x FIRST (αxj = B[col] * α; C[row] += nzv * αxj),
+// its transposed sweeps scale the finished sum (C[col] += tmp * α). With finite data the two agree to rounding; with an Inf
+// in x or in a stored value they do not: (±Inf ± Inf i) * α after the sum is Inf - Inf = NaN where the reference keeps ±Inf.
+// So the mode-N sweep multiplies every gathered x by α (sp_walk) and closes with α = 1. A Real α scales component by
+// component either way — same NaN / ±Inf map — and stays in the closing step, as do modes T and C.
+template <typename R, typename RA, typename RB, bool BETA0, bool PRE_ = false>
 struct SpFinCplx {
+  static constexpr bool PRE = PRE_;
   Sc<RA> alpha;
   RB bre, bim;
   bool b_real;
   __device__ __forceinline__ cx<R> operator()(const typename SpNum<cx<R>>::Acc &a, cx<R> old) const {
     RA tr, ti;
-    alpha.template mul<R>(cx<R>((R)a.re, (R)a.im), tr, ti);
+    if constexpr (PRE) {
+      tr = (RA)(R)a.re;
+      ti = (RA)(R)a.im;
+    } else {
+      alpha.template mul<R>(cx<R>((R)a.re, (R)a.im), tr, ti);
+    }
     return cfin<R, RA, RB, BETA0>(tr, ti, bre, bim, b_real, old);
   }
 };
 
 // sum of (value * x[index]) over the LDS entries e0, e0 + step, ... < e1, in that order, kSpBatch gathers at a time
-template <typename T, bool CONJ>
+template <typename T, bool CONJ, typename FIN>
 __device__ __forceinline__ typename SpNum<T>::Acc sp_walk(const T *__restrict__ x, const T *sval, const int32_t *sidx, int e0,
-                                                           int e1, int step) {
+                                                           int e1, int step, const FIN &fin) {
   typename SpNum<T>::Acc acc = SpNum<T>::zero();
   for (int e = e0; e < e1; e += step * kSpBatch) {
     T v[kSpBatch], xv[kSpBatch];
@@ -157,7 +180,10 @@ __device__ __forceinline__ typename SpNum<T>::Acc sp_walk(const T *__restrict__ 
     }
 #pragma unroll
     for (int u = 0; u < kSpBatch; ++u)
-      if (e + u * step < e1) SpNum<T>::template madd<CONJ>(acc, v[u], xv[u]);
+      if (e + u * step < e1) {
+        if constexpr (FIN::PRE) SpNum<T>::template madd_pre<CONJ>(acc, v[u], xv[u], fin);
+        else SpNum<T>::template madd<CONJ>(acc, v[u], xv[u]);
+      }
   }
   return acc;
 }
@@ -249,7 +275,7 @@ __device__ __forceinline__ void spmv_chunk(T *__restrict__ res, const T *__restr
         if constexpr (!BETA0) ro = res[row];
       }
       for (int j = 0; j < ncols; ++j) {
-        typename N::Acc acc = sp_walk<T, CONJ>(x + j * ldx, sval, sidx, (int)(q0 - c.k0) + l, (int)(q1 - c.k0), g);
+        typename N::Acc acc = sp_walk<T, CONJ>(x + j * ldx, sval, sidx, (int)(q0 - c.k0) + l, (int)(q1 - c.k0), g, fin);
         for (int off = g >> 1; off > 0; off >>= 1) N::add(acc, N::shfl_xor(acc, off));
         if (l == 0) {
           T *rp = res + j * ldr + row;
@@ -261,7 +287,7 @@ __device__ __forceinline__ void spmv_chunk(T *__restrict__ res, const T *__restr
   } else {                                                // one long row (or a piece of one): the whole workgroup
     __shared__ double red[(kBlock / 64) * 2];
     for (int j = 0; j < ncols; ++j) {
-      typename N::Acc acc = sp_walk<T, CONJ>(x + j * ldx, sval, sidx, tid, c.nz, kBlock);
+      typename N::Acc acc = sp_walk<T, CONJ>(x + j * ldx, sval, sidx, tid, c.nz, kBlock, fin);
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) N::add(acc, N::shfl_xor(acc, off));
       if (lane == 0) N::store(red + wave * N::NACC, acc);

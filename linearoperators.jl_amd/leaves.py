@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import operator
 import os
+import sys
 
 import ctypes as C
 from typing import Optional, Sequence
@@ -21,8 +22,9 @@ import torch
 
 from . import _lib
 from .device import Storage, check_vec, ctx_of, dtype_code, get_ctx, indexed_device, ptr, storage_of
-from .operators import (AbstractLinearOperator, LinearOperator, LinearOperatorException, _c4, adjoint, columnwise, compose,
-                        conj_scalar, issymmetric, ishermitian, mul, scalar_flags, state_version, storage_type, to_dense, transpose)
+from .operators import (AbstractLinearOperator, LinearOperator, LinearOperatorException, _c4, _is_complex_scalar, adjoint,
+                        columnwise, compose, conj_scalar, issymmetric, ishermitian, mul, scalar_flags, state_version,
+                        storage_type, to_dense, transpose)
 
 
 def _default_device() -> torch.device:
@@ -492,6 +494,11 @@ class _CscHandle:
                 "chunk": a[7]}
 
     def __del__(self):
+        # At interpreter shutdown (an object kept alive until then, e.g. by the traceback of a failed test) finalisers run in
+        # no defined order: the ctx this handle points to may be destroyed already, and mxlo_csc_destroy synchronises its
+        # stream. The process is ending; its device memory goes with it.
+        if sys.is_finalizing():
+            return
         try:
             _lib.lib().mxlo_csc_destroy(self.h)
         except Exception:
@@ -572,8 +579,33 @@ def LinearOperatorFromSparse(M: torch.Tensor, symmetric: bool = False, hermitian
             _lib.call("mxlo_eye_mul_c", ctx.handle, code, ptr(res), ptr(tmp), res.shape[0], res.shape[0], *_c4(a, b),
                       scalar_flags(res.dtype, a, b))
 
-        prod = columnwise(lambda res, v, a, b: cspmv(res, v, a, b, fwd))
-        tprod = columnwise(lambda res, u, a, b: cspmv(res, u, a, b, bwd))
+        def cprod(res, v, a, b):
+            # M*v with a Complex α scales x FIRST in the reference (SparseArrays `_spmatmul!`: αxj = B[col] * α), and so does
+            # the kernel's mode N (sparse_kernels.h: SpFinCplx). A CSR alias runs M*v as the TRANSPOSED sweep of its stored
+            # matrix, which closes with α * sum as the reference's transposed sweeps do — another NaN / ±Inf map when x or a
+            # stored value is not finite. For the alias only, α * v is formed in one pass of its own and the sweep runs
+            # with α = 1, so M*v is the same whichever layout M was handed over in.
+            if tr and _is_complex_scalar(a):
+                va = torch.empty_like(v)
+                _lib.call("mxlo_eye_mul_c", get_ctx(res.device).handle, code, ptr(va), ptr(v), v.shape[0], v.shape[0],
+                          *_c4(a, 0.0), scalar_flags(T, a, 0.0))
+                return cspmv(res, va, 1.0, b, fwd)
+            return cspmv(res, v, a, b, fwd)
+
+        prod = columnwise(cprod)
+        def ctprod_t(res, u, a, b):
+            # transpose(M)*u scales the finished sum in the reference (`C[col] += tmp * α`). A CSR alias runs it as the mode-N
+            # sweep of its stored matrix, which scales x first for a Complex α: for the alias only, the sweep runs with
+            # α = 1 into a temporary and res = α * tmp + β * res closes it (as cadj_of_csr does).
+            if tr and _is_complex_scalar(a):
+                tmp = torch.empty(res.shape[0], dtype=T, device=res.device)
+                cspmv(tmp, u, 1.0, 0.0, bwd)
+                _lib.call("mxlo_eye_mul_c", get_ctx(res.device).handle, code, ptr(res), ptr(tmp), res.shape[0], res.shape[0],
+                          *_c4(a, b), scalar_flags(res.dtype, a, b))
+                return
+            cspmv(res, u, a, b, bwd)
+
+        tprod = columnwise(ctprod_t)
         ctprod = columnwise(cadj_of_csr if tr else (lambda res, w, a, b: cspmv(res, w, a, b, _lib.OP_C)))
         op = LinearOperator(T, nrow, ncol, symmetric, hermitian, prod, tprod, ctprod,
                             S=S if S is not None else Storage(T, vals.device))
@@ -745,6 +777,8 @@ class _BlockDiagHandle:
         _lib.call("mxlo_blockdiag_create", ctx.handle, dtype_code(dtype), arr, len(descs), C.byref(self.h))
 
     def __del__(self):
+        if sys.is_finalizing():                # (as _CscHandle.__del__: the ctx may be gone already)
+            return
         try:
             _lib.lib().mxlo_blockdiag_destroy(self.h)
         except Exception:
