@@ -262,7 +262,9 @@ int32_t mxlo_debug_counters(int64_t out[12]);
  * Buffers, sizes and alpha/beta are baked in (the data they point to is read at replay time). The ctx
  * stream must not be the default stream (mxlo_ctx_create_stream gives the ctx one it owns). Not
  * capturable: push! and mxlo_memcpy_d2h (host control flow / synchronising) and the first opHermitian
- * apply of a new size (workspace growth) — run those outside, once, before capturing.
+ * apply of a new size (workspace growth) — run those outside, once, before capturing. Such a call invalidates the
+ * capture: mxlo_graph_end then returns MXLO_EHIP and no graph, and leaves the stream fit for the next capture
+ * (mxlo_graph_begin also clears an invalidated state an earlier failed capture left on the stream).
  * Staleness: a quasi-Newton apply bakes the handle's slot order, insert position and update count into the
  * recorded launches, and opHermitian bakes the ctx scratch pointer. A graph therefore remembers the generation of
  * every quasi-Newton handle it captured (bumped by push!, reset! and mode changes) and of the ctx scratch
@@ -945,6 +947,46 @@ int32_t mxlo_lu_mul_refine(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr,
                            const double *dinv_l, const double *dinv_u, const int32_t *perm, const void *A2, int64_t lda,
                            double *work, const void *V, int64_t ldv, int64_t k, int32_t steps, int32_t op_mode, double alpha,
                            double beta);
+
+/* opQR — what opInverse(M) = `M \ v` of src/linalg.jl:27-32 (mulFact!, src/linalg.jl:3-9) is for a RECTANGULAR dense M: the
+ * QR solve. mxlo_geqrf factors the tall orientation F (mf x nf, mf >= nf >= 1) as F = Q R by unpivoted Householder
+ * reflections, in the operator's own column-major W (mf x nf, ldw >= mf), which is first filled from M: column-major mf x nf
+ * (ldm >= mf) as it lies, or — m_trans — the column-major nf x mf storage of F' (ldm >= nf), transposed through LDS while it
+ * is copied. M is not modified. Afterwards R is on and above the diagonal of W and the reflector vectors below it with an
+ * implicit unit first entry (LAPACK's layout); tfac holds one 64 x 64 compact-WY factor T per block column (f64,
+ * column-major, upper triangular, Q_k = I - V_k T_k V_k'), dinv the inverses of R's diagonal blocks as mxlo_tri_prepare makes
+ * them (both ceil(nf/64) blocks of 64 x 64 doubles; tfac must come zeroed).
+ * Per block column of 64: (a) jb + 1 launches over ALL row chunks of the panel (chunks of 64 rows, dealt round-robin to
+ * at most 512 workgroups), one per column: a workgroup first adds up, in a fixed order, the partial dots the launch before
+ * left (column c with every column of the panel, rows below its diagonal) and from those alone has larfg's beta =
+ * -sign(alpha) |(alpha, x)|, tau = (beta - alpha) / beta, v = x / (alpha - beta) (x == 0: tau = 0, H = I), w_j = tau v' a_j
+ * and column c of T; it then updates its rows of the later panel columns, turns its rows of column c into v and leaves the
+ * partial dots of column c + 1 — no workgroup waits for another one and the cost is proportional to the panel; (c) the
+ * trailing update C -= V (T' (V' C)): V' C in row splits on v_mfma_f64_16x16x4_f64 (f32 data: the f32 MFMA), the splits
+ * added in order and multiplied by T' in f64, the rank-64 update on the MFMA again. (b) The block inverses of R: one launch
+ * at the end. The chain of launches depends on (mf, nf) only. The norms are taken without rescaling.
+ * A column of F whose norm from the diagonal down is exactly zero or not finite stores its 1-BASED index in *info_dev
+ * (LinearAlgebra.SingularException(info)); every later launch of the factorisation returns at once; *info (host) = that word,
+ * copied once after the last launch — the only synchronisation. Not capturable (MXLO_ESTATE). scratch: scratch_len >=
+ * 2 (512 * 64 + 64) + (512 + 2 ceil(nf/64)) * 4096 doubles, needed during the call only. No two operands may overlap. */
+int32_t mxlo_geqrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_trans, void *W, int64_t ldw, int64_t mf,
+                   int64_t nf, double *tfac, double *dinv, double *scratch, int64_t scratch_len, int32_t *info_dev, int32_t *info);
+/* mulFact!(res, qr(F), v, α, β) with W, tfac, dinv from mxlo_geqrf. MXLO_OP_N: res (nf) = alpha * x + beta * res, x =
+ * inv(R) (Q' v)[0:nf] the least-squares solution of F x ~ v (v: mf entries). Launch 0 loads v into the f64 work vector z
+ * and leaves the partial dots with V_0; launch k = 1 .. nb (nb = ceil(nf/64)) adds them up, multiplies by T_{k-1}', updates
+ * z -= V_{k-1} w on its rows and leaves the partial dots with V_k; then the descending sweep of mxlo_trisolve_mul solves with
+ * R out of z[0:nf], the epilogue fused into its last launch. MXLO_OP_T (MXLO_OP_C == T): res (mf) = alpha * y + beta * res,
+ * y = Q [inv(R') u; 0] the minimum-norm solution of F' y = u (u: nf entries): the ascending R' sweep from u into z[0:nf],
+ * then nb + 1 reflector launches with the blocks descending and T_k, the last one writing res over all mf entries.
+ * EXACTLY 2 ceil(nf/64) + 1 launches in both modes, whatever mf is, and nothing else: no allocation, copy or
+ * synchronisation, so an apply can be captured. Every reflector panel V_k is streamed by TWO launches (the one that takes
+ * its dots and the next one, which updates z with it; a panel larger than the caches comes from HBM both times), R is read
+ * once by the sweep: about (2 mf nf - nf^2 / 2) sizeof(T) bytes; tools/bench_linalg.py rates an apply by the one-read model
+ * (mf nf + nf^2 / 2) sizeof(T). All sums in a fixed order in f64: bit-reproducible.
+ * work: mf + 2 * 512 * 64 doubles. res == v is allowed when mf == nf; any other overlap of res and v, or of either with
+ * W, tfac, dinv or work, is MXLO_EINVAL before anything is launched. With beta == 0 res is not read. */
+int32_t mxlo_qr_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t mf, int64_t nf, const double *tfac,
+                    const double *dinv, double *work, const void *v, int32_t op_mode, double alpha, double beta);
 
 #ifdef __cplusplus
 }

@@ -270,6 +270,20 @@ static void try_linearise(mxlo_graph *g, int max_nodes) {
   (void)hipGetLastError();
 }
 
+// A capture that broke the rules (push!'s synchronisation inside it, say) is "invalidated". hipStreamEndCapture reports that and
+// returns no graph, but the runtime leaves the stream in the invalidated state with the dead capture's last nodes: the next capture
+// begun on that stream — torch hands its pooled streams out again after 32 — is accepted and then fails at its first launch with
+// "invalid argument". An empty capture begun and ended on the stream goes through the regular end and clears that state.
+static void clear_invalidated_capture(hipStream_t s) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &st) == hipSuccess && st == hipStreamCaptureStatusInvalidated) {
+    hipGraph_t g = nullptr;
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) (void)hipStreamEndCapture(s, &g);
+    if (g) (void)hipGraphDestroy(g);
+  }
+  (void)hipGetLastError();
+}
+
 MXLO_API int32_t mxlo_graph_begin(mxlo_ctx *ctx) {
   MXLO_REQUIRE(ctx, MXLO_EINVAL, "ctx is NULL");
   MXLO_DEVICE_GUARD(ctx);
@@ -277,6 +291,7 @@ MXLO_API int32_t mxlo_graph_begin(mxlo_ctx *ctx) {
   MXLO_REQUIRE(ctx->stream != nullptr, MXLO_ESTATE,
                "mxlo_graph_begin: the default stream cannot be captured; give the ctx a stream "
                "(mxlo_ctx_set_stream / mxlo_ctx_create_stream)");
+  clear_invalidated_capture(ctx->stream);                // left by a failed capture of another ctx or library on this stream
   MXLO_HIP(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
   ctx->capturing = true;
   ctx->captured_qn.clear();
@@ -294,7 +309,8 @@ MXLO_API int32_t mxlo_graph_end(mxlo_ctx *ctx, mxlo_graph **out) {
   if (e != hipSuccess || !graph) {  // a call inside the capture was not capturable (sync, allocation)
     set_error("mxlo_graph_end: capture failed: %s — only stream-ordered work (mul!, solve_shifted_system!, "
               "diag!) can be captured; push! and first-use workspace growth synchronise", hipGetErrorString(e));
-    (void)hipGetLastError();
+    if (graph) (void)hipGraphDestroy(graph);
+    clear_invalidated_capture(ctx->stream);              // the stream must be fit for the next capture
     return MXLO_EHIP;
   }
   mxlo_graph *g = new mxlo_graph();

@@ -1685,3 +1685,529 @@ MXLO_API int32_t mxlo_lu_mul_refine(mxlo_ctx *ctx, int32_t dtype, void *res, int
   return lu_refine_t<float>(ctx, (float *)res, ldr, (const float *)W, ldw, n, dinv_l, dinv_u, perm, (const float *)A2, lda, work,
                             (const float *)V, ldv, k, steps, tr, alpha, beta);
 }
+
+// ---------------------------------------------------------------------------------------------- geqrf / qr_mul
+// opQR (src/linalg.jl:3-9, 27-32 for a rectangular dense M): F = Q R of the TALL orientation F (mf x nf, mf >= nf) by unpivoted
+// Householder reflections in block columns of NB, LAPACK's layout (R on and above the diagonal of W, the reflector vectors
+// below it with an implicit unit first entry) with one NB x NB compact-WY factor T per block column, Q_k = I - V_k T_k V_k'.
+// Rows are cut into chunks of NB dealt round-robin to at most QG workgroups. A pass over a tall panel leaves one partial
+// sum per workgroup and column; the NEXT launch's workgroups each add them up in the same fixed order, so nothing but the
+// launch boundary orders the workgroups, and the grid and the order of every sum depend on the shape only.
+namespace {
+
+constexpr int QG = 512;              // most workgroups of a pass over the rows = partial slots per column
+
+inline int qr_grid(int64_t rows) {
+  const int64_t ch = (rows + NB - 1) / NB;
+  return (int)(ch < 1 ? 1 : (ch < QG ? ch : QG));
+}
+
+// s[c] = sum over g < G of part[g * NB + c]: four strided quarters, then (p0 + p1) + (p2 + p3)
+__device__ __forceinline__ void qr_reduce(const double *__restrict__ part, int G, double *s, double (*spart)[NB], int lane, int q) {
+  double acc = 0.0;
+  int g = q;
+  for (; g + 28 < G; g += 32) {                          // eight independent loads in flight, added in the order of the plain loop
+    double p[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) p[t] = part[(int64_t)(g + 4 * t) * NB + lane];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) acc += p[t];
+  }
+  for (; g < G; g += 4) acc += part[(int64_t)g * NB + lane];
+  spart[q][lane] = acc;
+  __syncthreads();
+  if (q == 0) s[lane] = (spart[0][lane] + spart[1][lane]) + (spart[2][lane] + spart[3][lane]);
+  __syncthreads();
+}
+
+// W = F: M as it lies (column-major mf x nf), or — trans — M is the column-major nf x mf storage of F', turned through LDS
+template <typename T>
+__global__ void __launch_bounds__(kBlock) qr_copy_kernel(T *__restrict__ W, int64_t ldw, const T *__restrict__ M, int64_t ldm, int trans,
+                                                         int64_t mf, int64_t nf) {
+  __shared__ T s[NB * (NB + 1)];
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int64_t i0 = (int64_t)blockIdx.x * NB, c0 = (int64_t)blockIdx.y * NB;
+  if (!trans) {
+    for (int cl = q; cl < NB; cl += 4) {
+      const int64_t i = i0 + lane, c = c0 + cl;
+      if (i < mf && c < nf) W[i + c * ldw] = M[i + c * ldm];
+    }
+    return;
+  }
+  for (int il = q; il < NB; il += 4) {                 // F[i, c] = M[c + i * ldm]: unit stride along c
+    const int64_t i = i0 + il, c = c0 + lane;
+    s[il * (NB + 1) + lane] = (i < mf && c < nf) ? M[c + i * ldm] : T(0);
+  }
+  __syncthreads();
+  for (int cl = q; cl < NB; cl += 4) {
+    const int64_t i = i0 + lane, c = c0 + cl;
+    if (i < mf && c < nf) W[i + c * ldw] = s[lane * (NB + 1) + cl];
+  }
+}
+
+// phase (a), one launch per panel column c = -1 .. jb - 1 over all row chunks of the panel (rows j0 .. mf, columns j0 .. j0 + jb).
+// Launch c (>= 0) first adds up what launch c - 1 left: pin, the dots of column c with every column of the panel over the rows
+// strictly below its diagonal row d = j0 + c, and din, row d itself. From those alone every workgroup has the reflector of
+// column c in larfg's convention — beta = -sign(alpha) |(alpha, x)|, tau = (beta - alpha) / beta, v = x / (alpha - beta);
+// x == 0: tau = 0, H = I — and w_j = tau v' a_j for the later columns; workgroup 0 also writes column c of T,
+// T[0:c, c] = -tau T[0:c, 0:c] (V[:, 0:c]' v), T[c, c] = tau. Then every workgroup turns its rows of column c into v, applies
+// a_j -= w_j v to its rows of the later columns, and (c + 1 < jb) leaves pout / dout for column c + 1. Launch -1 only does the
+// latter, for column 0. A column whose norm from the diagonal down is zero or not finite stores its 1-based index in *info.
+template <typename T>
+__global__ void __launch_bounds__(kBlock) geqrf_panel_kernel(T *W, int64_t ldw, int64_t mf, int64_t j0, int jb, int c,
+                                                             double *tfac, const double *__restrict__ pin,
+                                                             const double *__restrict__ din, double *__restrict__ pout,
+                                                             double *__restrict__ dout, int *info) {
+  __shared__ double sS[NB], sD[NB], sW[NB], spart[4][NB];
+  if (*info != 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int g = blockIdx.x, G = gridDim.x;
+  const int cn = c + 1 < jb ? c + 1 : -1;
+  const int64_t d = j0 + c, dn = j0 + cn;
+  double scale = 0.0, beta = 0.0;
+  if (c >= 0) {
+    qr_reduce(pin, G, sS, spart, lane, q);
+    if (tid < NB) sD[tid] = din[tid];
+    __syncthreads();
+    const double alpha = sD[c], sigma = sS[c];
+    const double nrm = sqrt(fma(alpha, alpha, sigma));
+    if (nrm == 0.0 || !(nrm < __builtin_inf())) {        // the same value in every thread of every workgroup
+      if (g == 0 && tid == 0) *info = (int)(d + 1);
+      return;
+    }
+    double tau = 0.0;
+    beta = alpha;
+    if (sigma != 0.0) {
+      beta = -copysign(nrm, alpha);
+      tau = (beta - alpha) / beta;
+      scale = 1.0 / (alpha - beta);
+    }
+    if (tid < NB) sW[tid] = (tid > c && tid < jb) ? tau * fma(scale, sS[tid], sD[tid]) : 0.0;
+    if (g == 0) {
+      if (tid < NB) spart[0][tid] = tid < c ? fma(scale, sS[tid], sD[tid]) : 0.0;     // V[:, i]' v, i < c
+      __syncthreads();
+      if (tid < NB) {
+        double t = 0.0;
+        if (tid < c) {
+#pragma unroll 8
+          for (int l = tid; l < c; ++l) t = fma(tfac[tid + l * NB], spart[0][l], t);
+          t = -tau * t;
+        } else if (tid == c) t = tau;
+        tfac[tid + c * NB] = t;
+      }
+    }
+    __syncthreads();
+  }
+  T *P = W + j0 * ldw;
+  const int64_t nch = (mf - j0 + NB - 1) / NB;
+  double acc[16];
+#pragma unroll
+  for (int t = 0; t < 16; ++t) acc[t] = 0.0;
+  for (int64_t ch = g; ch < nch; ch += G) {
+    const int64_t r = j0 + ch * NB + lane;
+    const bool in = r < mf;
+    double xr = 0.0, yr = 0.0, val[16];
+    if (c >= 0 && in && r > d) xr = (double)P[r + c * ldw];
+    if (cn >= 0 && in) yr = (double)P[r + cn * ldw];
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      const int j = q * 16 + t;
+      val[t] = (in && j < jb) ? (double)P[r + j * ldw] : 0.0;
+    }
+    __syncthreads();                                     // columns c and c + 1 are read by every wave before their owners write them
+    if (c >= 0 && in && r >= d) {
+      const double vr = r > d ? (double)(T)(xr * scale) : 1.0;
+#pragma unroll
+      for (int t = 0; t < 16; ++t) {
+        const int j = q * 16 + t;
+        if (j >= c && j < jb) {
+          const T x = j > c ? (T)fma(-sW[j], vr, val[t]) : (r > d ? (T)vr : (T)beta);
+          P[r + j * ldw] = x;
+          val[t] = j > c ? (double)x : vr;
+        }
+      }
+      if (cn >= 0) yr = (double)(T)fma(-sW[cn], vr, yr);
+    }
+    if (cn >= 0) {
+      if (in && r > dn) {
+#pragma unroll
+        for (int t = 0; t < 16; ++t) acc[t] = fma(val[t], yr, acc[t]);
+      }
+      if (r == dn) {
+#pragma unroll
+        for (int t = 0; t < 16; ++t) dout[q * 16 + t] = val[t];
+      }
+    }
+  }
+  if (cn >= 0) {
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      const double s = wave_sum(acc[t]);
+      if (lane == 0) pout[(int64_t)g * NB + q * 16 + t] = s;
+    }
+  }
+}
+
+// phase (c), step 1: partial Y = V' C over the rows [k_lo, k_hi) of split blockIdx.y, one 64 x 64 tile of columns of C per
+// blockIdx.x, on the MFMA of the element type. V is the panel with its implicit unit diagonal and zeros above it.
+template <typename T>
+__global__ void __launch_bounds__(kBlock) geqrf_vtc_kernel(const T *__restrict__ V, const T *__restrict__ Cm, int64_t ld, int64_t rows,
+                                                           int jb, int nc, int64_t rs, double *__restrict__ ypart, const int *info) {
+  if (*info != 0) return;
+  __shared__ T sA[SK][SLD], sB[SK][SLD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bn = blockIdx.x * NB;
+  const int64_t k_lo = (int64_t)blockIdx.y * rs, k_hi = k_lo + rs < rows ? k_lo + rs : rows;
+  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
+  using Acc = typename Mfma<T>::Acc;
+  Acc acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[a][b][r] = 0;
+  for (int64_t k0 = k_lo; k0 < k_hi; k0 += SK) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int e = tid + t * kBlock, kb = e & 15, col = e >> 4;
+      const int64_t gk = k0 + kb;
+      T va = T(0);
+      if (gk < k_hi && col < jb) va = gk > col ? V[gk + (int64_t)col * ld] : (gk == col ? T(1) : T(0));
+      sA[kb][col] = va;
+      sB[kb][col] = (gk < k_hi && bn + col < nc) ? Cm[gk + (int64_t)(bn + col) * ld] : T(0);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < SK; kk += 4) {
+      const int kr = kk + (lane >> 4);
+      const T a0 = sA[kr][wm + (lane & 15)], a1 = sA[kr][wm + 16 + (lane & 15)];
+      const T b0 = sB[kr][wn + (lane & 15)], b1 = sB[kr][wn + 16 + (lane & 15)];
+      acc[0][0] = Mfma<T>::run(a0, b0, acc[0][0]);
+      acc[0][1] = Mfma<T>::run(a0, b1, acc[0][1]);
+      acc[1][0] = Mfma<T>::run(a1, b0, acc[1][0]);
+      acc[1][1] = Mfma<T>::run(a1, b1, acc[1][1]);
+    }
+    __syncthreads();
+  }
+  double *out = ypart + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * NB2;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int gi = wm + a * 16 + Mfma<T>::row(lane, r), gj = wn + b * 16 + (lane & 15);
+        out[gj * NB + gi] = (double)acc[a][b][r];
+      }
+}
+
+// step 2: Y = T' (sum of the S partial tiles, in order), f64, stored in the element type for step 3; one workgroup a tile
+template <typename T>
+__global__ void __launch_bounds__(kBlock) geqrf_ty_kernel(const double *__restrict__ ypart, int S, const double *__restrict__ tfac, int jb,
+                                                          T *__restrict__ y2, const int *info) {
+  if (*info != 0) return;
+  __shared__ double sY[NB * (NB + 1)];
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  for (int e = tid; e < NB2; e += kBlock) {
+    double a = 0.0;
+    for (int s = 0; s < S; ++s) a += ypart[((int64_t)s * gridDim.x + blockIdx.x) * NB2 + e];
+    sY[(e >> 6) * (NB + 1) + (e & 63)] = a;
+  }
+  __syncthreads();
+  T *out = y2 + (int64_t)blockIdx.x * NB2;
+  for (int i = q; i < NB; i += 4) {                      // row i of T' Y, the lanes across the columns of the tile
+    double a = 0.0;
+    if (i < jb)
+      for (int l = 0; l <= i; ++l) a = fma(tfac[l + i * NB], sY[lane * (NB + 1) + l], a);
+    out[lane * NB + i] = (T)a;
+  }
+}
+
+// step 3: C -= V Y, the rank-jb update of getrf_gemm_kernel with V's implicit unit diagonal and a rectangular C (rows x nc)
+template <typename T>
+__global__ void __launch_bounds__(kBlock) geqrf_update_kernel(T *__restrict__ Cm, const T *__restrict__ V, const T *__restrict__ y2,
+                                                              int64_t ld, int64_t rows, int jb, int nc, const int *info) {
+  if (*info != 0) return;
+  __shared__ T sA[SK][SLD], sB[SK][SLD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t bm = (int64_t)blockIdx.x * NB;
+  const int bn = blockIdx.y * NB;
+  const T *Yt = y2 + (int64_t)blockIdx.y * NB2;
+  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
+  using Acc = typename Mfma<T>::Acc;
+  Acc acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[a][b][r] = 0;
+  for (int k0 = 0; k0 < jb; k0 += SK) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int e = tid + t * kBlock, i = e & 63, k = e >> 6, kb = e & 15, jn = e >> 4;
+      const int64_t gi = bm + i;
+      const int gk = k0 + k;
+      T va = T(0);
+      if (gi < rows && gk < jb) va = gi > gk ? V[gi + (int64_t)gk * ld] : (gi == gk ? T(1) : T(0));
+      sA[k][i] = va;
+      sB[kb][jn] = k0 + kb < jb ? Yt[jn * NB + k0 + kb] : T(0);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < SK; kk += 4) {
+      const int kr = kk + (lane >> 4);
+      const T a0 = sA[kr][wm + (lane & 15)], a1 = sA[kr][wm + 16 + (lane & 15)];
+      const T b0 = sB[kr][wn + (lane & 15)], b1 = sB[kr][wn + 16 + (lane & 15)];
+      acc[0][0] = Mfma<T>::run(a0, b0, acc[0][0]);
+      acc[0][1] = Mfma<T>::run(a0, b1, acc[0][1]);
+      acc[1][0] = Mfma<T>::run(a1, b0, acc[1][0]);
+      acc[1][1] = Mfma<T>::run(a1, b1, acc[1][1]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int64_t gi = bm + wm + a * 16 + Mfma<T>::row(lane, r);
+        const int gj = bn + wn + b * 16 + (lane & 15);
+        if (gi < rows && gj < nc) {
+          T *p = Cm + gi + (int64_t)gj * ld;
+          *p = *p - acc[a][b][r];
+        }
+      }
+}
+
+// doubles of mxlo_geqrf's scratch: two sets of partial slots and of the diagonal row, the partial tiles of V' C (at most
+// max(512, tiles) of them) and the tiles of T' V' C
+inline int64_t geqrf_scratch(int64_t nf) {
+  const int64_t nb = (nf + NB - 1) / NB;
+  return 2 * (int64_t)QG * NB + 2 * NB + (512 + 2 * nb) * NB2;
+}
+
+template <typename T>
+int32_t geqrf_t(mxlo_ctx *ctx, const T *M, int64_t ldm, int trans, T *W, int64_t ldw, int64_t mf, int64_t nf, double *tfac, double *dinv,
+                double *fwork, int *info_dev) {
+  const int64_t nb = (nf + NB - 1) / NB;
+  MXLO_HIP(hipMemsetAsync(info_dev, 0, sizeof(int), ctx->stream));
+  hipLaunchKernelGGL((qr_copy_kernel<T>), dim3((unsigned)((mf + NB - 1) / NB), (unsigned)nb), dim3(kBlock), 0, ctx->stream, W, ldw, M, ldm,
+                     trans, mf, nf);
+  MXLO_LAUNCH_CHECK();
+  double *pb[2] = {fwork, fwork + (int64_t)QG * NB}, *db[2] = {fwork + 2 * (int64_t)QG * NB, fwork + 2 * (int64_t)QG * NB + NB};
+  double *ypart = fwork + 2 * (int64_t)QG * NB + 2 * NB;
+  for (int64_t k = 0; k < nb; ++k) {
+    const int64_t j0 = k * NB, jb = nf - j0 < NB ? nf - j0 : NB, j1 = j0 + jb, nc = nf - j1, rows = mf - j0;
+    const unsigned G = (unsigned)qr_grid(rows);
+    for (int c = -1; c < (int)jb; ++c) {                 // launch c reads the slots c & 1 and leaves the others for launch c + 1
+      hipLaunchKernelGGL((geqrf_panel_kernel<T>), dim3(G), dim3(kBlock), 0, ctx->stream, W, ldw, mf, j0, (int)jb, c, tfac + k * NB2,
+                         (const double *)pb[c & 1], (const double *)db[c & 1], pb[(c + 1) & 1], db[(c + 1) & 1], info_dev);
+      MXLO_LAUNCH_CHECK();
+    }
+    if (nc <= 0) break;
+    const int64_t tiles = (nc + NB - 1) / NB, rch = (rows + NB - 1) / NB;
+    int64_t S = 512 / tiles;
+    S = S < 1 ? 1 : (S > rch ? rch : S);
+    const int64_t rs = ((rows + S - 1) / S + SK - 1) / SK * SK;
+    T *y2 = (T *)(ypart + S * tiles * NB2);
+    const T *V = W + j0 + j0 * ldw;
+    T *Cm = W + j0 + j1 * ldw;
+    hipLaunchKernelGGL((geqrf_vtc_kernel<T>), dim3((unsigned)tiles, (unsigned)S), dim3(kBlock), 0, ctx->stream, V, (const T *)Cm, ldw, rows,
+                       (int)jb, (int)nc, rs, ypart, (const int *)info_dev);
+    MXLO_LAUNCH_CHECK();
+    hipLaunchKernelGGL((geqrf_ty_kernel<T>), dim3((unsigned)tiles), dim3(kBlock), 0, ctx->stream, (const double *)ypart, (int)S,
+                       (const double *)(tfac + k * NB2), (int)jb, y2, (const int *)info_dev);
+    MXLO_LAUNCH_CHECK();
+    hipLaunchKernelGGL((geqrf_update_kernel<T>), dim3((unsigned)rch, (unsigned)tiles), dim3(kBlock), 0, ctx->stream, Cm, V, (const T *)y2,
+                       ldw, rows, (int)jb, (int)nc, (const int *)info_dev);
+    MXLO_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL((tri_prepare_kernel<T>), dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream, (const T *)W, ldw, nf, 1, dinv);   // phase (b)
+  MXLO_LAUNCH_CHECK();
+  return MXLO_OK;
+}
+
+// One launch of the reflector chain of an apply. It (1) adds up the partial dots d = V_p' z the launch before left and takes
+// w = T_p' d (Q') or T_p d (Q), (2) z -= V_p w on its rows, (3) leaves the partial dots of the new z with V_n. The first launch
+// of a chain has no block p and fills z (load 1: from v; 2: z below row nf is zero), the last has no block n and, with epi,
+// writes res = alpha z + beta res instead of z. The panels are streamed; a panel is read by the launch that takes its dots and again
+// by the next one, which applies it.
+struct QrArgs {
+  const void *W;
+  int64_t ld, mf, nf;
+  double *z;
+  const void *v;
+  int load;
+  int64_t jp, jn;        // first column of the block applied / dotted against
+  int jbp, jbn;          // their widths; 0: none
+  const double *tp;      // T of block p, applied transposed if tp_trans
+  int tp_trans;
+  const double *pin;
+  double *pout;
+  int epi;
+  void *res;
+  double alpha, beta;
+};
+
+template <typename T, bool BETA0>
+__global__ void __launch_bounds__(kBlock) qr_reflect_kernel(QrArgs a) {
+  __shared__ double sd[NB], sw[NB], spart[4][NB], sT[NB * (NB + 1)];
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int g = blockIdx.x, G = gridDim.x;
+  const T *W = (const T *)a.W;
+  if (a.jbp) {
+    for (int e = tid; e < NB2; e += kBlock) sT[(e >> 6) * (NB + 1) + (e & 63)] = a.tp[e];      // T[i, l] at sT[l * (NB + 1) + i]
+    qr_reduce(a.pin, G, sd, spart, lane, q);
+    double part = 0.0;                                   // T is upper triangular and zero outside its jbp columns: all 64 terms
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      const int l = q * 16 + t;
+      part = fma(a.tp_trans ? sT[lane * (NB + 1) + l] : sT[l * (NB + 1) + lane], sd[l], part);
+    }
+    spart[q][lane] = part;
+    __syncthreads();
+    if (q == 0) sw[lane] = (spart[0][lane] + spart[1][lane]) + (spart[2][lane] + spart[3][lane]);
+    __syncthreads();
+  }
+  double acc[16];
+#pragma unroll
+  for (int t = 0; t < 16; ++t) acc[t] = 0.0;
+  const int64_t nch = (a.mf + NB - 1) / NB;
+  for (int64_t ch = g; ch < nch; ch += G) {
+    const int64_t r = ch * NB + lane;
+    const bool in = r < a.mf;
+    double zr = 0.0;
+    if (in) zr = a.load == 1 ? (double)((const T *)a.v)[r] : ((a.load == 2 && r >= a.nf) ? 0.0 : a.z[r]);
+    if (a.jbp) {
+      double part = 0.0;
+#pragma unroll
+      for (int t = 0; t < 16; ++t) {
+        const int c = q * 16 + t;
+        const int64_t col = a.jp + c;
+        if (c < a.jbp && in && r >= col) part = fma(r > col ? ld_stream(W + r + col * a.ld) : 1.0, sw[c], part);
+      }
+      spart[q][lane] = part;
+      __syncthreads();
+      zr -= (spart[0][lane] + spart[1][lane]) + (spart[2][lane] + spart[3][lane]);
+      __syncthreads();
+    }
+    if (q == 0 && in) {
+      if (a.epi) store_res<T, BETA0>((T *)a.res, r, zr, a.alpha, a.beta);
+      else a.z[r] = zr;
+    }
+    if (a.jbn) {
+#pragma unroll
+      for (int t = 0; t < 16; ++t) {
+        const int c = q * 16 + t;
+        const int64_t col = a.jn + c;
+        if (c < a.jbn && in && r >= col) acc[t] = fma(r > col ? ld_stream(W + r + col * a.ld) : 1.0, zr, acc[t]);
+      }
+    }
+  }
+  if (a.jbn) {
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      const double s = wave_sum(acc[t]);
+      if (lane == 0) a.pout[(int64_t)g * NB + q * 16 + t] = s;
+    }
+  }
+}
+
+template <typename T>
+int32_t launch_reflect(mxlo_ctx *ctx, const QrArgs &a) {
+  const unsigned G = (unsigned)qr_grid(a.mf);
+  if (a.beta == 0.0) hipLaunchKernelGGL((qr_reflect_kernel<T, true>), dim3(G), dim3(kBlock), 0, ctx->stream, a);
+  else hipLaunchKernelGGL((qr_reflect_kernel<T, false>), dim3(G), dim3(kBlock), 0, ctx->stream, a);
+  MXLO_LAUNCH_CHECK();
+  return MXLO_OK;
+}
+
+// N: x = inv(R) (Q' v)[0:nf] — nb + 1 reflector launches, blocks ascending, then the descending sweep with R, which carries the
+// epilogue. T: y = Q [inv(R') u; 0] — the ascending sweep with R' into z, then nb + 1 reflector launches, blocks descending, the
+// last one with the epilogue over all mf entries. 2 nb + 1 launches either way. work: z (mf), then two sets of QG x NB slots.
+template <typename T>
+int32_t qr_mul_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t mf, int64_t nf, const double *tfac, const double *dinv,
+                 double *work, const T *v, bool trans, double alpha, double beta) {
+  const int64_t nb = (nf + NB - 1) / NB;
+  double *pb[2] = {work + mf, work + mf + (int64_t)QG * NB};
+  QrArgs a{};
+  a.W = W; a.ld = ld; a.mf = mf; a.nf = nf; a.z = work; a.res = res; a.alpha = alpha; a.beta = beta; a.tp_trans = trans ? 0 : 1;
+  if (trans) MXLO_TRY(sweep<T>(ctx, W, ld, nf, true, true, dinv, work, v, true, false, false, res, alpha, beta));
+  for (int64_t i = 0; i <= nb; ++i) {                    // launch i reads the slots (i + 1) & 1 and leaves the slots i & 1
+    const int64_t kp = trans ? nb - i : i - 1, kn = trans ? nb - 1 - i : i;
+    a.v = (!trans && i == 0) ? v : nullptr;
+    a.load = i == 0 ? (trans ? 2 : 1) : 0;
+    a.jbp = a.jbn = 0;
+    if (i > 0) { a.jp = kp * NB; a.jbp = (int)(nf - a.jp < NB ? nf - a.jp : NB); a.tp = tfac + kp * NB2; }
+    if (i < nb) { a.jn = kn * NB; a.jbn = (int)(nf - a.jn < NB ? nf - a.jn : NB); }
+    a.pin = pb[(i + 1) & 1]; a.pout = pb[i & 1];
+    a.epi = trans && i == nb;
+    MXLO_TRY(launch_reflect<T>(ctx, a));
+  }
+  if (trans) return MXLO_OK;
+  return sweep<T>(ctx, W, ld, nf, true, false, dinv, work, (const T *)nullptr, true, false, true, res, alpha, beta);
+}
+
+}  // namespace
+
+MXLO_API int32_t mxlo_geqrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_trans, void *W, int64_t ldw, int64_t mf,
+                            int64_t nf, double *tfac, double *dinv, double *scratch, int64_t scratch_len, int32_t *info_dev,
+                            int32_t *info) {
+  const char *what = "mxlo_geqrf";
+  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
+  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
+  MXLO_REQUIRE(nf >= 1 && mf >= nf && ldw >= mf, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld (1 <= nf <= mf), ldw = %lld", what, (long long)mf,
+               (long long)nf, (long long)ldw);
+  MXLO_REQUIRE(mf < (1LL << 31) - NB && (nf + NB - 1) / NB <= 65535, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld is too large", what,
+               (long long)mf, (long long)nf);
+  MXLO_REQUIRE(M && W && tfac && dinv && scratch && info_dev && info, MXLO_EINVAL, "%s: null operand", what);
+  *info = 0;
+  const int64_t mr = m_trans ? nf : mf, mc = m_trans ? mf : nf;       // M as it is stored: mr x mc, column-major
+  MXLO_REQUIRE(ldm >= mr, MXLO_ESHAPE, "%s: ldm = %lld < %lld", what, (long long)ldm, (long long)mr);
+  MXLO_REQUIRE(scratch_len >= geqrf_scratch(nf), MXLO_ESHAPE, "%s: scratch of %lld doubles, %lld needed", what, (long long)scratch_len,
+               (long long)geqrf_scratch(nf));
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4, nb = (nf + NB - 1) / NB;
+  const std::pair<const void *, int64_t> bufs[] = {{M, ((mc - 1) * ldm + mr) * es}, {W, ((nf - 1) * ldw + mf) * es}, {tfac, nb * NB2 * 8},
+                                                   {dinv, nb * NB2 * 8},           {scratch, scratch_len * 8},      {info_dev, 4}};
+  for (size_t x = 0; x < 6; ++x)
+    for (size_t y = x + 1; y < 6; ++y)
+      MXLO_REQUIRE(!bytes_overlap(bufs[x].first, bufs[x].second, bufs[y].first, bufs[y].second), MXLO_EINVAL,
+                   "%s: M, the factor, the T factors, the block inverses, the scratch and the info word overlap", what);
+  MXLO_REQUIRE(!ctx->capturing, MXLO_ESTATE, "%s: reads its info word back, which a graph capture cannot hold", what);
+  MXLO_DEVICE_GUARD(ctx);
+  if (dtype == MXLO_F64)
+    MXLO_TRY(geqrf_t<double>(ctx, (const double *)M, ldm, m_trans ? 1 : 0, (double *)W, ldw, mf, nf, tfac, dinv, scratch, info_dev));
+  else MXLO_TRY(geqrf_t<float>(ctx, (const float *)M, ldm, m_trans ? 1 : 0, (float *)W, ldw, mf, nf, tfac, dinv, scratch, info_dev));
+  MXLO_HIP(hipMemcpyAsync(info, info_dev, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MXLO_HIP(hipStreamSynchronize(ctx->stream));
+  return MXLO_OK;
+}
+
+MXLO_API int32_t mxlo_qr_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t mf, int64_t nf,
+                             const double *tfac, const double *dinv, double *work, const void *v, int32_t op_mode, double alpha,
+                             double beta) {
+  const char *what = "mxlo_qr_mul";
+  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
+  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
+  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "%s: op_mode %d", what, op_mode);
+  MXLO_REQUIRE(nf >= 1 && mf >= nf && ldw >= mf && mf < (1LL << 31) - NB, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld (1 <= nf <= mf), ldw = %lld",
+               what, (long long)mf, (long long)nf, (long long)ldw);
+  MXLO_REQUIRE(res && W && tfac && dinv && work && v, MXLO_EINVAL, "%s: null operand", what);
+  const bool tr = op_mode != MXLO_OP_N;
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4, nb = (nf + NB - 1) / NB;
+  const int64_t rb = (tr ? mf : nf) * es, vb = (tr ? nf : mf) * es;
+  MXLO_REQUIRE((res == v && mf == nf) || !bytes_overlap(res, rb, v, vb), MXLO_EINVAL,
+               "%s: res overlaps v without being v (only mul!(x, op, x) of a square operator is defined)", what);
+  const std::pair<const void *, int64_t> own[] = {{W, ((nf - 1) * ldw + mf) * es}, {tfac, nb * NB2 * 8}, {dinv, nb * NB2 * 8},
+                                                  {work, (mf + 2 * (int64_t)QG * NB) * 8}};
+  for (const auto &[p, pb] : own)
+    MXLO_REQUIRE(!bytes_overlap(res, rb, p, pb) && !bytes_overlap(v, vb, p, pb), MXLO_EINVAL,
+                 "%s: res / v overlap the factor, the T factors, the block inverses or the work vector", what);
+  MXLO_DEVICE_GUARD(ctx);
+  if (dtype == MXLO_F64)
+    return qr_mul_t<double>(ctx, (double *)res, (const double *)W, ldw, mf, nf, tfac, dinv, work, (const double *)v, tr, alpha, beta);
+  return qr_mul_t<float>(ctx, (float *)res, (const float *)W, ldw, mf, nf, tfac, dinv, work, (const float *)v, tr, alpha, beta);
+}

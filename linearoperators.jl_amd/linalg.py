@@ -8,7 +8,8 @@ Real Float64 / Float32 only. `mul!` on an n x k matrix (`F \\ V`, src/operations
 bit-identical to its vector apply. The inverse of a general dense matrix is `opLU` (partially pivoted LU); `opInverse` itself
 stays triangular-only. A pivoted (Bunch–Kaufman) or sparse LDLᵀ are not provided. `refine=r` on the three
 factorisation operators adds r steps of iterative refinement to every apply (`mxlo_*_mul_refine`), with the residual and the
-iterate in Float64 and a snapshot of M the operator keeps.
+iterate in Float64 and a snapshot of M the operator keeps. `opQR` is the rectangular `M \\ v`: least-squares and minimum-norm
+solves through an unpivoted Householder QR (`mxlo_geqrf`, `mxlo_qr_mul`).
 """
 from __future__ import annotations
 
@@ -428,3 +429,89 @@ def opLU(M: torch.Tensor, symm: bool = False, herm: bool = False, refine: int = 
 
 
 opLU.__doc__ += _REFINE_DOC
+
+
+QR_SLOTS = 512        # most workgroups of a pass over the rows (QG of csrc/linalg.hip): partial slots per column
+
+
+def qr_launches(nf: int) -> int:
+    """Launches of ONE opQR apply, in either mode, for a factor with nf columns: ⌈nf/64⌉ + 1 reflector launches and the
+    ⌈nf/64⌉ of the sweep with R. It does not depend on the number of rows."""
+    return 2 * ((int(nf) + BLOCK - 1) // BLOCK) + 1
+
+
+def _check_rect(A, name: str):
+    """opQR's checks that need no device, in the order the docstring states. Rectangular is not a shape mismatch."""
+    if not isinstance(A, torch.Tensor) or A.dim() != 2:
+        raise TypeError(f"{name}: A must be a 2-D torch.Tensor on the GPU")
+    m, k = A.shape
+    if m == 0 or k == 0:
+        raise LinearOperatorException(f"{name}: a {m} x {k} matrix has no QR solve")
+    if A.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"{name}: real Float64 / Float32 only, got {A.dtype} (complex and half factorisations are not instantiated)")
+    if not A.is_cuda:
+        raise RuntimeError(f"{name}: A lives on {A.device}: the MI355X path has no CPU fallback")
+    return m, k
+
+
+def opQR(A: torch.Tensor):
+    """opQR(A): the pseudo-inverse A⁺ of a full-rank dense m x k matrix, a k x m operator — what `opInverse(M)` = `M \\ v` of
+    src/linalg.jl:27-32 is for a rectangular M: Julia's QR solve. prod!: res = α (A⁺ v) + β res, the least-squares solution
+    of A x ≈ v for m >= k and the minimum-norm solution of A x = v for m < k; tprod! = ctprod!: res = α ((A⁺)ᵀ u) + β res, the
+    same pair of problems for Aᵀ. With β == 0 res is not read. Never the normal equations: the condition number is not squared.
+
+    ONE factorisation, computed here, on the device, of the TALL orientation F (F = A if m >= k, else Aᵀ; mf x nf): F = Q R by
+    unpivoted Householder reflections in block columns of 64 with compact-WY factors (`mxlo_geqrf`), into storage the
+    operator owns. A is not modified and a later change of A is not seen. A row-major wide A is the column-major tall Aᵀ
+    and is read as it lies, as a column-major tall A is; a column-major wide A (or row-major tall A) is transposed once while
+    it is copied; any other striding is copied first. `op._tall`: was A itself factored? `op._factor` = (W, T, dinv, work):
+    W (mf x nf, column-major) holds R on and above its diagonal and the reflector vectors below it, LAPACK's layout.
+
+    A column of F whose norm from the diagonal down is exactly zero or not finite raises `SingularException(info)` with
+    its 1-based index in F, here, at construction; a zero sub-column below a non-zero diagonal entry is legitimate (τ = 0).
+    The norms are taken without rescaling: data whose squares overflow or underflow Float64 is outside what this handles.
+
+    An apply is `qr_launches(nf)` = 2⌈nf/64⌉ + 1 launches, whatever mf is, and nothing else: it allocates nothing, never
+    synchronises, can be captured (`capture_mul`) and is bit-reproducible (every sum in a fixed order in Float64). res may be
+    v when m == k. Matrix operands go column by column. NOT provided: a block form, `refine`, column pivoting
+    or any rank-revealing form (a rank-deficient A that escapes the exact test above gives a meaningless answer), complex
+    element types, Julia glue."""
+    m, k = _check_rect(A, "opQR")
+    T = A.dtype
+    tall = m >= k
+    mf, nf = (m, k) if tall else (k, m)
+    St, tr = _stored_colmajor(A)                        # tr: St is the column-major storage of Aᵀ
+    m_trans = tall == tr                                # St holds Fᵀ: transpose while copying
+    ldm = St.stride(1) if St.shape[1] > 1 else max(1, St.shape[0])
+    ctx = get_ctx(A.device)
+    W = torch.empty((nf, mf), dtype=T, device=A.device).t()           # column-major mf x nf, ld = mf
+    ldw = mf
+    nblk = (nf + BLOCK - 1) // BLOCK
+    tfac = torch.zeros(nblk * BLOCK * BLOCK, dtype=torch.float64, device=A.device)
+    dinv = torch.empty(nblk * BLOCK * BLOCK, dtype=torch.float64, device=A.device)
+    work = torch.empty(mf + 2 * QR_SLOTS * BLOCK, dtype=torch.float64, device=A.device)     # z, then two sets of partial slots
+    nscratch = 2 * (QR_SLOTS * BLOCK + BLOCK) + (512 + 2 * nblk) * BLOCK * BLOCK
+    scratch = torch.empty(nscratch, dtype=torch.float64, device=A.device)                   # needed by the factorisation only
+    info_dev = torch.zeros(1, dtype=torch.int32, device=A.device)
+    info = C.c_int32(0)
+    code = dtype_code(T)
+    _lib.call("mxlo_geqrf", ctx.handle, code, St.data_ptr(), ldm, 1 if m_trans else 0, W.data_ptr(), ldw, mf, nf, tfac.data_ptr(),
+              dinv.data_ptr(), scratch.data_ptr(), nscratch, info_dev.data_ptr(), C.byref(info))
+    del scratch
+    if info.value != 0:
+        raise SingularException(info.value)
+    pW, pT, pD, pZ = W.data_ptr(), tfac.data_ptr(), dinv.data_ptr(), work.data_ptr()
+
+    def solve(res, v, a, b, mode):                      # mulFact!(res, qr(F), v, α, β) — src/linalg.jl:3-9
+        _check_operands(res, v, T)
+        _lib.call("mxlo_qr_mul", ctx_of(res).handle, code, res.data_ptr(), pW, ldw, mf, nf, pT, pD, pZ, v.data_ptr(), mode, float(a),
+                  float(b))
+
+    fwd, bwd = (_lib.OP_N, _lib.OP_T) if tall else (_lib.OP_T, _lib.OP_N)
+    prod = columnwise(lambda res, v, a, b: solve(res, v, a, b, fwd))
+    tprod = columnwise(lambda res, u, a, b: solve(res, u, a, b, bwd))
+    op = LinearOperator(T, k, m, False, False, prod, tprod, tprod, S=Storage(T, A.device))
+    op._deps = (W,)
+    op._tall = tall
+    op._factor = (W, tfac, dinv, work)                  # owned storage (kept alive with the operator)
+    return op

@@ -28,6 +28,14 @@ the expectation to hold it against is (r + 1) + r × (residual time / plain appl
 the same shapes on another commit come from `--block --mul-only` (its k = 1 and k = 8 rows), which is how a baseline is taken.
 
     python tools/bench_linalg.py --refine [n ...] > profiles/linalg_refine.txt
+
+--qr: opQR on a tall-thin (10⁶ x 128) and a square (8192²) Gaussian matrix (the square one with √n on its diagonal), both
+precisions: the factorisation (construction, allocations and the one synchronisation included) and the apply in both modes —
+time, spread, launches, and the fraction of the 8 TB/s peak by the byte model (mf·nf + nf²/2)·sizeof(T) — and, for comparison,
+what a caller had to do before: opCholesky(AᵀA) (the Gram matrix by a torch GEMM) and per apply the dense Aᵀv plus the
+Cholesky apply. Other shapes: arguments of the form MFxNF.
+
+    python tools/bench_linalg.py --qr [MFxNF ...] > profiles/linalg_qr.txt
 """
 import ctypes as C
 import os
@@ -48,7 +56,7 @@ PEAK = 8000.0          # GB/s
 BLOCK = "--block" in sys.argv
 MUL_ONLY = "--mul-only" in sys.argv
 REFINE = "--refine" in sys.argv
-NS = [int(a) for a in sys.argv[1:] if not a.startswith("--")] or ([2048, 8192, 16384] if BLOCK or REFINE else [1024, 4096, 16384])
+NS = [int(a) for a in sys.argv[1:] if not a.startswith("--") and "x" not in a] or ([2048, 8192, 16384] if BLOCK or REFINE else [1024, 4096, 16384])
 
 
 def timeit(fn, reps):
@@ -193,6 +201,56 @@ def refine_legs():
             torch.cuda.empty_cache()
 
 
+def qr_legs():
+    """opQR: see the module docstring"""
+    print(f"# {torch.cuda.get_device_name(0)}; opQR; ms per call, median of 3 event-timed windows, spread = (max - min) / median")
+    print(f"# bytes of an apply: (mf nf + nf^2 / 2) sizeof(T); peak {PEAK:.0f} GB/s. normal equations: opCholesky(A'A) built from a "
+          f"torch GEMM, apply = dense A'v (LinearOperatorFromMatrix) + opCholesky apply")
+    print(f"{'case':44s} {'mf':>8s} {'nf':>5s} {'ms':>10s} {'spread':>6s} {'launch':>6s} {'GB/s':>8s} {'%peak':>6s}", flush=True)
+    shapes = [tuple(int(x) for x in a.split("x")) for a in sys.argv[1:] if "x" in a] or [(1000000, 128), (8192, 8192)]
+    for dtype, tag in ((torch.float64, "f64"), (torch.float32, "f32")):
+        es = 8 if dtype is torch.float64 else 4
+        for mf, nf in shapes:
+            gen = torch.Generator(device=dev).manual_seed(mf + nf)
+            A = torch.randn(nf, mf, dtype=dtype, device=dev, generator=gen).t()           # column-major mf x nf
+            if mf == nf:
+                A = A + (nf ** 0.5) * torch.eye(nf, dtype=dtype, device=dev)
+            v = torch.randn(mf, dtype=dtype, device=dev, generator=gen)
+            u = torch.randn(nf, dtype=dtype, device=dev, generator=gen)
+            x, y = torch.empty_like(u), torch.empty_like(v)
+            nbytes = (mf * nf + nf * nf // 2) * es
+            reps = 10 if mf * nf <= 2 ** 27 else 5
+
+            def row(name, fn, reps, nbytes, nl):
+                ms = timeit(fn, reps)
+                gbs = nbytes / ms / 1e6 if nbytes else 0.0
+                print(f"{name + ' ' + tag:44s} {mf:8d} {nf:5d} {ms:10.4f} {100 * timeit.spread:5.1f}% {nl:6d} {gbs:8.1f} {100 * gbs / PEAK:6.2f}",
+                      flush=True)
+
+            row("opQR(A) factorisation", lambda: lo.opQR(A), 2, 0, 0)
+            op = lo.opQR(A)
+            row("opQR apply (least squares)", lambda: lo.mul(x, op, v, 1.0, 0.0), reps, nbytes, launches(lambda: lo.mul(x, op, v, 1.0, 0.0)))
+            row("transpose(opQR) apply (minimum norm)", lambda: lo.mul(y, op.T, u, 1.0, 0.0), reps, nbytes,
+                launches(lambda: lo.mul(y, op.T, u, 1.0, 0.0)))
+            del op
+            torch.cuda.empty_cache()
+            dense = lo.LinearOperatorFromMatrix(A)
+            t = torch.empty_like(u)
+            row("normal equations: A'A + opCholesky", lambda: lo.opCholesky((A.t() @ A).t().contiguous().t()), 2, 0, 0)
+            ch = lo.opCholesky((A.t() @ A).t().contiguous().t())
+
+            def normal():
+                lo.mul(t, dense.T, v, 1.0, 0.0)
+                lo.mul(x, ch, t, 1.0, 0.0)
+
+            row("normal equations: A'v + opCholesky apply", normal, reps, (mf * nf + nf * nf) * es, launches(normal))
+            del ch, dense, A
+            torch.cuda.empty_cache()
+
+
+if "--qr" in sys.argv:
+    qr_legs()
+    sys.exit(0)
 if BLOCK:
     block_legs()
     sys.exit(0)
