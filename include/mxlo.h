@@ -987,6 +987,26 @@ int32_t mxlo_geqrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int
  * W, tfac, dinv or work, is MXLO_EINVAL before anything is launched. With beta == 0 res is not read. */
 int32_t mxlo_qr_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t mf, int64_t nf, const double *tfac,
                     const double *dinv, double *work, const void *v, int32_t op_mode, double alpha, double beta);
+/* mxlo_qr_mul on k columns, the operand convention of the other block entry points. MXLO_OP_N: V is mf x k (ldv >= mf), res
+ * nf x k (ldr >= nf); MXLO_OP_T / MXLO_OP_C: V is nf x k, res mf x k; both column-major, a smaller leading dimension is
+ * MXLO_ESHAPE. The columns go through the chain of ONE vector apply in groups of up to 8: ceil(k/8) (2 ceil(nf/64) + 1)
+ * launches, the reflector launches on the vector apply's grid (at most 512 workgroups, here of 1024 threads) with the same two
+ * alternating sets of partial slots per column, the sweep with R in its block form. Per chunk of 64 rows every element of the
+ * panel applied and of the panel dotted against is loaded once and used for all columns of the group, and the barriers are paid
+ * once. Column j of the result equals mxlo_qr_mul on column j BIT FOR BIT, for every k and every position in a group.
+ * Bytes per group of 8: the factor's (2 mf nf - nf^2 / 2) sizeof(T) as in the vector apply — each panel is still streamed by
+ * two launches —, next to O((mf + nf) k) for V, res and the work matrices; tools/bench_linalg.py rates a block apply by the
+ * one-read model, (mf nf + nf^2 / 2) sizeof(T) per group of 8 plus the operands.
+ * work: 8 (mf + nf + 2 * 512 * 64) doubles, whatever k is — z (mf x 8, column stride mf), two sets of 512 x 64 slots for each
+ * of 8 columns, then the nf x 8 matrix of the sweep (column stride nf). A buffer of this size serves mxlo_qr_mul as well.
+ * A group with fewer than 8 columns reads and writes its own columns only; rows past an operand's height and columns >= k are
+ * never touched; with beta == 0 res is not read. k == 0: MXLO_OK, nothing is launched. res == V is allowed only when
+ * mf == nf, with the same pointer AND the same leading dimension (a group's columns are read completely by its first launch
+ * and written only by its last); any other overlap of res and V, or of either with W, tfac, dinv or work, is MXLO_EINVAL
+ * before anything is launched. No allocation, copy or synchronisation: capturable. */
+int32_t mxlo_qr_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf, int64_t nf,
+                          const double *tfac, const double *dinv, double *work, const void *V, int64_t ldv, int64_t k,
+                          int32_t op_mode, double alpha, double beta);
 
 #ifdef __cplusplus
 }

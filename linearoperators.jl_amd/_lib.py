@@ -204,6 +204,7 @@ _PROTOS = {
     # opQR: (M, ldm, m_trans), (W, ldw, mf, nf), tfac, dinv, (scratch, scratch_len), info_dev, info / the apply with op_mode
     "mxlo_geqrf": [_vp, _i32, _vp, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, C.POINTER(_i32)],
     "mxlo_qr_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl],
+    "mxlo_qr_mul_block": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _dbl, _dbl],
 }
 
 

@@ -1702,8 +1702,8 @@ inline int qr_grid(int64_t rows) {
   return (int)(ch < 1 ? 1 : (ch < QG ? ch : QG));
 }
 
-// s[c] = sum over g < G of part[g * NB + c]: four strided quarters, then (p0 + p1) + (p2 + p3)
-__device__ __forceinline__ void qr_reduce(const double *__restrict__ part, int G, double *s, double (*spart)[NB], int lane, int q) {
+// quarter q of the sum below: part[g * NB + lane] over g = q, q + 4, .. < G, in that order
+__device__ __forceinline__ double qr_quarter(const double *__restrict__ part, int G, int lane, int q) {
   double acc = 0.0;
   int g = q;
   for (; g + 28 < G; g += 32) {                          // eight independent loads in flight, added in the order of the plain loop
@@ -1714,7 +1714,12 @@ __device__ __forceinline__ void qr_reduce(const double *__restrict__ part, int G
     for (int t = 0; t < 8; ++t) acc += p[t];
   }
   for (; g < G; g += 4) acc += part[(int64_t)g * NB + lane];
-  spart[q][lane] = acc;
+  return acc;
+}
+
+// s[c] = sum over g < G of part[g * NB + c]: four strided quarters, then (p0 + p1) + (p2 + p3)
+__device__ __forceinline__ void qr_reduce(const double *__restrict__ part, int G, double *s, double (*spart)[NB], int lane, int q) {
+  spart[q][lane] = qr_quarter(part, G, lane, q);
   __syncthreads();
   if (q == 0) s[lane] = (spart[0][lane] + spart[1][lane]) + (spart[2][lane] + spart[3][lane]);
   __syncthreads();
@@ -2050,6 +2055,10 @@ struct QrArgs {
   int epi;
   void *res;
   double alpha, beta;
+  int kb;                // block form (qr_reflect_block_kernel): the group's right-hand sides, 1 .. KB; 0: the vector kernel. v and
+  int64_t ldr, ldv;      // res are then matrices with these leading dimensions, z is mf x kb with column stride mf, and right-hand
+  double *zc;            // side j has its partial slots at pin / pout + j QG NB. zc: the sweep's compact nf x kb matrix (column stride
+  int zc_out;            // nf), which load 2 reads rows < nf from and which the launch with zc_out writes them to instead of z
 };
 
 template <typename T, bool BETA0>
@@ -2151,6 +2160,180 @@ int32_t qr_mul_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t mf, int6
   return sweep<T>(ctx, W, ld, nf, true, false, dinv, work, (const T *)nullptr, true, false, true, res, alpha, beta);
 }
 
+// qr_reflect_kernel carrying a group of kb <= KB right-hand sides, in a workgroup of 16 waves. Per right-hand side the
+// operations and their order are the vector kernel's (qr_quarter and (p0 + p1) + (p2 + p3) for the slots, the four 16-term fma
+// chains for w = T d and for z -= V w, one fma chain per (row, column) over the workgroup's chunks for the new dots, then
+// wave_sum with the rows in the lanes), so column j is the vector apply of column j bit for bit. What is shared: every element
+// of the chunk of V_p and of V_n is loaded from memory ONCE, by thread (row = lane, columns 4 wv .. 4 wv + 3), all at the top of
+// the chunk — the chunk of V_p into LDS, that of V_n into four registers —, and the barriers of a chunk are paid once.
+//   update (and the prologue): wave wv holds quarter q = wv & 3 of the right-hand sides 2 (wv >> 2), + 1; it reads V_p from LDS.
+//   dots: thread (lane, wv) holds its 4 columns x KB right-hand sides: 32 accumulators, where 16 columns x KB would be 128.
+//   z: wave j < kb holds z of right-hand side j for the chunk's rows and passes it to the dots through LDS.
+constexpr int QBT = 1024;            // threads of qr_reflect_block_kernel
+
+template <typename T, bool BETA0>
+__global__ void __launch_bounds__(QBT) qr_reflect_block_kernel(QrArgs a) {
+  __shared__ double sTV[NB * (NB + 1)];                  // the prologue's T, as the vector kernel lays it out; then the chunk of V_p [c][row]
+  __shared__ double sd[KB][NB], sw[NB][KB], spart[KB][4][NB], sz[KB][NB];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);      // the same in a whole wave: column and right-hand-side indices stay scalar
+  const int q = wv & 3, j0 = (wv >> 2) * 2;
+  const int g = blockIdx.x, G = gridDim.x, kb = a.kb;
+  const T *W = (const T *)a.W;
+  const int64_t slots = (int64_t)QG * NB;
+  if (a.jbp) {
+    for (int e = tid; e < NB2; e += QBT) sTV[(e >> 6) * (NB + 1) + (e & 63)] = a.tp[e];      // T[i, l] at sTV[l * (NB + 1) + i]
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj)
+      if (j0 + jj < kb) spart[j0 + jj][q][lane] = qr_quarter(a.pin + (j0 + jj) * slots, G, lane, q);
+    __syncthreads();
+    if (wv < kb) sd[wv][lane] = (spart[wv][0][lane] + spart[wv][1][lane]) + (spart[wv][2][lane] + spart[wv][3][lane]);
+    __syncthreads();
+    double part[2] = {0.0, 0.0};
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      const int l = q * 16 + t;
+      const double tv = a.tp_trans ? sTV[lane * (NB + 1) + l] : sTV[l * (NB + 1) + lane];
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj)
+        if (j0 + jj < kb) part[jj] = fma(tv, sd[j0 + jj][l], part[jj]);
+    }
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj)
+      if (j0 + jj < kb) spart[j0 + jj][q][lane] = part[jj];
+    __syncthreads();
+    if (wv < kb) sw[lane][wv] = (spart[wv][0][lane] + spart[wv][1][lane]) + (spart[wv][2][lane] + spart[wv][3][lane]);
+    __syncthreads();                                     // sTV is free for the chunks from here
+  }
+  double acc[4][KB];
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+#pragma unroll
+    for (int j = 0; j < KB; ++j) acc[u][j] = 0.0;
+  const int64_t nch = (a.mf + NB - 1) / NB;
+  for (int64_t ch = g; ch < nch; ch += G) {
+    const int64_t r = ch * NB + lane;
+    const bool in = r < a.mf;
+    double zr = 0.0;
+    if (wv < kb && in) {
+      if (a.load == 1) zr = (double)((const T *)a.v)[r + wv * a.ldv];
+      else if (a.load == 2) zr = r < a.nf ? a.zc[r + wv * a.nf] : 0.0;
+      else zr = a.z[r + wv * a.mf];
+    }
+    double vn[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int c = wv * 4 + u;
+      const int64_t col = a.jn + c;
+      vn[u] = (c < a.jbn && in && r > col) ? ld_stream(W + r + col * a.ld) : 1.0;
+    }
+    if (a.jbp) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int c = wv * 4 + u;
+        const int64_t col = a.jp + c;
+        sTV[c * NB + lane] = (c < a.jbp && in && r > col) ? ld_stream(W + r + col * a.ld) : 1.0;
+      }
+      __syncthreads();
+      double part[2] = {0.0, 0.0};
+#pragma unroll 4
+      for (int t = 0; t < 16; ++t) {
+        const int c = q * 16 + t;
+        if (c < a.jbp && in && r >= a.jp + c) {
+          const double pv = sTV[c * NB + lane];
+#pragma unroll
+          for (int jj = 0; jj < 2; ++jj)
+            if (j0 + jj < kb) part[jj] = fma(pv, sw[c][j0 + jj], part[jj]);
+        }
+      }
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj)
+        if (j0 + jj < kb) spart[j0 + jj][q][lane] = part[jj];
+      __syncthreads();
+      if (wv < kb) zr -= (spart[wv][0][lane] + spart[wv][1][lane]) + (spart[wv][2][lane] + spart[wv][3][lane]);
+    }
+    if (wv < kb) {
+      if (in) {
+        if (a.epi) store_res<T, BETA0>((T *)a.res + wv * a.ldr, r, zr, a.alpha, a.beta);
+        else if (!a.zc_out) a.z[r + wv * a.mf] = zr;
+        else if (r < a.nf) a.zc[r + wv * a.nf] = zr;
+      }
+      if (a.jbn) sz[wv][lane] = zr;
+    }
+    if (a.jbn) {
+      __syncthreads();
+      bool on[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) on[u] = wv * 4 + u < a.jbn && in && r >= a.jn + wv * 4 + u;
+#pragma unroll
+      for (int j = 0; j < KB; ++j) {
+        if (j < kb) {
+          const double zj = sz[j][lane];
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (on[u]) acc[u][j] = fma(vn[u], zj, acc[u][j]);
+        }
+      }
+      if (!a.jbp) __syncthreads();                       // a chain's first launch: nothing else separates these reads of sz from the next chunk
+    }
+  }
+  if (a.jbn) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int j = 0; j < KB; ++j)
+        if (j < kb) {
+          const double s = wave_sum(acc[u][j]);
+          if (lane == 0) a.pout[j * slots + (int64_t)g * NB + wv * 4 + u] = s;
+        }
+  }
+}
+
+template <typename T>
+int32_t launch_reflect_block(mxlo_ctx *ctx, const QrArgs &a) {
+  const unsigned G = (unsigned)qr_grid(a.mf);
+  if (a.beta == 0.0) hipLaunchKernelGGL((qr_reflect_block_kernel<T, true>), dim3(G), dim3(QBT), 0, ctx->stream, a);
+  else hipLaunchKernelGGL((qr_reflect_block_kernel<T, false>), dim3(G), dim3(QBT), 0, ctx->stream, a);
+  MXLO_LAUNCH_CHECK();
+  return MXLO_OK;
+}
+
+// doubles of work: the vector apply's, and the block apply's — z (mf x KB), two sets of QG x NB slots per right-hand side, and
+// the compact nf x KB matrix the block sweep works on (it addresses its matrix with column stride n = nf)
+inline int64_t qr_work(int64_t mf) { return mf + 2 * (int64_t)QG * NB; }
+inline int64_t qr_block_work(int64_t mf, int64_t nf) { return KB * (mf + nf + 2 * (int64_t)QG * NB); }
+
+// qr_mul_t for a group of grp.kb columns: the same 2 nb + 1 launches on the same grids. The sweep with R keeps its own
+// kernel and its own nf x kb matrix zc: N — the last reflector launch writes rows < nf of z there (the others are not needed
+// again); T — the first one reads them from there.
+template <typename T>
+int32_t qr_mul_block_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t mf, int64_t nf, const double *tfac, const double *dinv,
+                       double *work, const T *V, bool trans, double alpha, double beta, Group grp) {
+  const int64_t nb = (nf + NB - 1) / NB, slots = (int64_t)KB * QG * NB;
+  double *pb[2] = {work + KB * mf, work + KB * mf + slots};
+  QrArgs a{};
+  a.W = W; a.ld = ld; a.mf = mf; a.nf = nf; a.z = work; a.res = res; a.alpha = alpha; a.beta = beta; a.tp_trans = trans ? 0 : 1;
+  a.kb = grp.kb; a.ldr = grp.ldr; a.ldv = grp.ldv; a.zc = pb[1] + slots;
+  if (trans)
+    MXLO_TRY(sweep<T>(ctx, W, ld, nf, true, true, dinv, a.zc, V, true, false, false, res, alpha, beta, nullptr, nullptr, nullptr, nullptr,
+                      false, grp));
+  for (int64_t i = 0; i <= nb; ++i) {                    // launch i reads the slots (i + 1) & 1 and leaves the slots i & 1
+    const int64_t kp = trans ? nb - i : i - 1, kn = trans ? nb - 1 - i : i;
+    a.v = (!trans && i == 0) ? V : nullptr;
+    a.load = i == 0 ? (trans ? 2 : 1) : 0;
+    a.jbp = a.jbn = 0;
+    if (i > 0) { a.jp = kp * NB; a.jbp = (int)(nf - a.jp < NB ? nf - a.jp : NB); a.tp = tfac + kp * NB2; }
+    if (i < nb) { a.jn = kn * NB; a.jbn = (int)(nf - a.jn < NB ? nf - a.jn : NB); }
+    a.pin = pb[(i + 1) & 1]; a.pout = pb[i & 1];
+    a.epi = trans && i == nb;
+    a.zc_out = !trans && i == nb;
+    MXLO_TRY(launch_reflect_block<T>(ctx, a));
+  }
+  if (trans) return MXLO_OK;
+  return sweep<T>(ctx, W, ld, nf, true, false, dinv, a.zc, (const T *)nullptr, true, false, true, res, alpha, beta, nullptr, nullptr,
+                  nullptr, nullptr, false, grp);
+}
+
 }  // namespace
 
 MXLO_API int32_t mxlo_geqrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_trans, void *W, int64_t ldw, int64_t mf,
@@ -2202,7 +2385,7 @@ MXLO_API int32_t mxlo_qr_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void
   MXLO_REQUIRE((res == v && mf == nf) || !bytes_overlap(res, rb, v, vb), MXLO_EINVAL,
                "%s: res overlaps v without being v (only mul!(x, op, x) of a square operator is defined)", what);
   const std::pair<const void *, int64_t> own[] = {{W, ((nf - 1) * ldw + mf) * es}, {tfac, nb * NB2 * 8}, {dinv, nb * NB2 * 8},
-                                                  {work, (mf + 2 * (int64_t)QG * NB) * 8}};
+                                                  {work, qr_work(mf) * 8}};
   for (const auto &[p, pb] : own)
     MXLO_REQUIRE(!bytes_overlap(res, rb, p, pb) && !bytes_overlap(v, vb, p, pb), MXLO_EINVAL,
                  "%s: res / v overlap the factor, the T factors, the block inverses or the work vector", what);
@@ -2210,4 +2393,38 @@ MXLO_API int32_t mxlo_qr_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void
   if (dtype == MXLO_F64)
     return qr_mul_t<double>(ctx, (double *)res, (const double *)W, ldw, mf, nf, tfac, dinv, work, (const double *)v, tr, alpha, beta);
   return qr_mul_t<float>(ctx, (float *)res, (const float *)W, ldw, mf, nf, tfac, dinv, work, (const float *)v, tr, alpha, beta);
+}
+
+MXLO_API int32_t mxlo_qr_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf,
+                                   int64_t nf, const double *tfac, const double *dinv, double *work, const void *V, int64_t ldv,
+                                   int64_t k, int32_t op_mode, double alpha, double beta) {
+  const char *what = "mxlo_qr_mul_block";
+  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
+  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
+  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "%s: op_mode %d", what, op_mode);
+  MXLO_REQUIRE(nf >= 1 && mf >= nf && ldw >= mf && mf < (1LL << 31) - NB, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld (1 <= nf <= mf), ldw = %lld",
+               what, (long long)mf, (long long)nf, (long long)ldw);
+  const bool tr = op_mode != MXLO_OP_N;
+  const int64_t rrows = tr ? mf : nf, vrows = tr ? nf : mf;
+  MXLO_REQUIRE(k >= 0 && ldr >= rrows && ldv >= vrows, MXLO_ESHAPE, "%s: k = %lld, ldr = %lld for %lld rows, ldv = %lld for %lld rows", what,
+               (long long)k, (long long)ldr, (long long)rrows, (long long)ldv, (long long)vrows);
+  if (k == 0) return MXLO_OK;
+  MXLO_REQUIRE(res && W && tfac && dinv && work && V, MXLO_EINVAL, "%s: null operand", what);
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4, nb = (nf + NB - 1) / NB;
+  const int64_t rb = ((k - 1) * ldr + rrows) * es, vb = ((k - 1) * ldv + vrows) * es;
+  MXLO_REQUIRE((res == V && ldr == ldv && mf == nf) || !bytes_overlap(res, rb, V, vb), MXLO_EINVAL,
+               "%s: res overlaps V without being V (only mul!(X, op, X) of a square operator, as the same matrix, is defined)", what);
+  const std::pair<const void *, int64_t> own[] = {{W, ((nf - 1) * ldw + mf) * es}, {tfac, nb * NB2 * 8}, {dinv, nb * NB2 * 8},
+                                                  {work, qr_block_work(mf, nf) * 8}};
+  for (const auto &[p, pb] : own)
+    MXLO_REQUIRE(!bytes_overlap(res, rb, p, pb) && !bytes_overlap(V, vb, p, pb), MXLO_EINVAL,
+                 "%s: res or V overlaps the factor, the T factors, the block inverses or the work space", what);
+  MXLO_DEVICE_GUARD(ctx);
+  if (dtype == MXLO_F64)
+    return for_groups((double *)res, ldr, (const double *)V, ldv, k, [&](double *r, const double *v, Group grp) {
+      return qr_mul_block_t<double>(ctx, r, (const double *)W, ldw, mf, nf, tfac, dinv, work, v, tr, alpha, beta, grp);
+    });
+  return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
+    return qr_mul_block_t<float>(ctx, r, (const float *)W, ldw, mf, nf, tfac, dinv, work, v, tr, alpha, beta, grp);
+  });
 }

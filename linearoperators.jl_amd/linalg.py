@@ -9,7 +9,7 @@ bit-identical to its vector apply. The inverse of a general dense matrix is `opL
 stays triangular-only. A pivoted (Bunch–Kaufman) or sparse LDLᵀ are not provided. `refine=r` on the three
 factorisation operators adds r steps of iterative refinement to every apply (`mxlo_*_mul_refine`), with the residual and the
 iterate in Float64 and a snapshot of M the operator keeps. `opQR` is the rectangular `M \\ v`: least-squares and minimum-norm
-solves through an unpivoted Householder QR (`mxlo_geqrf`, `mxlo_qr_mul`).
+solves through an unpivoted Householder QR (`mxlo_geqrf`, `mxlo_qr_mul`, and `mxlo_qr_mul_block` for matrix operands).
 """
 from __future__ import annotations
 
@@ -78,20 +78,21 @@ def _check_operands(res, v, T):
         raise ValueError("mul!: res and v must have unit stride")
 
 
-def _check_block_operands(res, m, T, n):
-    """The n x k operands of a block apply, as `_apply_closure_to_matrix` hands them over (column-major, any leading
-    dimension): returns (ldr, ldv, k)."""
+def _check_block_operands(res, m, T, n, nres=None):
+    """The operands of a block apply, as `_apply_closure_to_matrix` hands them over (column-major, any leading
+    dimension): V is n x k and res nres x k (nres = n unless given: a rectangular operator). Returns (ldr, ldv, k)."""
+    nres = n if nres is None else nres
     if res.dtype is not T or m.dtype is not T:
         raise TypeError(f"mul!: {res.dtype} / {m.dtype} operands next to a {T} factorisation")
-    if res.dim() != 2 or m.dim() != 2 or m.shape[0] != n or res.shape[0] != n or res.shape[1] != m.shape[1]:
+    if res.dim() != 2 or m.dim() != 2 or m.shape[0] != n or res.shape[0] != nres or res.shape[1] != m.shape[1]:
         raise LinearOperatorException("shape mismatch")
     k = m.shape[1]
     lds = []
-    for X in (res, m):
-        if n > 1 and X.stride(0) != 1:
+    for X, rows in ((res, nres), (m, n)):
+        if rows > 1 and X.stride(0) != 1:
             raise ValueError("mul!: the columns of res and V must have unit stride")
-        ldx = X.stride(1) if k > 1 else max(1, n)
-        if ldx < max(1, n):
+        ldx = X.stride(1) if k > 1 else max(1, rows)
+        if ldx < max(1, rows):
             raise ValueError("mul!: res and V must be column-major (leading dimension >= n)")
         lds.append(ldx)
     return lds[0], lds[1], k
@@ -440,6 +441,11 @@ def qr_launches(nf: int) -> int:
     return 2 * ((int(nf) + BLOCK - 1) // BLOCK) + 1
 
 
+def qr_block_launches(nf: int, k: int) -> int:
+    """Launches of an opQR apply to a matrix with k columns: the chain of one vector apply per group of GROUP columns."""
+    return ((int(k) + GROUP - 1) // GROUP) * qr_launches(nf)
+
+
 def _check_rect(A, name: str):
     """opQR's checks that need no device, in the order the docstring states. Rectangular is not a shape mismatch."""
     if not isinstance(A, torch.Tensor) or A.dim() != 2:
@@ -473,9 +479,12 @@ def opQR(A: torch.Tensor):
 
     An apply is `qr_launches(nf)` = 2⌈nf/64⌉ + 1 launches, whatever mf is, and nothing else: it allocates nothing, never
     synchronises, can be captured (`capture_mul`) and is bit-reproducible (every sum in a fixed order in Float64). res may be
-    v when m == k. Matrix operands go column by column. NOT provided: a block form, `refine`, column pivoting
-    or any rank-revealing form (a rank-deficient A that escapes the exact test above gives a meaningless answer), complex
-    element types, Julia glue."""
+    v when m == k. Matrix operands (`A \\ V`, `to_dense`) go through the block form (`mxlo_qr_mul_block`): the chain of ONE vector
+    apply per GROUP = 8 columns, `qr_block_launches(nf, k)` launches, every element of a reflector panel loaded once per chunk
+    of rows for the whole group, each column bit-identical to its vector apply; res may be V (the same matrix) when m == k.
+    The work space, allocated once here, is 8 (mf + nf + 2·512·64) Float64; the vector apply uses its first
+    mf + 2·512·64. NOT provided: `refine`, column pivoting or any rank-revealing form (a rank-deficient A
+    that escapes the exact test above gives a meaningless answer), complex element types, Julia glue."""
     m, k = _check_rect(A, "opQR")
     T = A.dtype
     tall = m >= k
@@ -489,7 +498,8 @@ def opQR(A: torch.Tensor):
     nblk = (nf + BLOCK - 1) // BLOCK
     tfac = torch.zeros(nblk * BLOCK * BLOCK, dtype=torch.float64, device=A.device)
     dinv = torch.empty(nblk * BLOCK * BLOCK, dtype=torch.float64, device=A.device)
-    work = torch.empty(mf + 2 * QR_SLOTS * BLOCK, dtype=torch.float64, device=A.device)     # z, then two sets of partial slots
+    # the block apply's: z (mf x GROUP), two sets of partial slots per column, the sweep's nf x GROUP; the vector apply uses a prefix
+    work = torch.empty(GROUP * (mf + nf + 2 * QR_SLOTS * BLOCK), dtype=torch.float64, device=A.device)
     nscratch = 2 * (QR_SLOTS * BLOCK + BLOCK) + (512 + 2 * nblk) * BLOCK * BLOCK
     scratch = torch.empty(nscratch, dtype=torch.float64, device=A.device)                   # needed by the factorisation only
     info_dev = torch.zeros(1, dtype=torch.int32, device=A.device)
@@ -507,9 +517,17 @@ def opQR(A: torch.Tensor):
         _lib.call("mxlo_qr_mul", ctx_of(res).handle, code, res.data_ptr(), pW, ldw, mf, nf, pT, pD, pZ, v.data_ptr(), mode, float(a),
                   float(b))
 
+    def block(res, V, a, b, mode):
+        nv, nres = (mf, nf) if mode == _lib.OP_N else (nf, mf)
+        ldr, ldv, cols = _check_block_operands(res, V, T, nv, nres)
+        _lib.call("mxlo_qr_mul_block", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, mf, nf, pT, pD, pZ, V.data_ptr(), ldv,
+                  cols, mode, float(a), float(b))
+
     fwd, bwd = (_lib.OP_N, _lib.OP_T) if tall else (_lib.OP_T, _lib.OP_N)
     prod = columnwise(lambda res, v, a, b: solve(res, v, a, b, fwd))
     tprod = columnwise(lambda res, u, a, b: solve(res, u, a, b, bwd))
+    prod._matrix = lambda res, V, a, b: block(res, V, a, b, fwd)
+    tprod._matrix = lambda res, V, a, b: block(res, V, a, b, bwd)
     op = LinearOperator(T, k, m, False, False, prod, tprod, tprod, S=Storage(T, A.device))
     op._deps = (W,)
     op._tall = tall

@@ -33,7 +33,10 @@ the same shapes on another commit come from `--block --mul-only` (its k = 1 and 
 precisions: the factorisation (construction, allocations and the one synchronisation included) and the apply in both modes —
 time, spread, launches, and the fraction of the 8 TB/s peak by the byte model (mf·nf + nf²/2)·sizeof(T) — and, for comparison,
 what a caller had to do before: opCholesky(AᵀA) (the Gram matrix by a torch GEMM) and per apply the dense Aᵀv plus the
-Cholesky apply. Other shapes: arguments of the form MFxNF.
+Cholesky apply. The k = 8 and k = 32 rows are `mul!(X, op, V)` on a matrix operand in both modes, rated by the block's byte
+model: the factor once per group of 8 columns, ⌈k/8⌉·(mf·nf + nf²/2)·sizeof(T), plus the operands, (mf + nf)·k·sizeof(T).
+--mul-only prints the apply rows alone (the protocol for a baseline run on another commit). Other shapes: arguments of the
+form MFxNF.
 
     python tools/bench_linalg.py --qr [MFxNF ...] > profiles/linalg_qr.txt
 """
@@ -227,13 +230,26 @@ def qr_legs():
                 print(f"{name + ' ' + tag:44s} {mf:8d} {nf:5d} {ms:10.4f} {100 * timeit.spread:5.1f}% {nl:6d} {gbs:8.1f} {100 * gbs / PEAK:6.2f}",
                       flush=True)
 
-            row("opQR(A) factorisation", lambda: lo.opQR(A), 2, 0, 0)
+            if not MUL_ONLY:
+                row("opQR(A) factorisation", lambda: lo.opQR(A), 2, 0, 0)
             op = lo.opQR(A)
             row("opQR apply (least squares)", lambda: lo.mul(x, op, v, 1.0, 0.0), reps, nbytes, launches(lambda: lo.mul(x, op, v, 1.0, 0.0)))
             row("transpose(opQR) apply (minimum norm)", lambda: lo.mul(y, op.T, u, 1.0, 0.0), reps, nbytes,
                 launches(lambda: lo.mul(y, op.T, u, 1.0, 0.0)))
+            for k in (8, 32):                           # matrix operands: the factor once per group of 8 columns, plus the operands
+                V, U = colmajor(mf, k, dtype, 10 * mf + k), colmajor(nf, k, dtype, 10 * nf + k)
+                X, Y = torch.empty_like(U), torch.empty_like(V)
+                kbytes = -(-k // 8) * nbytes + (mf + nf) * k * es
+                kreps = max(2, reps // (k // 8))
+                row(f"opQR apply, k = {k}", lambda: lo.mul(X, op, V, 1.0, 0.0), kreps, kbytes, launches(lambda: lo.mul(X, op, V, 1.0, 0.0)))
+                row(f"transpose(opQR) apply, k = {k}", lambda: lo.mul(Y, op.T, U, 1.0, 0.0), kreps, kbytes,
+                    launches(lambda: lo.mul(Y, op.T, U, 1.0, 0.0)))
+                del V, U, X, Y
             del op
             torch.cuda.empty_cache()
+            if MUL_ONLY:
+                del A
+                continue
             dense = lo.LinearOperatorFromMatrix(A)
             t = torch.empty_like(u)
             row("normal equations: A'A + opCholesky", lambda: lo.opCholesky((A.t() @ A).t().contiguous().t()), 2, 0, 0)
