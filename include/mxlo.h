@@ -1008,6 +1008,44 @@ int32_t mxlo_qr_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, 
                           const double *tfac, const double *dinv, double *work, const void *V, int64_t ldv, int64_t k,
                           int32_t op_mode, double alpha, double beta);
 
+/* opQR(A, pivot=true) — `M \ v` of src/linalg.jl:27-32 (mulFact!, src/linalg.jl:3-9) for a rectangular dense M as Julia
+ * computes it: a COLUMN-PIVOTED QR with a numerical rank decision. mxlo_geqp3 is mxlo_geqrf with pivoting: F P = Q R in W
+ * (LAPACK's layout), jpvt (device, nf int32): F[:, jpvt[j]] is column j of Q R. At every step the pivot is the remaining
+ * column of largest 2-norm from the diagonal row down, the first one on a tie.
+ * Right-looking, one column per step, three launches per step and nothing read back in between: (1) one workgroup adds up,
+ * in order, the partial squared norms the step before left for the trailing columns, takes the first arg-max and exchanges
+ * jpvt; (2) a grid of (row groups: chunks of 64 rows dealt to at most 64) x (tiles of 64 trailing columns) leaves the partial
+ * dots of the pivot column with every trailing column and copies of the two columns to exchange; (3) the same grid adds up
+ * its own tile's dots, forms the reflector in larfg's convention exactly as mxlo_geqrf does, applies it to its rows,
+ * exchanges the two columns over their whole height, and leaves the partial squared norms of what it wrote for the next
+ * step: the norms are RECOMPUTED, never downdated. 3 nf + 3 launches whose grids depend on (mf, nf) only; no workgroup waits
+ * for another; every sum in a fixed order in f64. About 2 sizeof(T) sum_c (mf - c)(nf - c) bytes.
+ * rank (host out) = the length of the leading run of j with |R_jj| > rtol |R_11| (0 <= rtol < 1), decided on the device and
+ * read back with the info word — the only synchronisation; info_dev is TWO device words. Afterwards, for the leading rank
+ * columns only: the compact-WY factors T per block column of 64 from V'V (LAPACK's larft) into tfac, and the block inverses
+ * of R11 = R[0:rank, 0:rank] into dinv (2 ceil(rank/64) + 1 more launches, not waited for).
+ * *info: c + 1 when a remaining column norm at step c is not finite (a NaN counts as the largest), or 1 when F == 0;
+ * a rank-deficient F, zero columns included, is not an error. Not capturable (MXLO_ESTATE). scratch: scratch_len >=
+ * 2 * 64 * nf + 64 + 2 nf + 2 mf + 2 + 64 * 4096 doubles, needed during the call only. No two operands may overlap. */
+int32_t mxlo_geqp3(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_trans, void *W, int64_t ldw, int64_t mf,
+                   int64_t nf, double *tfac, double *dinv, int32_t *jpvt, double rtol, double *scratch, int64_t scratch_len,
+                   int32_t *info_dev, int32_t *info, int32_t *rank);
+/* mulFact! (src/linalg.jl:3-9) with the factor of mxlo_geqp3: the BASIC solution of rank `rank` (1 <= rank <= nf).
+ * MXLO_OP_N: x[jpvt[0:rank]] = inv(R11) (Q' v)[0:rank] and the other nf - rank entries of x are exactly zero; res (nf) =
+ * alpha x + beta res. MXLO_OP_T / MXLO_OP_C: res (mf) = alpha y + beta res, y = Q[:, 0:rank] inv(R11') u[jpvt[0:rank]].
+ * The launches are those of mxlo_qr_mul for nf := rank, 2 ceil(rank/64) + 1, on the same kernels: the sweep reads u / writes
+ * x through jpvt, and the last reflector launch of MXLO_OP_N also writes the entries of res that are no pivots. Operands,
+ * work, aliasing rules and promises as mxlo_qr_mul; jpvt may overlap neither res nor v. */
+int32_t mxlo_qrp_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t mf, int64_t nf, const double *tfac,
+                     const double *dinv, const int32_t *jpvt, int64_t rank, double *work, const void *v, int32_t op_mode, double alpha,
+                     double beta);
+/* mxlo_qrp_mul on k columns, as mxlo_qr_mul_block is to mxlo_qr_mul: groups of 8 columns, ceil(k/8) (2 ceil(rank/64) + 1)
+ * launches, column j BIT FOR BIT the vector apply of column j. Operands and work as mxlo_qr_mul_block (V is nf x k in
+ * MXLO_OP_T whatever the rank is); jpvt may overlap neither res nor V. */
+int32_t mxlo_qrp_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf, int64_t nf,
+                           const double *tfac, const double *dinv, const int32_t *jpvt, int64_t rank, double *work, const void *V,
+                           int64_t ldv, int64_t k, int32_t op_mode, double alpha, double beta);
+
 #ifdef __cplusplus
 }
 #endif

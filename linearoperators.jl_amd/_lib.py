@@ -205,6 +205,11 @@ _PROTOS = {
     "mxlo_geqrf": [_vp, _i32, _vp, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, C.POINTER(_i32)],
     "mxlo_qr_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl],
     "mxlo_qr_mul_block": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _dbl, _dbl],
+    # opQR(pivot=True): mxlo_geqrf's, with jpvt, rtol after dinv and rank after info / the applies with (jpvt, rank) after dinv
+    "mxlo_geqp3": [_vp, _i32, _vp, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _dbl, _vp, _i64, _vp, C.POINTER(_i32),
+                   C.POINTER(_i32)],
+    "mxlo_qrp_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _dbl, _dbl],
+    "mxlo_qrp_mul_block": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _dbl, _dbl],
 }
 
 

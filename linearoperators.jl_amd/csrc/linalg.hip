@@ -2059,6 +2059,8 @@ struct QrArgs {
   int64_t ldr, ldv;      // res are then matrices with these leading dimensions, z is mf x kb with column stride mf, and right-hand
   double *zc;            // side j has its partial slots at pin / pout + j QG NB. zc: the sweep's compact nf x kb matrix (column stride
   int zc_out;            // nf), which load 2 reads rows < nf from and which the launch with zc_out writes them to instead of z
+  const int *fill_idx;   // pivoted form, or NULL: this launch also writes res[fill_idx[i]] = alpha 0 + beta res[..] for fill_lo <= i <
+  int64_t fill_lo, fill_hi;      // fill_hi, the entries of a rank-deficient solution that are no pivots (every column of a group)
 };
 
 template <typename T, bool BETA0>
@@ -2123,6 +2125,9 @@ __global__ void __launch_bounds__(kBlock) qr_reflect_kernel(QrArgs a) {
       if (lane == 0) a.pout[(int64_t)g * NB + q * 16 + t] = s;
     }
   }
+  if (a.fill_idx)
+    for (int64_t i = a.fill_lo + (int64_t)g * kBlock + tid; i < a.fill_hi; i += (int64_t)G * kBlock)
+      store_res<T, BETA0>((T *)a.res, a.fill_idx[i], 0.0, a.alpha, a.beta);
 }
 
 template <typename T>
@@ -2139,12 +2144,12 @@ int32_t launch_reflect(mxlo_ctx *ctx, const QrArgs &a) {
 // last one with the epilogue over all mf entries. 2 nb + 1 launches either way. work: z (mf), then two sets of QG x NB slots.
 template <typename T>
 int32_t qr_mul_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t mf, int64_t nf, const double *tfac, const double *dinv,
-                 double *work, const T *v, bool trans, double alpha, double beta) {
+                 double *work, const T *v, bool trans, double alpha, double beta, const int *jpvt = nullptr, int64_t nfull = 0) {
   const int64_t nb = (nf + NB - 1) / NB;
   double *pb[2] = {work + mf, work + mf + (int64_t)QG * NB};
   QrArgs a{};
   a.W = W; a.ld = ld; a.mf = mf; a.nf = nf; a.z = work; a.res = res; a.alpha = alpha; a.beta = beta; a.tp_trans = trans ? 0 : 1;
-  if (trans) MXLO_TRY(sweep<T>(ctx, W, ld, nf, true, true, dinv, work, v, true, false, false, res, alpha, beta));
+  if (trans) MXLO_TRY(sweep<T>(ctx, W, ld, nf, true, true, dinv, work, v, true, false, false, res, alpha, beta, nullptr, nullptr, jpvt));
   for (int64_t i = 0; i <= nb; ++i) {                    // launch i reads the slots (i + 1) & 1 and leaves the slots i & 1
     const int64_t kp = trans ? nb - i : i - 1, kn = trans ? nb - 1 - i : i;
     a.v = (!trans && i == 0) ? v : nullptr;
@@ -2154,10 +2159,12 @@ int32_t qr_mul_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t mf, int6
     if (i < nb) { a.jn = kn * NB; a.jbn = (int)(nf - a.jn < NB ? nf - a.jn : NB); }
     a.pin = pb[(i + 1) & 1]; a.pout = pb[i & 1];
     a.epi = trans && i == nb;
+    if (jpvt && !trans && i == nb) { a.fill_idx = jpvt; a.fill_lo = nf; a.fill_hi = nfull; }
     MXLO_TRY(launch_reflect<T>(ctx, a));
   }
   if (trans) return MXLO_OK;
-  return sweep<T>(ctx, W, ld, nf, true, false, dinv, work, (const T *)nullptr, true, false, true, res, alpha, beta);
+  return sweep<T>(ctx, W, ld, nf, true, false, dinv, work, (const T *)nullptr, true, false, true, res, alpha, beta, nullptr, nullptr,
+                  nullptr, jpvt);
 }
 
 // qr_reflect_kernel carrying a group of kb <= KB right-hand sides, in a workgroup of 16 waves. Per right-hand side the
@@ -2287,6 +2294,11 @@ __global__ void __launch_bounds__(QBT) qr_reflect_block_kernel(QrArgs a) {
           if (lane == 0) a.pout[j * slots + (int64_t)g * NB + wv * 4 + u] = s;
         }
   }
+  if (a.fill_idx)
+    for (int64_t i = a.fill_lo + (int64_t)g * QBT + tid; i < a.fill_hi; i += (int64_t)G * QBT) {
+      const int64_t o = a.fill_idx[i];
+      for (int j = 0; j < kb; ++j) store_res<T, BETA0>((T *)a.res + j * a.ldr, o, 0.0, a.alpha, a.beta);
+    }
 }
 
 template <typename T>
@@ -2308,14 +2320,15 @@ inline int64_t qr_block_work(int64_t mf, int64_t nf) { return KB * (mf + nf + 2 
 // again); T — the first one reads them from there.
 template <typename T>
 int32_t qr_mul_block_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t mf, int64_t nf, const double *tfac, const double *dinv,
-                       double *work, const T *V, bool trans, double alpha, double beta, Group grp) {
+                       double *work, const T *V, bool trans, double alpha, double beta, Group grp, const int *jpvt = nullptr,
+                       int64_t nfull = 0) {
   const int64_t nb = (nf + NB - 1) / NB, slots = (int64_t)KB * QG * NB;
   double *pb[2] = {work + KB * mf, work + KB * mf + slots};
   QrArgs a{};
   a.W = W; a.ld = ld; a.mf = mf; a.nf = nf; a.z = work; a.res = res; a.alpha = alpha; a.beta = beta; a.tp_trans = trans ? 0 : 1;
   a.kb = grp.kb; a.ldr = grp.ldr; a.ldv = grp.ldv; a.zc = pb[1] + slots;
   if (trans)
-    MXLO_TRY(sweep<T>(ctx, W, ld, nf, true, true, dinv, a.zc, V, true, false, false, res, alpha, beta, nullptr, nullptr, nullptr, nullptr,
+    MXLO_TRY(sweep<T>(ctx, W, ld, nf, true, true, dinv, a.zc, V, true, false, false, res, alpha, beta, nullptr, nullptr, jpvt, nullptr,
                       false, grp));
   for (int64_t i = 0; i <= nb; ++i) {                    // launch i reads the slots (i + 1) & 1 and leaves the slots i & 1
     const int64_t kp = trans ? nb - i : i - 1, kn = trans ? nb - 1 - i : i;
@@ -2327,11 +2340,354 @@ int32_t qr_mul_block_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t mf
     a.pin = pb[(i + 1) & 1]; a.pout = pb[i & 1];
     a.epi = trans && i == nb;
     a.zc_out = !trans && i == nb;
+    if (jpvt && !trans && i == nb) { a.fill_idx = jpvt; a.fill_lo = nf; a.fill_hi = nfull; }
     MXLO_TRY(launch_reflect_block<T>(ctx, a));
   }
   if (trans) return MXLO_OK;
   return sweep<T>(ctx, W, ld, nf, true, false, dinv, a.zc, (const T *)nullptr, true, false, true, res, alpha, beta, nullptr, nullptr,
-                  nullptr, nullptr, false, grp);
+                  nullptr, jpvt, false, grp);
+}
+
+// ---------------------------------------------------------------------------------------------- geqp3
+// F P = Q R with column pivoting, right-looking, ONE column per step, three launches per step (below). The grids of a step are
+// 2-D — row groups x tiles of NB trailing columns — so a workgroup adds up only its own tile's partial sums. The chunks of NB
+// rows from the diagonal's chunk down are dealt round-robin to at most QPG row groups; tiles and chunks are aligned to NB in
+// absolute indices. A step reads the two columns it exchanges only through copies (xbuf: the pivot column, cbuf: the one it
+// displaces) that the launch before made, so no workgroup reads what another one of the same launch writes. The squared
+// norms of the trailing columns are RECOMPUTED by the pass that has just written them, never downdated.
+constexpr int QPG = 64;              // most row groups of a step = partial slots per column
+
+struct QpScratch {
+  double *npart, *dpart, *sig, *drow, *taus, *xbuf, *cbuf, *gpart;
+  int *piv;
+};
+
+inline int64_t geqp3_scratch(int64_t mf, int64_t nf) { return 2 * (int64_t)QPG * nf + QPG + 2 * nf + 2 * mf + 2 + (int64_t)QPG * NB2; }
+
+inline QpScratch qp_layout(double *s, int64_t mf, int64_t nf) {
+  QpScratch l;
+  l.npart = s; s += (int64_t)QPG * nf;
+  l.dpart = s; s += (int64_t)QPG * nf;
+  l.sig = s; s += QPG;
+  l.drow = s; s += nf;
+  l.taus = s; s += nf;
+  l.xbuf = s; s += mf;
+  l.cbuf = s; s += mf;
+  l.piv = (int *)s; s += 2;
+  l.gpart = s;
+  return l;
+}
+
+// step 1, one workgroup: the squared norms of the columns c .. nf - 1 over the rows from c down, each the sum of the Gp partial
+// sums the launch before left, in order; the first largest one is the pivot: piv[0] = its column, jpvt[c] <-> jpvt[piv]. A norm
+// that is not finite (NaN counts as the largest), or a largest norm of zero at c == 0, stores c + 1 in *info.
+__global__ void __launch_bounds__(kBlock) geqp3_pivot_kernel(const double *__restrict__ npart, int Gp, int64_t nf, int64_t c, int *jpvt,
+                                                             int *piv, int *info) {
+  __shared__ double sv[kBlock];
+  __shared__ int sj[kBlock], sbad;
+  if (*info != 0) return;
+  const int tid = threadIdx.x;
+  if (tid == 0) sbad = 0;
+  if (c == 0)
+    for (int64_t j = tid; j < nf; j += kBlock) jpvt[j] = (int)j;
+  __syncthreads();
+  double best = -1.0;
+  int bj = 0x7fffffff;
+  for (int64_t j = c + tid; j < nf; j += kBlock) {
+    double s = 0.0;
+    for (int g = 0; g < Gp; ++g) s += npart[(int64_t)g * nf + j];
+    if (!(s < __builtin_inf())) sbad = 1;
+    if (s > best) { best = s; bj = (int)j; }
+  }
+  sv[tid] = best; sj[tid] = bj;
+  __syncthreads();
+  for (int h = kBlock / 2; h > 0; h >>= 1) {
+    if (tid < h) {
+      const double o = sv[tid + h];
+      const int oj = sj[tid + h];
+      if (o > sv[tid] || (o == sv[tid] && oj < sj[tid])) { sv[tid] = o; sj[tid] = oj; }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    if (sbad || (c == 0 && sv[0] == 0.0)) *info = (int)(c + 1);
+    else {
+      const int p = sj[0], t = jpvt[c];
+      piv[0] = p;
+      jpvt[c] = jpvt[p]; jpvt[p] = t;
+    }
+  }
+}
+
+// step 2, grid (row groups, tiles): x = the pivot column (memory column p), which becomes column c. Leaves the partial dots
+// of x below row c with every trailing column of the tile (memory column c standing in for column p), row c of those columns
+// (drow), and — tile 0 — the partial sums of sigma = |x below row c|^2 and the copies xbuf / cbuf of the memory columns p / c
+// over their whole height. Nothing of W is written.
+template <typename T>
+__global__ void __launch_bounds__(kBlock) geqp3_dot_kernel(const T *__restrict__ W, int64_t ld, int64_t mf, int64_t nf, int64_t c,
+                                                           const int *__restrict__ piv, double *__restrict__ dpart,
+                                                           double *__restrict__ sig, double *__restrict__ drow,
+                                                           double *__restrict__ xbuf, double *__restrict__ cbuf, const int *info) {
+  if (*info != 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int g = blockIdx.x, G = gridDim.x;
+  const bool t0 = blockIdx.y == 0;
+  const int64_t p = piv[0];
+  const int64_t ch0 = c / NB, nch = (mf + NB - 1) / NB, tlo = ((c + 1) / NB + blockIdx.y) * NB;
+  const T *xc = W + p * ld, *oc = W + c * ld;
+  double acc[16], sacc = 0.0;
+#pragma unroll
+  for (int t = 0; t < 16; ++t) acc[t] = 0.0;
+  for (int64_t ch = ch0 + g; ch < nch; ch += G) {
+    const int64_t r = ch * NB + lane;
+    const bool in = r < mf;
+    const double xr = in ? (double)xc[r] : 0.0, xd = r > c ? xr : 0.0;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      const int64_t j = tlo + q * 16 + t;
+      if (in && j > c && j < nf) {
+        const double val = (double)(j == p ? oc[r] : W[r + j * ld]);
+        acc[t] = fma(val, xd, acc[t]);
+        if (r == c) drow[j] = val;
+      }
+    }
+    if (t0 && q == 0 && in) {
+      xbuf[r] = xr;
+      cbuf[r] = (double)oc[r];
+      sacc = fma(xd, xd, sacc);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 16; ++t) {
+    const int64_t j = tlo + q * 16 + t;
+    const double s = wave_sum(acc[t]);
+    if (lane == 0 && j > c && j < nf) dpart[(int64_t)g * nf + j] = s;
+  }
+  if (t0 && q == 0) {
+    const double s = wave_sum(sacc);
+    if (lane == 0) sig[g] = s;
+  }
+  if (t0 && g == 0)
+    for (int64_t r = tid; r < ch0 * NB; r += kBlock) { xbuf[r] = (double)xc[r]; cbuf[r] = (double)oc[r]; }
+}
+
+// step 3, the same grid: adds up its tile's dots and sigma, forms the reflector of column c exactly as geqrf_panel_kernel does
+// (larfg: beta = -sign(alpha) |(alpha, x)|, tau = (beta - alpha) / beta, v = x / (alpha - beta); x == 0: tau = 0, H = I),
+// applies it to its rows of the tile's trailing columns — column p takes the displaced column from cbuf, over its whole
+// height — and leaves the partial squared norms of what it wrote below row c for the next step 1. Tile 0 writes column c:
+// R above the diagonal, beta on it, v below. c == -1: only the norms, of all columns over all rows. A norm that is not finite
+// stores c + 1 in *info; a zero one is a legitimate rank-deficient step.
+template <typename T>
+__global__ void __launch_bounds__(kBlock) geqp3_reflect_kernel(T *W, int64_t ld, int64_t mf, int64_t nf, int64_t c,
+                                                               const int *__restrict__ piv, const double *__restrict__ dpart,
+                                                               const double *__restrict__ sig, const double *__restrict__ drow,
+                                                               const double *__restrict__ xbuf, const double *__restrict__ cbuf,
+                                                               double *__restrict__ taus, double *__restrict__ npart, int *info) {
+  __shared__ double sW[NB], spart[4][NB];
+  if (*info != 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int g = blockIdx.x, G = gridDim.x;
+  const bool t0 = blockIdx.y == 0;
+  const int64_t p = c >= 0 ? (int64_t)piv[0] : -1;
+  const int64_t ch0 = (c < 0 ? 0 : c) / NB, nch = (mf + NB - 1) / NB, tlo = ((c + 1) / NB + blockIdx.y) * NB;
+  double scale = 0.0, beta = 0.0;
+  if (c >= 0) {
+    const int64_t jl = tlo + lane;
+    double a = 0.0;
+    if (jl > c && jl < nf)
+      for (int gg = q; gg < G; gg += 4) a += dpart[(int64_t)gg * nf + jl];
+    spart[q][lane] = a;
+    double sigma = 0.0;
+    for (int gg = 0; gg < G; ++gg) sigma += sig[gg];
+    __syncthreads();
+    const double alpha = xbuf[c];
+    const double nrm = sqrt(fma(alpha, alpha, sigma));
+    if (!(nrm < __builtin_inf())) {                      // the same value in every thread of every workgroup
+      if (g == 0 && t0 && tid == 0) *info = (int)(c + 1);
+      return;
+    }
+    double tau = 0.0;
+    beta = alpha;
+    if (sigma != 0.0) {
+      beta = -copysign(nrm, alpha);
+      tau = (beta - alpha) / beta;
+      scale = 1.0 / (alpha - beta);
+    }
+    if (tid < NB) {
+      const int64_t j = tlo + tid;
+      const double dot = (spart[0][tid] + spart[1][tid]) + (spart[2][tid] + spart[3][tid]);
+      sW[tid] = (j > c && j < nf) ? tau * fma(scale, dot, drow[j]) : 0.0;
+    }
+    if (g == 0 && t0 && tid == 0) taus[c] = tau;
+    __syncthreads();
+  }
+  double acc[16];
+#pragma unroll
+  for (int t = 0; t < 16; ++t) acc[t] = 0.0;
+  for (int64_t ch = ch0 + g; ch < nch; ch += G) {
+    const int64_t r = ch * NB + lane;
+    const bool in = r < mf;
+    double vr = 0.0;
+    if (c >= 0 && in) vr = r > c ? (double)(T)(xbuf[r] * scale) : (r == c ? 1.0 : 0.0);
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      const int64_t j = tlo + q * 16 + t;
+      if (in && j > c && j < nf) {
+        const double val = j == p ? cbuf[r] : (double)W[r + j * ld];
+        T x = (T)val;
+        if (c >= 0) {
+          if (r >= c) x = (T)fma(-sW[q * 16 + t], vr, val);
+          if (r >= c || j == p) W[r + j * ld] = x;
+        }
+        if (r > c) acc[t] = fma((double)x, (double)x, acc[t]);
+      }
+    }
+    if (c >= 0 && t0 && q == 0 && in) W[r + c * ld] = r > c ? (T)vr : (r == c ? (T)beta : (T)xbuf[r]);
+  }
+#pragma unroll
+  for (int t = 0; t < 16; ++t) {
+    const int64_t j = tlo + q * 16 + t;
+    const double s = wave_sum(acc[t]);
+    if (lane == 0 && j > c && j < nf) npart[(int64_t)g * nf + j] = s;
+  }
+  if (c >= 0 && t0 && g == 0)                            // the rows of R above the diagonal's chunk
+    for (int64_t r = tid; r < ch0 * NB; r += kBlock) {
+      W[r + c * ld] = (T)xbuf[r];
+      if (p != c) W[r + p * ld] = (T)cbuf[r];
+    }
+}
+
+// after the last step, one workgroup: rank = the length of the leading run of j with |R_jj| > rtol |R_00|, into info[1]
+template <typename T>
+__global__ void __launch_bounds__(kBlock) geqp3_rank_kernel(const T *__restrict__ W, int64_t ld, int64_t nf, double rtol, int *info) {
+  __shared__ int sm[kBlock];
+  const int tid = threadIdx.x;
+  if (info[0] != 0) return;
+  const double thr = rtol * fabs((double)W[0]);
+  int first = (int)nf;
+  for (int64_t j = tid; j < nf; j += kBlock)
+    if (!(fabs((double)W[j + j * ld]) > thr)) { first = (int)j; break; }
+  sm[tid] = first;
+  __syncthreads();
+  for (int h = kBlock / 2; h > 0; h >>= 1) {
+    if (tid < h && sm[tid + h] < sm[tid]) sm[tid] = sm[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) info[1] = sm[0];
+}
+
+// larft for one block column (columns j0 .. j0 + jb of the factor, rows from j0 down), two launches. (1) The partial Gram
+// matrices V' V of the panel, V with its implicit unit diagonal, one per row group, the chunks of a group in order.
+template <typename T>
+__global__ void __launch_bounds__(kBlock) geqp3_gram_kernel(const T *__restrict__ W, int64_t ld, int64_t mf, int64_t j0, int jb,
+                                                            double *__restrict__ gpart) {
+  __shared__ double sV[NB][NB + 1];                      // [column][row of the chunk]
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int g = blockIdx.x, G = gridDim.x;
+  const int64_t nch = (mf - j0 + NB - 1) / NB;
+  double acc[16];
+#pragma unroll
+  for (int t = 0; t < 16; ++t) acc[t] = 0.0;
+  for (int64_t ch = g; ch < nch; ch += G) {
+    const int64_t r = j0 + ch * NB + lane;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      const int col = q * 16 + t;
+      const int64_t d = j0 + col;
+      double v = 0.0;
+      if (col < jb && r < mf) v = r > d ? (double)W[r + d * ld] : (r == d ? 1.0 : 0.0);
+      sV[col][lane] = v;
+    }
+    __syncthreads();
+    for (int row = 0; row < NB; ++row) {
+      const double a = sV[lane][row];
+#pragma unroll
+      for (int t = 0; t < 16; ++t) acc[t] = fma(a, sV[q * 16 + t][row], acc[t]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int t = 0; t < 16; ++t) gpart[(int64_t)g * NB2 + lane + (q * 16 + t) * NB] = acc[t];
+}
+
+// (2) one workgroup: column c of T from column c of the Gram matrix (the G partial ones added in four strided quarters, then
+// (p0 + p1) + (p2 + p3)): T[0:c, c] = -tau_c T[0:c, 0:c] (V[:, 0:c]' v_c), T[c, c] = tau_c, as geqrf_panel_kernel builds it;
+// the rest of the 64 x 64 block is zero.
+__global__ void __launch_bounds__(kBlock) geqp3_larft_kernel(const double *__restrict__ gpart, int G, const double *__restrict__ taus,
+                                                             int jb, double *__restrict__ tf) {
+  __shared__ double sT[NB2], sg[NB], spart[4][NB];
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  for (int e = tid; e < NB2; e += kBlock) sT[e] = 0.0;
+  __syncthreads();
+  for (int c = 0; c < jb; ++c) {
+    double a = 0.0;
+    for (int gg = q; gg < G; gg += 4) a += gpart[(int64_t)gg * NB2 + lane + c * NB];
+    spart[q][lane] = a;
+    __syncthreads();
+    if (q == 0) sg[lane] = (spart[0][lane] + spart[1][lane]) + (spart[2][lane] + spart[3][lane]);
+    __syncthreads();
+    if (tid < NB) {
+      const double tau = taus[c];
+      double t = 0.0;
+      if (tid < c) {
+        for (int l = tid; l < c; ++l) t = fma(sT[tid + l * NB], sg[l], t);
+        t = -tau * t;
+      } else if (tid == c) t = tau;
+      sT[tid + c * NB] = t;
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < NB2; e += kBlock) tf[e] = sT[e];
+}
+
+// the chain up to the rank: 3 nf + 3 launches whose grids depend on (mf, nf) only; info_dev[0] = info, info_dev[1] = rank
+template <typename T>
+int32_t geqp3_t(mxlo_ctx *ctx, const T *M, int64_t ldm, int trans, T *W, int64_t ldw, int64_t mf, int64_t nf, int *jpvt, double rtol,
+                const QpScratch &l, int *info_dev) {
+  const int64_t nbt = (nf + NB - 1) / NB, nch = (mf + NB - 1) / NB;
+  MXLO_HIP(hipMemsetAsync(info_dev, 0, 2 * sizeof(int), ctx->stream));
+  hipLaunchKernelGGL((qr_copy_kernel<T>), dim3((unsigned)nch, (unsigned)nbt), dim3(kBlock), 0, ctx->stream, W, ldw, M, ldm, trans, mf, nf);
+  MXLO_LAUNCH_CHECK();
+  int Gp = (int)(nch < QPG ? nch : QPG);
+  hipLaunchKernelGGL((geqp3_reflect_kernel<T>), dim3((unsigned)Gp, (unsigned)nbt), dim3(kBlock), 0, ctx->stream, W, ldw, mf, nf,
+                     (int64_t)-1, (const int *)l.piv, (const double *)l.dpart, (const double *)l.sig, (const double *)l.drow,
+                     (const double *)l.xbuf, (const double *)l.cbuf, l.taus, l.npart, info_dev);
+  MXLO_LAUNCH_CHECK();
+  for (int64_t c = 0; c < nf; ++c) {
+    hipLaunchKernelGGL(geqp3_pivot_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, (const double *)l.npart, Gp, nf, c, jpvt, l.piv, info_dev);
+    MXLO_LAUNCH_CHECK();
+    const int64_t rch = nch - c / NB, tl = nbt - (c + 1) / NB;
+    const dim3 grid((unsigned)(rch < QPG ? rch : QPG), (unsigned)(tl < 1 ? 1 : tl));
+    hipLaunchKernelGGL((geqp3_dot_kernel<T>), grid, dim3(kBlock), 0, ctx->stream, (const T *)W, ldw, mf, nf, c, (const int *)l.piv, l.dpart,
+                       l.sig, l.drow, l.xbuf, l.cbuf, (const int *)info_dev);
+    MXLO_LAUNCH_CHECK();
+    hipLaunchKernelGGL((geqp3_reflect_kernel<T>), grid, dim3(kBlock), 0, ctx->stream, W, ldw, mf, nf, c, (const int *)l.piv,
+                       (const double *)l.dpart, (const double *)l.sig, (const double *)l.drow, (const double *)l.xbuf,
+                       (const double *)l.cbuf, l.taus, l.npart, info_dev);
+    MXLO_LAUNCH_CHECK();
+    Gp = (int)grid.x;
+  }
+  hipLaunchKernelGGL((geqp3_rank_kernel<T>), dim3(1), dim3(kBlock), 0, ctx->stream, (const T *)W, ldw, nf, rtol, info_dev);
+  MXLO_LAUNCH_CHECK();
+  return MXLO_OK;
+}
+
+// once the rank is known: T of the leading rank columns, block column by block column, and the block inverses of R11
+template <typename T>
+int32_t geqp3_finish_t(mxlo_ctx *ctx, const T *W, int64_t ldw, int64_t mf, int64_t rank, double *tfac, double *dinv, const QpScratch &l) {
+  const int64_t nb = (rank + NB - 1) / NB;
+  for (int64_t k = 0; k < nb; ++k) {
+    const int64_t j0 = k * NB, jb = rank - j0 < NB ? rank - j0 : NB, rch = (mf - j0 + NB - 1) / NB;
+    const int G = (int)(rch < QPG ? rch : QPG);
+    hipLaunchKernelGGL((geqp3_gram_kernel<T>), dim3((unsigned)G), dim3(kBlock), 0, ctx->stream, W, ldw, mf, j0, (int)jb, l.gpart);
+    MXLO_LAUNCH_CHECK();
+    hipLaunchKernelGGL(geqp3_larft_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, (const double *)l.gpart, G, (const double *)(l.taus + j0),
+                       (int)jb, tfac + k * NB2);
+    MXLO_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL((tri_prepare_kernel<T>), dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream, W, ldw, rank, 1, dinv);
+  MXLO_LAUNCH_CHECK();
+  return MXLO_OK;
 }
 
 }  // namespace
@@ -2426,5 +2782,110 @@ MXLO_API int32_t mxlo_qr_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int6
     });
   return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
     return qr_mul_block_t<float>(ctx, r, (const float *)W, ldw, mf, nf, tfac, dinv, work, v, tr, alpha, beta, grp);
+  });
+}
+
+MXLO_API int32_t mxlo_geqp3(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_trans, void *W, int64_t ldw, int64_t mf,
+                            int64_t nf, double *tfac, double *dinv, int32_t *jpvt, double rtol, double *scratch, int64_t scratch_len,
+                            int32_t *info_dev, int32_t *info, int32_t *rank) {
+  const char *what = "mxlo_geqp3";
+  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
+  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
+  MXLO_REQUIRE(nf >= 1 && mf >= nf && ldw >= mf, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld (1 <= nf <= mf), ldw = %lld", what, (long long)mf,
+               (long long)nf, (long long)ldw);
+  MXLO_REQUIRE(mf < (1LL << 31) - NB && (nf + NB - 1) / NB <= 65535, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld is too large", what,
+               (long long)mf, (long long)nf);
+  MXLO_REQUIRE(rtol >= 0.0 && rtol < 1.0, MXLO_EINVAL, "%s: rtol = %g (0 <= rtol < 1)", what, rtol);
+  MXLO_REQUIRE(M && W && tfac && dinv && jpvt && scratch && info_dev && info && rank, MXLO_EINVAL, "%s: null operand", what);
+  *info = 0;
+  *rank = 0;
+  const int64_t mr = m_trans ? nf : mf, mc = m_trans ? mf : nf;       // M as it is stored: mr x mc, column-major
+  MXLO_REQUIRE(ldm >= mr, MXLO_ESHAPE, "%s: ldm = %lld < %lld", what, (long long)ldm, (long long)mr);
+  MXLO_REQUIRE(scratch_len >= geqp3_scratch(mf, nf), MXLO_ESHAPE, "%s: scratch of %lld doubles, %lld needed", what, (long long)scratch_len,
+               (long long)geqp3_scratch(mf, nf));
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4, nb = (nf + NB - 1) / NB;
+  const std::pair<const void *, int64_t> bufs[] = {{M, ((mc - 1) * ldm + mr) * es}, {W, ((nf - 1) * ldw + mf) * es}, {tfac, nb * NB2 * 8},
+                                                   {dinv, nb * NB2 * 8},           {jpvt, nf * 4},                  {scratch, scratch_len * 8},
+                                                   {info_dev, 8}};
+  for (size_t x = 0; x < 7; ++x)
+    for (size_t y = x + 1; y < 7; ++y)
+      MXLO_REQUIRE(!bytes_overlap(bufs[x].first, bufs[x].second, bufs[y].first, bufs[y].second), MXLO_EINVAL,
+                   "%s: M, the factor, the T factors, the block inverses, the permutation, the scratch and the info words overlap", what);
+  MXLO_REQUIRE(!ctx->capturing, MXLO_ESTATE, "%s: reads its info word and the rank back, which a graph capture cannot hold", what);
+  MXLO_DEVICE_GUARD(ctx);
+  const QpScratch l = qp_layout(scratch, mf, nf);
+  if (dtype == MXLO_F64)
+    MXLO_TRY(geqp3_t<double>(ctx, (const double *)M, ldm, m_trans ? 1 : 0, (double *)W, ldw, mf, nf, jpvt, rtol, l, info_dev));
+  else MXLO_TRY(geqp3_t<float>(ctx, (const float *)M, ldm, m_trans ? 1 : 0, (float *)W, ldw, mf, nf, jpvt, rtol, l, info_dev));
+  int32_t words[2] = {0, 0};
+  MXLO_HIP(hipMemcpyAsync(words, info_dev, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
+  MXLO_HIP(hipStreamSynchronize(ctx->stream));
+  *info = words[0];
+  *rank = words[1];
+  if (words[0] != 0 || words[1] < 1) return MXLO_OK;
+  if (dtype == MXLO_F64) return geqp3_finish_t<double>(ctx, (const double *)W, ldw, mf, words[1], tfac, dinv, l);
+  return geqp3_finish_t<float>(ctx, (const float *)W, ldw, mf, words[1], tfac, dinv, l);
+}
+
+MXLO_API int32_t mxlo_qrp_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t mf, int64_t nf,
+                              const double *tfac, const double *dinv, const int32_t *jpvt, int64_t rank, double *work, const void *v,
+                              int32_t op_mode, double alpha, double beta) {
+  const char *what = "mxlo_qrp_mul";
+  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
+  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
+  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "%s: op_mode %d", what, op_mode);
+  MXLO_REQUIRE(nf >= 1 && mf >= nf && ldw >= mf && mf < (1LL << 31) - NB, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld (1 <= nf <= mf), ldw = %lld",
+               what, (long long)mf, (long long)nf, (long long)ldw);
+  MXLO_REQUIRE(rank >= 1 && rank <= nf, MXLO_ESHAPE, "%s: rank = %lld (1 <= rank <= nf = %lld)", what, (long long)rank, (long long)nf);
+  MXLO_REQUIRE(res && W && tfac && dinv && jpvt && work && v, MXLO_EINVAL, "%s: null operand", what);
+  const bool tr = op_mode != MXLO_OP_N;
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4, nb = (nf + NB - 1) / NB;
+  const int64_t rb = (tr ? mf : nf) * es, vb = (tr ? nf : mf) * es;
+  MXLO_REQUIRE((res == v && mf == nf) || !bytes_overlap(res, rb, v, vb), MXLO_EINVAL,
+               "%s: res overlaps v without being v (only mul!(x, op, x) of a square operator is defined)", what);
+  const std::pair<const void *, int64_t> own[] = {{W, ((nf - 1) * ldw + mf) * es}, {tfac, nb * NB2 * 8}, {dinv, nb * NB2 * 8},
+                                                  {jpvt, nf * 4},                  {work, qr_work(mf) * 8}};
+  for (const auto &[p, pb] : own)
+    MXLO_REQUIRE(!bytes_overlap(res, rb, p, pb) && !bytes_overlap(v, vb, p, pb), MXLO_EINVAL,
+                 "%s: res / v overlap the factor, the T factors, the block inverses, the permutation or the work vector", what);
+  MXLO_DEVICE_GUARD(ctx);
+  if (dtype == MXLO_F64)
+    return qr_mul_t<double>(ctx, (double *)res, (const double *)W, ldw, mf, rank, tfac, dinv, work, (const double *)v, tr, alpha, beta, jpvt,
+                            nf);
+  return qr_mul_t<float>(ctx, (float *)res, (const float *)W, ldw, mf, rank, tfac, dinv, work, (const float *)v, tr, alpha, beta, jpvt, nf);
+}
+
+MXLO_API int32_t mxlo_qrp_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf,
+                                    int64_t nf, const double *tfac, const double *dinv, const int32_t *jpvt, int64_t rank, double *work,
+                                    const void *V, int64_t ldv, int64_t k, int32_t op_mode, double alpha, double beta) {
+  const char *what = "mxlo_qrp_mul_block";
+  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
+  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
+  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "%s: op_mode %d", what, op_mode);
+  MXLO_REQUIRE(nf >= 1 && mf >= nf && ldw >= mf && mf < (1LL << 31) - NB, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld (1 <= nf <= mf), ldw = %lld",
+               what, (long long)mf, (long long)nf, (long long)ldw);
+  MXLO_REQUIRE(rank >= 1 && rank <= nf, MXLO_ESHAPE, "%s: rank = %lld (1 <= rank <= nf = %lld)", what, (long long)rank, (long long)nf);
+  const bool tr = op_mode != MXLO_OP_N;
+  const int64_t rrows = tr ? mf : nf, vrows = tr ? nf : mf;
+  MXLO_REQUIRE(k >= 0 && ldr >= rrows && ldv >= vrows, MXLO_ESHAPE, "%s: k = %lld, ldr = %lld for %lld rows, ldv = %lld for %lld rows", what,
+               (long long)k, (long long)ldr, (long long)rrows, (long long)ldv, (long long)vrows);
+  if (k == 0) return MXLO_OK;
+  MXLO_REQUIRE(res && W && tfac && dinv && jpvt && work && V, MXLO_EINVAL, "%s: null operand", what);
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4, nb = (nf + NB - 1) / NB;
+  const int64_t rb = ((k - 1) * ldr + rrows) * es, vb = ((k - 1) * ldv + vrows) * es;
+  MXLO_REQUIRE((res == V && ldr == ldv && mf == nf) || !bytes_overlap(res, rb, V, vb), MXLO_EINVAL,
+               "%s: res overlaps V without being V (only mul!(X, op, X) of a square operator, as the same matrix, is defined)", what);
+  const std::pair<const void *, int64_t> own[] = {{W, ((nf - 1) * ldw + mf) * es}, {tfac, nb * NB2 * 8}, {dinv, nb * NB2 * 8},
+                                                  {jpvt, nf * 4},                  {work, qr_block_work(mf, nf) * 8}};
+  for (const auto &[p, pb] : own)
+    MXLO_REQUIRE(!bytes_overlap(res, rb, p, pb) && !bytes_overlap(V, vb, p, pb), MXLO_EINVAL,
+                 "%s: res or V overlaps the factor, the T factors, the block inverses, the permutation or the work space", what);
+  MXLO_DEVICE_GUARD(ctx);
+  if (dtype == MXLO_F64)
+    return for_groups((double *)res, ldr, (const double *)V, ldv, k, [&](double *r, const double *v, Group grp) {
+      return qr_mul_block_t<double>(ctx, r, (const double *)W, ldw, mf, rank, tfac, dinv, work, v, tr, alpha, beta, grp, jpvt, nf);
+    });
+  return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
+    return qr_mul_block_t<float>(ctx, r, (const float *)W, ldw, mf, rank, tfac, dinv, work, v, tr, alpha, beta, grp, jpvt, nf);
   });
 }

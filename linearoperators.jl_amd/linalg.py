@@ -9,11 +9,13 @@ bit-identical to its vector apply. The inverse of a general dense matrix is `opL
 stays triangular-only. A pivoted (Bunch–Kaufman) or sparse LDLᵀ are not provided. `refine=r` on the three
 factorisation operators adds r steps of iterative refinement to every apply (`mxlo_*_mul_refine`), with the residual and the
 iterate in Float64 and a snapshot of M the operator keeps. `opQR` is the rectangular `M \\ v`: least-squares and minimum-norm
-solves through an unpivoted Householder QR (`mxlo_geqrf`, `mxlo_qr_mul`, and `mxlo_qr_mul_block` for matrix operands).
+solves through an unpivoted Householder QR (`mxlo_geqrf`, `mxlo_qr_mul`, and `mxlo_qr_mul_block` for matrix operands), or — `pivot=True` —
+through a column-pivoted, rank-revealing one (`mxlo_geqp3`, `mxlo_qrp_mul`, `mxlo_qrp_mul_block`).
 """
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 
 import torch
 
@@ -460,7 +462,97 @@ def _check_rect(A, name: str):
     return m, k
 
 
-def opQR(A: torch.Tensor):
+def qrp_launches(rank: int) -> int:
+    """Launches of ONE apply of opQR(A, pivot=True) whose numerical rank is `rank`, in either mode: those of the unpivoted
+    apply of a factor with `rank` columns. The entries of a rank-deficient solution that are no pivots are written by the
+    last reflector launch, so the launch the contract allows for them is not spent."""
+    return qr_launches(rank)
+
+
+def qrp_block_launches(rank: int, k: int) -> int:
+    """Launches of a pivoted apply to a matrix with k columns: the chain of one vector apply per group of GROUP columns."""
+    return ((int(k) + GROUP - 1) // GROUP) * qrp_launches(rank)
+
+
+def _check_pivot(pivot, rtol, name: str):
+    """Runs before A is looked at. Returns rtol as a float, or None for the default."""
+    if not isinstance(pivot, bool):
+        raise TypeError(f"{name}: pivot must be a bool, got {type(pivot).__name__}")
+    if rtol is None:
+        return None
+    if isinstance(rtol, bool) or not isinstance(rtol, numbers.Real):
+        raise TypeError(f"{name}: rtol must be None or a real number, got {type(rtol).__name__}")
+    if not pivot:
+        raise ValueError(f"{name}: rtol is the rank tolerance of the pivoted factorisation; it needs pivot=True")
+    if not 0 <= rtol < 1:                               # false for NaN as well
+        raise ValueError(f"{name}: rtol = {rtol} outside 0 <= rtol < 1")
+    return float(rtol)
+
+
+QRP_SLOTS = 64        # most row groups of a step of the pivoted factorisation (QPG of csrc/linalg.hip)
+
+
+def _qr_pivoted(A, m, k, rtol):
+    """opQR(A, pivot=True) once the checks have passed; the storage is opQR's, with the permutation"""
+    T = A.dtype
+    tall = m >= k
+    mf, nf = (m, k) if tall else (k, m)
+    if rtol is None:
+        rtol = max(mf, nf) * float(torch.finfo(T).eps)
+    St, tr = _stored_colmajor(A)
+    m_trans = tall == tr
+    ldm = St.stride(1) if St.shape[1] > 1 else max(1, St.shape[0])
+    ctx = get_ctx(A.device)
+    W = torch.empty((nf, mf), dtype=T, device=A.device).t()           # column-major mf x nf, ld = mf
+    ldw = mf
+    nblk = (nf + BLOCK - 1) // BLOCK
+    tfac = torch.zeros(nblk * BLOCK * BLOCK, dtype=torch.float64, device=A.device)
+    dinv = torch.zeros(nblk * BLOCK * BLOCK, dtype=torch.float64, device=A.device)
+    perm = torch.empty(nf, dtype=torch.int32, device=A.device)
+    work = torch.empty(GROUP * (mf + nf + 2 * QR_SLOTS * BLOCK), dtype=torch.float64, device=A.device)
+    nscratch = 2 * QRP_SLOTS * nf + QRP_SLOTS + 2 * nf + 2 * mf + 2 + QRP_SLOTS * BLOCK * BLOCK
+    scratch = torch.empty(nscratch, dtype=torch.float64, device=A.device)                   # needed by the factorisation only
+    info_dev = torch.zeros(2, dtype=torch.int32, device=A.device)
+    info, rank = C.c_int32(0), C.c_int32(0)
+    code = dtype_code(T)
+    _lib.call("mxlo_geqp3", ctx.handle, code, St.data_ptr(), ldm, 1 if m_trans else 0, W.data_ptr(), ldw, mf, nf, tfac.data_ptr(),
+              dinv.data_ptr(), perm.data_ptr(), rtol, scratch.data_ptr(), nscratch, info_dev.data_ptr(), C.byref(info),
+              C.byref(rank))
+    if info.value != 0:
+        raise SingularException(info.value)
+    r = int(rank.value)
+    # the T factors and the block inverses are made after the read-back, out of the scratch, on the stream the scratch was
+    # allocated on: the allocator hands its memory only to work that this stream runs later
+    del scratch
+    pW, pT, pD, pP, pZ = W.data_ptr(), tfac.data_ptr(), dinv.data_ptr(), perm.data_ptr(), work.data_ptr()
+
+    def solve(res, v, a, b, mode):                      # mulFact!(res, qr(F, ColumnNorm()), v, α, β) — src/linalg.jl:3-9
+        _check_operands(res, v, T)
+        _lib.call("mxlo_qrp_mul", ctx_of(res).handle, code, res.data_ptr(), pW, ldw, mf, nf, pT, pD, pP, r, pZ, v.data_ptr(), mode,
+                  float(a), float(b))
+
+    def block(res, V, a, b, mode):
+        nv, nres = (mf, nf) if mode == _lib.OP_N else (nf, mf)
+        ldr, ldv, cols = _check_block_operands(res, V, T, nv, nres)
+        _lib.call("mxlo_qrp_mul_block", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, mf, nf, pT, pD, pP, r, pZ, V.data_ptr(),
+                  ldv, cols, mode, float(a), float(b))
+
+    fwd, bwd = (_lib.OP_N, _lib.OP_T) if tall else (_lib.OP_T, _lib.OP_N)
+    prod = columnwise(lambda res, v, a, b: solve(res, v, a, b, fwd))
+    tprod = columnwise(lambda res, u, a, b: solve(res, u, a, b, bwd))
+    prod._matrix = lambda res, V, a, b: block(res, V, a, b, fwd)
+    tprod._matrix = lambda res, V, a, b: block(res, V, a, b, bwd)
+    op = LinearOperator(T, k, m, False, False, prod, tprod, tprod, S=Storage(T, A.device))
+    op._deps = (W,)
+    op._tall = tall
+    op._rank = r
+    op._perm = perm
+    op._rtol = rtol
+    op._factor = (W, tfac, dinv, work, perm)            # owned storage (kept alive with the operator)
+    return op
+
+
+def opQR(A: torch.Tensor, pivot: bool = False, rtol=None):
     """opQR(A): the pseudo-inverse A⁺ of a full-rank dense m x k matrix, a k x m operator — what `opInverse(M)` = `M \\ v` of
     src/linalg.jl:27-32 is for a rectangular M: Julia's QR solve. prod!: res = α (A⁺ v) + β res, the least-squares solution
     of A x ≈ v for m >= k and the minimum-norm solution of A x = v for m < k; tprod! = ctprod!: res = α ((A⁺)ᵀ u) + β res, the
@@ -483,9 +575,31 @@ def opQR(A: torch.Tensor):
     apply per GROUP = 8 columns, `qr_block_launches(nf, k)` launches, every element of a reflector panel loaded once per chunk
     of rows for the whole group, each column bit-identical to its vector apply; res may be V (the same matrix) when m == k.
     The work space, allocated once here, is 8 (mf + nf + 2·512·64) Float64; the vector apply uses its first
-    mf + 2·512·64. NOT provided: `refine`, column pivoting or any rank-revealing form (a rank-deficient A
-    that escapes the exact test above gives a meaningless answer), complex element types, Julia glue."""
+    mf + 2·512·64. Without pivoting a rank-deficient A that escapes the exact test above gives a meaningless answer.
+
+    pivot=True: F P = Q R with column pivoting (`mxlo_geqp3`), what Julia's `\\` does for a rectangular matrix. At every step
+    the pivot is the remaining column of largest 2-norm from the diagonal row down, the first one on a tie; the norms are
+    recomputed at every step, never downdated. One column per step, three launches per step, 3 nf + 3 in all, nothing read
+    back in between: BLAS-2 work, about 2·sizeof(T)·Σ_c (mf − c)(nf − c) bytes, paid once here. The numerical rank r is the
+    length of the leading run of j with |R_jj| > rtol·|R_11|; rtol defaults to max(mf, nf)·eps(T) and must satisfy
+    0 <= rtol < 1 (rtol without pivot=True is a ValueError). The rank is decided on the device and read back together with
+    the info word, the one synchronisation of the construction. `op._rank` = r, `op._perm` (int32, device, nf entries):
+    F[:, op._perm[j]] is column j of Q R, `op._rtol`; `op._factor` = (W, T, dinv, work, perm). A rank-deficient A, zero columns
+    included, raises nothing; `SingularException(info)` only when a remaining column norm at step info is not finite (a NaN
+    counts as the largest), or info = 1 for A == 0.
+    The solves are the BASIC solution of rank r: prod! of a tall A gives x[perm[0:r]] = R11⁻¹ (Qᵀv)[0:r] with the other
+    nf − r entries exactly zero before the α, β epilogue; the transposed mode gives y = Q[:, 0:r] R11⁻ᵀ u[perm[0:r]]. For r = nf
+    these are the unique least-squares / minimum-norm solutions, as without pivoting. For r < nf they are A least-squares
+    solution and, when the system is consistent, A solution — NOT the minimum-norm ones that Julia's complete orthogonal
+    decomposition returns (the further `tzrzf` step is not provided). An apply runs the unpivoted apply's kernels on the
+    leading r columns, `qrp_launches(r)` = `qr_launches(r)` launches (`qrp_block_launches(r, k)` for a matrix operand), with
+    every promise of the paragraph above.
+
+    NOT provided: `refine`, minimum-norm solutions of rank-deficient problems, complex element types, Julia glue."""
+    rtol = _check_pivot(pivot, rtol, "opQR")
     m, k = _check_rect(A, "opQR")
+    if pivot:
+        return _qr_pivoted(A, m, k, rtol)
     T = A.dtype
     tall = m >= k
     mf, nf = (m, k) if tall else (k, m)

@@ -39,6 +39,12 @@ model: the factor once per group of 8 columns, ⌈k/8⌉·(mf·nf + nf²/2)·siz
 form MFxNF.
 
     python tools/bench_linalg.py --qr [MFxNF ...] > profiles/linalg_qr.txt
+
+--qrp: opQR(A, pivot=True) on the matrices of --qr, each row beside the unpivoted one of the same run: the factorisation (rated
+by its byte model, 2·sizeof(T)·Σ_c (mf − c)(nf − c)) and the vector apply in both modes at rank nf, where the two run the same
+kernels; the last column is the time over the unpivoted row's.
+
+    python tools/bench_linalg.py --qrp [MFxNF ...] > profiles/linalg_qrp.txt
 """
 import ctypes as C
 import os
@@ -264,6 +270,53 @@ def qr_legs():
             torch.cuda.empty_cache()
 
 
+def qrp_legs():
+    """opQR(A, pivot=True) beside opQR(A) in the same run: see the module docstring"""
+    print(f"# {torch.cuda.get_device_name(0)}; opQR(A, pivot=True) beside opQR(A); ms per call, median of 3 event-timed windows, "
+          f"spread = (max - min) / median")
+    print(f"# factorisation: construction, allocations and the one synchronisation included; model bytes of the pivoted one: "
+          f"2 sizeof(T) sum_c (mf - c)(nf - c). apply: (mf nf + nf^2 / 2) sizeof(T), at rank nf; peak {PEAK:.0f} GB/s")
+    print(f"{'case':44s} {'mf':>8s} {'nf':>5s} {'ms':>10s} {'spread':>6s} {'launch':>6s} {'GB/s':>8s} {'%peak':>6s} {'x plain':>8s}", flush=True)
+    shapes = [tuple(int(x) for x in a.split("x")) for a in sys.argv[1:] if "x" in a] or [(1000000, 128), (8192, 8192)]
+    for dtype, tag in ((torch.float64, "f64"), (torch.float32, "f32")):
+        es = 8 if dtype is torch.float64 else 4
+        for mf, nf in shapes:
+            gen = torch.Generator(device=dev).manual_seed(mf + nf)
+            A = torch.randn(nf, mf, dtype=dtype, device=dev, generator=gen).t()           # the matrices of --qr
+            if mf == nf:
+                A = A + (nf ** 0.5) * torch.eye(nf, dtype=dtype, device=dev)
+            v = torch.randn(mf, dtype=dtype, device=dev, generator=gen)
+            u = torch.randn(nf, dtype=dtype, device=dev, generator=gen)
+            x, y = torch.empty_like(u), torch.empty_like(v)
+            nbytes = (mf * nf + nf * nf // 2) * es
+            fbytes = 2 * es * sum((mf - c) * (nf - c) for c in range(nf))
+            reps = 10 if mf * nf <= 2 ** 27 else 5
+            base = {}
+
+            def row(name, fn, reps, nbytes, nl, key=None):
+                ms = timeit(fn, reps)
+                gbs = nbytes / ms / 1e6 if nbytes else 0.0
+                ratio = f"{ms / base[key]:8.3f}" if key in base else f"{'':8s}"
+                base.setdefault(key, ms)
+                print(f"{name + ' ' + tag:44s} {mf:8d} {nf:5d} {ms:10.4f} {100 * timeit.spread:5.1f}% {nl:6d} {gbs:8.1f} {100 * gbs / PEAK:6.2f} "
+                      f"{ratio}", flush=True)
+
+            row("opQR(A) factorisation", lambda: lo.opQR(A), 1, 0, 0, "f")
+            row("opQR(A, pivot=True) factorisation", lambda: lo.opQR(A, pivot=True), 1, fbytes, 0, "f")
+            plain, piv = lo.opQR(A), lo.opQR(A, pivot=True)
+            assert piv._rank == nf, piv._rank
+            for name, res, w, wp, rhs, key in (("apply (least squares)", x, plain, piv, v, "n"),
+                                               ("transposed apply (minimum norm)", y, plain.T, piv.T, u, "t")):
+                row("opQR " + name, lambda: lo.mul(res, w, rhs, 1.0, 0.0), reps, nbytes, launches(lambda: lo.mul(res, w, rhs, 1.0, 0.0)), key)
+                row("pivoted " + name, lambda: lo.mul(res, wp, rhs, 1.0, 0.0), reps, nbytes,
+                    launches(lambda: lo.mul(res, wp, rhs, 1.0, 0.0)), key)
+            del plain, piv, A
+            torch.cuda.empty_cache()
+
+
+if "--qrp" in sys.argv:
+    qrp_legs()
+    sys.exit(0)
 if "--qr" in sys.argv:
     qr_legs()
     sys.exit(0)
