@@ -1046,6 +1046,49 @@ int32_t mxlo_qrp_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr,
                            const double *tfac, const double *dinv, const int32_t *jpvt, int64_t rank, double *work, const void *V,
                            int64_t ldv, int64_t k, int32_t op_mode, double alpha, double beta);
 
+/* opPinv — the pseudo-inverse of a RANK-DEFICIENT rectangular M: the minimum-norm least-squares solution Julia's `M \ v`
+ * returns through a complete orthogonal decomposition. On top of mxlo_geqp3's F P = Q1 [R11 R12; 0 0] of numerical rank r < nf,
+ * mxlo_cod_factor takes S = [R11 R12]' (nf x rank, of full column rank since |R_jj| > rtol |R_11| > 0 for j < rank) out of
+ * the leading `rank` rows of W — one launch over 64 x 64 tiles turned through LDS, reads and writes both of unit stride,
+ * zeros where W holds reflector vectors — into W2 (nf x rank, column-major, ld = nf, the element type of W) and factors it
+ * there as S = Q2 R2 with mxlo_geqrf's chain (LAPACK's layout; tfac2 and dinv2: ceil(rank/64) blocks of 64 x 64 doubles each,
+ * tfac2 must come zeroed). Then [R11 R12] = R2' Q2' and
+ *   pinv(F) = P Q2 inv(R2') [I_r 0] Q1',     pinv(F)' = Q1 [I_r; 0] inv(R2) Q2' P'.
+ * Q2 is a general orthogonal factor, nf x rank reflector vectors; LAPACK's tzrzf, which uses the triangle of R11 (reflectors
+ * of length 1 + nf - rank), is not what this is. W is read (rows < rank only; ldw >= nf), never written. *info: as
+ * mxlo_geqrf's — with S of full column rank it can be non-zero only through rounding or a non-finite entry — copied once after
+ * the last launch, the only synchronisation. Not capturable (MXLO_ESTATE). scratch: scratch_len >= mxlo_geqrf's for nf := rank,
+ * 2 (512 * 64 + 64) + (512 + 2 ceil(rank/64)) * 4096 doubles, needed during the call only. info_dev is one device word.
+ * No two operands may overlap. Memory kept: one more nf x rank factor and two tables of ceil(rank/64) * 64^2 doubles. */
+int32_t mxlo_cod_factor(mxlo_ctx *ctx, int32_t dtype, const void *W, int64_t ldw, int64_t nf, int64_t rank, void *W2, double *tfac2,
+                        double *dinv2, double *scratch, int64_t scratch_len, int32_t *info_dev, int32_t *info);
+/* res = alpha pinv(F) v + beta res (MXLO_OP_N: v mf entries, res nf) or alpha pinv(F)' u + beta res (MXLO_OP_T / MXLO_OP_C: u nf
+ * entries, res mf), with W, tfac, jpvt, rank of mxlo_geqp3 and W2, tfac2, dinv2 of mxlo_cod_factor; 1 <= rank < nf (rank == nf
+ * is mxlo_qrp_mul's, MXLO_ESHAPE here). Two reflector chains of mxlo_qr_mul's kernel joined by one sweep of mxlo_trisolve_mul's:
+ * N — Q1' over the leading rank columns of W (ceil(rank/64) + 1 launches), w = inv(R2') z[0:rank] (ceil(rank/64)), Q2 [w; 0]
+ * over the nf rows of W2 (ceil(rank/64) + 1), whose last launch writes res[jpvt[i]] = alpha z[i] + beta res[jpvt[i]], every
+ * entry of res once; T — Q2' over W2, the first launch reading z[i] = u[jpvt[i]], w = inv(R2) z[0:rank], Q1 [w; 0] over W, the
+ * last launch writing res. jpvt is read once per chunk of 64 rows by those two launches only; there is no permutation launch
+ * and no further pass over res. EXACTLY 3 ceil(rank/64) + 2 launches in both modes, whatever mf is, and nothing else: no
+ * allocation, copy or synchronisation, capturable; all sums in a fixed order in f64: bit-reproducible. Bytes: each chain
+ * streams its panels twice, about 2 (mf + nf) rank sizeof(T), where mxlo_qrp_mul streams 2 mf rank.
+ * work: mxlo_qr_mul's mf + 2 * 512 * 64 doubles — the second chain's z has nf <= mf rows and the two chains use the same slots
+ * one after the other. res == v is allowed when mf == nf (the first launch has read all of v before the last writes res);
+ * any other overlap of res and v, or of either with W, tfac, jpvt, W2, tfac2, dinv2 or work, is MXLO_EINVAL before anything
+ * is launched. With beta == 0 res is not read. */
+int32_t mxlo_pinv_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t mf, int64_t nf, const double *tfac,
+                      const int32_t *jpvt, int64_t rank, const void *W2, const double *tfac2, const double *dinv2, double *work,
+                      const void *v, int32_t op_mode, double alpha, double beta);
+/* mxlo_pinv_mul on k columns, as mxlo_qr_mul_block is to mxlo_qr_mul: groups of 8 columns, ceil(k/8) (3 ceil(rank/64) + 2)
+ * launches, column j BIT FOR BIT the vector apply of column j. Operands as mxlo_qrp_mul_block (MXLO_OP_N: V mf x k, res nf x k;
+ * MXLO_OP_T: V nf x k, res mf x k). work: mxlo_qr_mul_block's 8 (mf + nf + 2 * 512 * 64) doubles — z of the second chain is
+ * nf x 8 <= mf x 8 and the sweep's matrix rank x 8 <= nf x 8. k == 0: MXLO_OK, nothing is launched. res == V only when mf == nf,
+ * with the same leading dimension. */
+int32_t mxlo_pinv_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf, int64_t nf,
+                            const double *tfac, const int32_t *jpvt, int64_t rank, const void *W2, const double *tfac2,
+                            const double *dinv2, double *work, const void *V, int64_t ldv, int64_t k, int32_t op_mode, double alpha,
+                            double beta);
+
 #ifdef __cplusplus
 }
 #endif

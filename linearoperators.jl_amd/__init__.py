@@ -33,7 +33,7 @@ from .diagqn import DiagonalAndrei, DiagonalBFGS, DiagonalPSB, SpectralGradient
 from .graph import CapturedSequence, capture_mul
 from .utilities import check_ctranspose, check_hermitian, check_positive_definite, normest
 from .opnorm import estimate_opnorm
-from .linalg import PosDefException, SingularException, ZeroPivotException, opCholesky, opInverse, opLDL, opLU, opQR
+from .linalg import PosDefException, SingularException, ZeroPivotException, opCholesky, opInverse, opLDL, opLU, opPinv, opQR
 
 try:
     from . import sharded

@@ -210,6 +210,12 @@ _PROTOS = {
                    C.POINTER(_i32)],
     "mxlo_qrp_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _dbl, _dbl],
     "mxlo_qrp_mul_block": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _dbl, _dbl],
+    # opPinv: (W, ldw, nf, rank), W2, tfac2, dinv2, (scratch, scratch_len), info_dev, info / the applies: mxlo_qrp_mul's with
+    # (W2, tfac2, dinv2) in place of dinv, after (jpvt, rank)
+    "mxlo_cod_factor": [_vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, C.POINTER(_i32)],
+    "mxlo_pinv_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl],
+    "mxlo_pinv_mul_block": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32,
+                            _dbl, _dbl],
 }
 
 

@@ -1995,6 +1995,9 @@ inline int64_t geqrf_scratch(int64_t nf) {
 }
 
 template <typename T>
+int32_t geqrf_chain_t(mxlo_ctx *ctx, T *W, int64_t ldw, int64_t mf, int64_t nf, double *tfac, double *dinv, double *fwork, int *info_dev);
+
+template <typename T>
 int32_t geqrf_t(mxlo_ctx *ctx, const T *M, int64_t ldm, int trans, T *W, int64_t ldw, int64_t mf, int64_t nf, double *tfac, double *dinv,
                 double *fwork, int *info_dev) {
   const int64_t nb = (nf + NB - 1) / NB;
@@ -2002,6 +2005,13 @@ int32_t geqrf_t(mxlo_ctx *ctx, const T *M, int64_t ldm, int trans, T *W, int64_t
   hipLaunchKernelGGL((qr_copy_kernel<T>), dim3((unsigned)((mf + NB - 1) / NB), (unsigned)nb), dim3(kBlock), 0, ctx->stream, W, ldw, M, ldm,
                      trans, mf, nf);
   MXLO_LAUNCH_CHECK();
+  return geqrf_chain_t<T>(ctx, W, ldw, mf, nf, tfac, dinv, fwork, info_dev);
+}
+
+// geqrf_t once W holds F and *info_dev is zero: the panels, the trailing updates and the block inverses of R
+template <typename T>
+int32_t geqrf_chain_t(mxlo_ctx *ctx, T *W, int64_t ldw, int64_t mf, int64_t nf, double *tfac, double *dinv, double *fwork, int *info_dev) {
+  const int64_t nb = (nf + NB - 1) / NB;
   double *pb[2] = {fwork, fwork + (int64_t)QG * NB}, *db[2] = {fwork + 2 * (int64_t)QG * NB, fwork + 2 * (int64_t)QG * NB + NB};
   double *ypart = fwork + 2 * (int64_t)QG * NB + 2 * NB;
   for (int64_t k = 0; k < nb; ++k) {
@@ -2061,9 +2071,11 @@ struct QrArgs {
   int zc_out;            // nf), which load 2 reads rows < nf from and which the launch with zc_out writes them to instead of z
   const int *fill_idx;   // pivoted form, or NULL: this launch also writes res[fill_idx[i]] = alpha 0 + beta res[..] for fill_lo <= i <
   int64_t fill_lo, fill_hi;      // fill_hi, the entries of a rank-deficient solution that are no pivots (every column of a group)
-};
+  const int *idx;        // opPinv, or NULL: the launch with load 1 reads row r of z from v[idx[r]], the one with epi writes it to
+};                       // res[idx[r]]; read once per chunk of rows, outside the loops over the columns. Such a launch runs the IDX
+                         // instantiation of its kernel; the others run the code they ran before there was an idx
 
-template <typename T, bool BETA0>
+template <typename T, bool BETA0, bool IDX>
 __global__ void __launch_bounds__(kBlock) qr_reflect_kernel(QrArgs a) {
   __shared__ double sd[NB], sw[NB], spart[4][NB], sT[NB * (NB + 1)];
   const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
@@ -2091,7 +2103,7 @@ __global__ void __launch_bounds__(kBlock) qr_reflect_kernel(QrArgs a) {
     const int64_t r = ch * NB + lane;
     const bool in = r < a.mf;
     double zr = 0.0;
-    if (in) zr = a.load == 1 ? (double)((const T *)a.v)[r] : ((a.load == 2 && r >= a.nf) ? 0.0 : a.z[r]);
+    if (in) zr = a.load == 1 ? (double)((const T *)a.v)[IDX ? (int64_t)a.idx[r] : r] : ((a.load == 2 && r >= a.nf) ? 0.0 : a.z[r]);
     if (a.jbp) {
       double part = 0.0;
 #pragma unroll
@@ -2106,7 +2118,7 @@ __global__ void __launch_bounds__(kBlock) qr_reflect_kernel(QrArgs a) {
       __syncthreads();
     }
     if (q == 0 && in) {
-      if (a.epi) store_res<T, BETA0>((T *)a.res, r, zr, a.alpha, a.beta);
+      if (a.epi) store_res<T, BETA0>((T *)a.res, IDX ? (int64_t)a.idx[r] : r, zr, a.alpha, a.beta);
       else a.z[r] = zr;
     }
     if (a.jbn) {
@@ -2133,8 +2145,11 @@ __global__ void __launch_bounds__(kBlock) qr_reflect_kernel(QrArgs a) {
 template <typename T>
 int32_t launch_reflect(mxlo_ctx *ctx, const QrArgs &a) {
   const unsigned G = (unsigned)qr_grid(a.mf);
-  if (a.beta == 0.0) hipLaunchKernelGGL((qr_reflect_kernel<T, true>), dim3(G), dim3(kBlock), 0, ctx->stream, a);
-  else hipLaunchKernelGGL((qr_reflect_kernel<T, false>), dim3(G), dim3(kBlock), 0, ctx->stream, a);
+  if (a.idx) {
+    if (a.beta == 0.0) hipLaunchKernelGGL((qr_reflect_kernel<T, true, true>), dim3(G), dim3(kBlock), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((qr_reflect_kernel<T, false, true>), dim3(G), dim3(kBlock), 0, ctx->stream, a);
+  } else if (a.beta == 0.0) hipLaunchKernelGGL((qr_reflect_kernel<T, true, false>), dim3(G), dim3(kBlock), 0, ctx->stream, a);
+  else hipLaunchKernelGGL((qr_reflect_kernel<T, false, false>), dim3(G), dim3(kBlock), 0, ctx->stream, a);
   MXLO_LAUNCH_CHECK();
   return MXLO_OK;
 }
@@ -2178,7 +2193,7 @@ int32_t qr_mul_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t mf, int6
 //   z: wave j < kb holds z of right-hand side j for the chunk's rows and passes it to the dots through LDS.
 constexpr int QBT = 1024;            // threads of qr_reflect_block_kernel
 
-template <typename T, bool BETA0>
+template <typename T, bool BETA0, bool IDX>
 __global__ void __launch_bounds__(QBT) qr_reflect_block_kernel(QrArgs a) {
   __shared__ double sTV[NB * (NB + 1)];                  // the prologue's T, as the vector kernel lays it out; then the chunk of V_p [c][row]
   __shared__ double sd[KB][NB], sw[NB][KB], spart[KB][4][NB], sz[KB][NB];
@@ -2223,7 +2238,7 @@ __global__ void __launch_bounds__(QBT) qr_reflect_block_kernel(QrArgs a) {
     const bool in = r < a.mf;
     double zr = 0.0;
     if (wv < kb && in) {
-      if (a.load == 1) zr = (double)((const T *)a.v)[r + wv * a.ldv];
+      if (a.load == 1) zr = (double)((const T *)a.v)[(IDX ? (int64_t)a.idx[r] : r) + wv * a.ldv];
       else if (a.load == 2) zr = r < a.nf ? a.zc[r + wv * a.nf] : 0.0;
       else zr = a.z[r + wv * a.mf];
     }
@@ -2261,7 +2276,7 @@ __global__ void __launch_bounds__(QBT) qr_reflect_block_kernel(QrArgs a) {
     }
     if (wv < kb) {
       if (in) {
-        if (a.epi) store_res<T, BETA0>((T *)a.res + wv * a.ldr, r, zr, a.alpha, a.beta);
+        if (a.epi) store_res<T, BETA0>((T *)a.res + wv * a.ldr, IDX ? (int64_t)a.idx[r] : r, zr, a.alpha, a.beta);
         else if (!a.zc_out) a.z[r + wv * a.mf] = zr;
         else if (r < a.nf) a.zc[r + wv * a.nf] = zr;
       }
@@ -2304,8 +2319,11 @@ __global__ void __launch_bounds__(QBT) qr_reflect_block_kernel(QrArgs a) {
 template <typename T>
 int32_t launch_reflect_block(mxlo_ctx *ctx, const QrArgs &a) {
   const unsigned G = (unsigned)qr_grid(a.mf);
-  if (a.beta == 0.0) hipLaunchKernelGGL((qr_reflect_block_kernel<T, true>), dim3(G), dim3(QBT), 0, ctx->stream, a);
-  else hipLaunchKernelGGL((qr_reflect_block_kernel<T, false>), dim3(G), dim3(QBT), 0, ctx->stream, a);
+  if (a.idx) {
+    if (a.beta == 0.0) hipLaunchKernelGGL((qr_reflect_block_kernel<T, true, true>), dim3(G), dim3(QBT), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((qr_reflect_block_kernel<T, false, true>), dim3(G), dim3(QBT), 0, ctx->stream, a);
+  } else if (a.beta == 0.0) hipLaunchKernelGGL((qr_reflect_block_kernel<T, true, false>), dim3(G), dim3(QBT), 0, ctx->stream, a);
+  else hipLaunchKernelGGL((qr_reflect_block_kernel<T, false, false>), dim3(G), dim3(QBT), 0, ctx->stream, a);
   MXLO_LAUNCH_CHECK();
   return MXLO_OK;
 }
@@ -2346,6 +2364,90 @@ int32_t qr_mul_block_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t mf
   if (trans) return MXLO_OK;
   return sweep<T>(ctx, W, ld, nf, true, false, dinv, a.zc, (const T *)nullptr, true, false, true, res, alpha, beta, nullptr, nullptr,
                   nullptr, jpvt, false, grp);
+}
+
+// ---------------------------------------------------------------------------------------------- cod / pinv_mul
+// opPinv for a numerical rank r < nf: the complete orthogonal decomposition on top of geqp3's F P = Q1 [R11 R12; 0 0]. With
+// S = [R11 R12]' (nf x r, full column rank) factored as S = Q2 R2 by the unpivoted chain above, [R11 R12] = R2' Q2' and
+//   pinv(F) = P Q2 inv(R2') [I_r 0] Q1',    pinv(F)' = Q1 [I_r; 0] inv(R2) Q2' P'.
+// An apply is two reflector chains joined by one sweep with R2: 3 ceil(r/64) + 2 launches.
+
+// W2 = S: W2[i, c] = W[c, i] for c <= i, zero above the diagonal (where W holds reflector vectors); an NB x NB tile of W is
+// read with unit stride along its rows c and written with unit stride along i, turned through LDS as qr_copy_kernel does
+template <typename T>
+__global__ void __launch_bounds__(kBlock) cod_extract_kernel(T *__restrict__ W2, const T *__restrict__ W, int64_t ldw, int64_t nf,
+                                                             int64_t rank) {
+  __shared__ T s[NB * (NB + 1)];
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int64_t i0 = (int64_t)blockIdx.x * NB, c0 = (int64_t)blockIdx.y * NB;
+  for (int il = q; il < NB; il += 4) {
+    const int64_t i = i0 + il, c = c0 + lane;
+    s[il * (NB + 1) + lane] = (i < nf && c < rank && c <= i) ? W[c + i * ldw] : T(0);
+  }
+  __syncthreads();
+  for (int cl = q; cl < NB; cl += 4) {
+    const int64_t i = i0 + lane, c = c0 + cl;
+    if (i < nf && c < rank) W2[i + c * nf] = s[lane * (NB + 1) + cl];
+  }
+}
+
+template <typename T>
+int32_t cod_factor_t(mxlo_ctx *ctx, const T *W, int64_t ldw, int64_t nf, int64_t rank, T *W2, double *tfac2, double *dinv2,
+                     double *fwork, int *info_dev) {
+  MXLO_HIP(hipMemsetAsync(info_dev, 0, sizeof(int), ctx->stream));
+  hipLaunchKernelGGL((cod_extract_kernel<T>), dim3((unsigned)((nf + NB - 1) / NB), (unsigned)((rank + NB - 1) / NB)), dim3(kBlock), 0,
+                     ctx->stream, W2, W, ldw, nf, rank);
+  MXLO_LAUNCH_CHECK();
+  return geqrf_chain_t<T>(ctx, W2, nf, nf, rank, tfac2, dinv2, fwork, info_dev);
+}
+
+// One reflector chain of a pinv apply, the nb + 1 launches of qr_mul_t's loop, over the leading nc columns of a factor with
+// `rows` rows. a carries what the two chains share (z, res, alpha, beta, the group). !trans: Q', the FIRST stage — launch 0
+// loads v (through idx if given), the last launch of a group writes rows < nc to zc. trans: Q, the LAST stage — launch 0 takes
+// rows < nc from z (zc) and zero below, the last launch writes res (through idx if given).
+template <typename T>
+int32_t pinv_chain(mxlo_ctx *ctx, QrArgs a, const T *W, int64_t ld, int64_t rows, int64_t nc, const double *tfac, double *const *pb,
+                   bool trans, const T *v, const int *idx) {
+  const int64_t nb = (nc + NB - 1) / NB;
+  a.W = W; a.ld = ld; a.mf = rows; a.nf = nc; a.tp_trans = trans ? 0 : 1;
+  for (int64_t i = 0; i <= nb; ++i) {                    // launch i reads the slots (i + 1) & 1 and leaves the slots i & 1
+    const int64_t kp = trans ? nb - i : i - 1, kn = trans ? nb - 1 - i : i;
+    a.v = (!trans && i == 0) ? v : nullptr;
+    a.load = i == 0 ? (trans ? 2 : 1) : 0;
+    a.jbp = a.jbn = 0;
+    if (i > 0) { a.jp = kp * NB; a.jbp = (int)(nc - a.jp < NB ? nc - a.jp : NB); a.tp = tfac + kp * NB2; }
+    if (i < nb) { a.jn = kn * NB; a.jbn = (int)(nc - a.jn < NB ? nc - a.jn : NB); }
+    a.pin = pb[(i + 1) & 1]; a.pout = pb[i & 1];
+    a.epi = trans && i == nb;
+    a.zc_out = a.kb > 0 && !trans && i == nb;
+    a.idx = ((!trans && i == 0) || a.epi) ? idx : nullptr;
+    MXLO_TRY(a.kb > 0 ? launch_reflect_block<T>(ctx, a) : launch_reflect<T>(ctx, a));
+  }
+  return MXLO_OK;
+}
+
+// The factor of geqp3 (W, tfac; mf x nf, rank r < nf), the permutation and the second factor (W2: nf x r with ld nf, tfac2,
+// dinv2). N: res (nf) — Q1' over the leading r columns of W, w = inv(R2') z[0:r], Q2 [w; 0] over the nf rows of W2 with
+// res[jpvt[i]] written by the epilogue. T: res (mf) — Q2' over W2 with z[i] = u[jpvt[i]] gathered by launch 0, w = inv(R2)
+// z[0:r], Q1 [w; 0]. work is qr_mul_t's (grp.kb == 0) or qr_mul_block_t's: the second chain's z has nf <= mf rows, its sweep
+// matrix r <= nf, and both chains use the same two sets of slots, so nothing more is needed.
+template <typename T>
+int32_t pinv_mul_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t mf, int64_t nf, const double *tfac, const int *jpvt, int64_t r,
+                   const T *W2, const double *tfac2, const double *dinv2, double *work, const T *v, bool trans, double alpha, double beta,
+                   Group grp = {}) {
+  const bool blk = grp.kb > 0;
+  const int64_t slots = (int64_t)(blk ? KB : 1) * QG * NB, zlen = (blk ? KB : 1) * mf;
+  double *pb[2] = {work + zlen, work + zlen + slots};
+  QrArgs a{};
+  a.z = work; a.res = res; a.alpha = alpha; a.beta = beta;
+  a.kb = grp.kb; a.ldr = grp.ldr; a.ldv = grp.ldv; a.zc = blk ? pb[1] + slots : nullptr;
+  double *zs = blk ? a.zc : work;                        // what the sweep works on: r x kb with column stride r, or z[0:r]
+  if (!trans) MXLO_TRY(pinv_chain<T>(ctx, a, W, ld, mf, r, tfac, pb, false, v, nullptr));
+  else MXLO_TRY(pinv_chain<T>(ctx, a, W2, nf, nf, r, tfac2, pb, false, v, jpvt));
+  MXLO_TRY(sweep<T>(ctx, W2, nf, r, true, !trans, dinv2, zs, (const T *)nullptr, true, false, false, res, alpha, beta, nullptr, nullptr,
+                    nullptr, nullptr, false, grp));
+  if (!trans) return pinv_chain<T>(ctx, a, W2, nf, nf, r, tfac2, pb, true, (const T *)nullptr, jpvt);
+  return pinv_chain<T>(ctx, a, W, ld, mf, r, tfac, pb, true, (const T *)nullptr, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------- geqp3
@@ -2887,5 +2989,101 @@ MXLO_API int32_t mxlo_qrp_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int
     });
   return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
     return qr_mul_block_t<float>(ctx, r, (const float *)W, ldw, mf, rank, tfac, dinv, work, v, tr, alpha, beta, grp, jpvt, nf);
+  });
+}
+
+MXLO_API int32_t mxlo_cod_factor(mxlo_ctx *ctx, int32_t dtype, const void *W, int64_t ldw, int64_t nf, int64_t rank, void *W2,
+                                 double *tfac2, double *dinv2, double *scratch, int64_t scratch_len, int32_t *info_dev, int32_t *info) {
+  const char *what = "mxlo_cod_factor";
+  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
+  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
+  MXLO_REQUIRE(nf >= 1 && ldw >= nf, MXLO_ESHAPE, "%s: nf = %lld (nf >= 1), ldw = %lld (ldw >= mf >= nf)", what, (long long)nf,
+               (long long)ldw);
+  MXLO_REQUIRE(nf < (1LL << 31) - NB && (nf + NB - 1) / NB <= 65535, MXLO_ESHAPE, "%s: nf = %lld is too large", what, (long long)nf);
+  MXLO_REQUIRE(rank >= 1 && rank <= nf, MXLO_ESHAPE, "%s: rank = %lld (1 <= rank <= nf = %lld)", what, (long long)rank, (long long)nf);
+  MXLO_REQUIRE(W && W2 && tfac2 && dinv2 && scratch && info_dev && info, MXLO_EINVAL, "%s: null operand", what);
+  *info = 0;
+  MXLO_REQUIRE(scratch_len >= geqrf_scratch(rank), MXLO_ESHAPE, "%s: scratch of %lld doubles, %lld needed", what, (long long)scratch_len,
+               (long long)geqrf_scratch(rank));
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4, nb = (rank + NB - 1) / NB;
+  const std::pair<const void *, int64_t> bufs[] = {{W, ((nf - 1) * ldw + rank) * es}, {W2, nf * rank * es},  {tfac2, nb * NB2 * 8},
+                                                   {dinv2, nb * NB2 * 8},             {scratch, scratch_len * 8}, {info_dev, 4}};
+  for (size_t x = 0; x < 6; ++x)
+    for (size_t y = x + 1; y < 6; ++y)
+      MXLO_REQUIRE(!bytes_overlap(bufs[x].first, bufs[x].second, bufs[y].first, bufs[y].second), MXLO_EINVAL,
+                   "%s: the factor, the second factor, its T factors, its block inverses, the scratch and the info word overlap", what);
+  MXLO_REQUIRE(!ctx->capturing, MXLO_ESTATE, "%s: reads its info word back, which a graph capture cannot hold", what);
+  MXLO_DEVICE_GUARD(ctx);
+  if (dtype == MXLO_F64)
+    MXLO_TRY(cod_factor_t<double>(ctx, (const double *)W, ldw, nf, rank, (double *)W2, tfac2, dinv2, scratch, info_dev));
+  else MXLO_TRY(cod_factor_t<float>(ctx, (const float *)W, ldw, nf, rank, (float *)W2, tfac2, dinv2, scratch, info_dev));
+  MXLO_HIP(hipMemcpyAsync(info, info_dev, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MXLO_HIP(hipStreamSynchronize(ctx->stream));
+  return MXLO_OK;
+}
+
+namespace {
+// the checks mxlo_pinv_mul and mxlo_pinv_mul_block share, mxlo_qrp_mul_block's with the second factor; a vector is k = 1
+int32_t check_pinv(mxlo_ctx *ctx, int32_t dtype, const void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf, int64_t nf,
+                   const double *tfac, const int32_t *jpvt, int64_t rank, const void *W2, const double *tfac2, const double *dinv2,
+                   const double *work, int64_t work_len, const void *V, int64_t ldv, int64_t k, int32_t op_mode, const char *what) {
+  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
+  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
+  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "%s: op_mode %d", what, op_mode);
+  MXLO_REQUIRE(nf >= 1 && mf >= nf && ldw >= mf && mf < (1LL << 31) - NB, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld (1 <= nf <= mf), ldw = %lld",
+               what, (long long)mf, (long long)nf, (long long)ldw);
+  MXLO_REQUIRE(rank >= 1 && rank < nf, MXLO_ESHAPE, "%s: rank = %lld (1 <= rank < nf = %lld; rank == nf is mxlo_qrp_mul's)", what,
+               (long long)rank, (long long)nf);
+  const bool tr = op_mode != MXLO_OP_N;
+  const int64_t rrows = tr ? mf : nf, vrows = tr ? nf : mf;
+  MXLO_REQUIRE(k >= 0 && ldr >= rrows && ldv >= vrows, MXLO_ESHAPE, "%s: k = %lld, ldr = %lld for %lld rows, ldv = %lld for %lld rows", what,
+               (long long)k, (long long)ldr, (long long)rrows, (long long)ldv, (long long)vrows);
+  if (k == 0) return MXLO_OK;
+  MXLO_REQUIRE(res && W && tfac && jpvt && W2 && tfac2 && dinv2 && work && V, MXLO_EINVAL, "%s: null operand", what);
+  const int64_t es = dtype == MXLO_F64 ? 8 : 4, nb = (rank + NB - 1) / NB;
+  const int64_t rb = ((k - 1) * ldr + rrows) * es, vb = ((k - 1) * ldv + vrows) * es;
+  MXLO_REQUIRE((res == V && ldr == ldv && mf == nf) || !bytes_overlap(res, rb, V, vb), MXLO_EINVAL,
+               "%s: res overlaps v without being v (only mul!(x, op, x) of a square operator, as the same matrix, is defined)", what);
+  const std::pair<const void *, int64_t> own[] = {{W, ((nf - 1) * ldw + mf) * es}, {tfac, nb * NB2 * 8},  {jpvt, nf * 4},    {W2, nf * rank * es},
+                                                  {tfac2, nb * NB2 * 8},           {dinv2, nb * NB2 * 8}, {work, work_len * 8}};
+  for (const auto &[p, pb] : own)
+    MXLO_REQUIRE(!bytes_overlap(res, rb, p, pb) && !bytes_overlap(V, vb, p, pb), MXLO_EINVAL,
+                 "%s: res / v overlap a factor, its T factors, the block inverses, the permutation or the work space", what);
+  return MXLO_OK;
+}
+}  // namespace
+
+MXLO_API int32_t mxlo_pinv_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t mf, int64_t nf,
+                               const double *tfac, const int32_t *jpvt, int64_t rank, const void *W2, const double *tfac2,
+                               const double *dinv2, double *work, const void *v, int32_t op_mode, double alpha, double beta) {
+  const int64_t ldmax = mf > 1 ? mf : 1;                 // one column: any leading dimension >= its rows
+  MXLO_TRY(check_pinv(ctx, dtype, res, ldmax, W, ldw, mf, nf, tfac, jpvt, rank, W2, tfac2, dinv2, work, mf >= 0 ? qr_work(mf) : 0, v, ldmax,
+                      1, op_mode, "mxlo_pinv_mul"));
+  MXLO_DEVICE_GUARD(ctx);
+  const bool tr = op_mode != MXLO_OP_N;
+  if (dtype == MXLO_F64)
+    return pinv_mul_t<double>(ctx, (double *)res, (const double *)W, ldw, mf, nf, tfac, jpvt, rank, (const double *)W2, tfac2, dinv2, work,
+                              (const double *)v, tr, alpha, beta);
+  return pinv_mul_t<float>(ctx, (float *)res, (const float *)W, ldw, mf, nf, tfac, jpvt, rank, (const float *)W2, tfac2, dinv2, work,
+                           (const float *)v, tr, alpha, beta);
+}
+
+MXLO_API int32_t mxlo_pinv_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf,
+                                     int64_t nf, const double *tfac, const int32_t *jpvt, int64_t rank, const void *W2,
+                                     const double *tfac2, const double *dinv2, double *work, const void *V, int64_t ldv, int64_t k,
+                                     int32_t op_mode, double alpha, double beta) {
+  MXLO_TRY(check_pinv(ctx, dtype, res, ldr, W, ldw, mf, nf, tfac, jpvt, rank, W2, tfac2, dinv2, work,
+                      (mf >= 0 && nf >= 0) ? qr_block_work(mf, nf) : 0, V, ldv, k, op_mode, "mxlo_pinv_mul_block"));
+  if (k == 0) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  const bool tr = op_mode != MXLO_OP_N;
+  if (dtype == MXLO_F64)
+    return for_groups((double *)res, ldr, (const double *)V, ldv, k, [&](double *r, const double *v, Group grp) {
+      return pinv_mul_t<double>(ctx, r, (const double *)W, ldw, mf, nf, tfac, jpvt, rank, (const double *)W2, tfac2, dinv2, work, v, tr,
+                                alpha, beta, grp);
+    });
+  return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
+    return pinv_mul_t<float>(ctx, r, (const float *)W, ldw, mf, nf, tfac, jpvt, rank, (const float *)W2, tfac2, dinv2, work, v, tr, alpha,
+                             beta, grp);
   });
 }

@@ -10,7 +10,8 @@ stays triangular-only. A pivoted (Bunch–Kaufman) or sparse LDLᵀ are not prov
 factorisation operators adds r steps of iterative refinement to every apply (`mxlo_*_mul_refine`), with the residual and the
 iterate in Float64 and a snapshot of M the operator keeps. `opQR` is the rectangular `M \\ v`: least-squares and minimum-norm
 solves through an unpivoted Householder QR (`mxlo_geqrf`, `mxlo_qr_mul`, and `mxlo_qr_mul_block` for matrix operands), or — `pivot=True` —
-through a column-pivoted, rank-revealing one (`mxlo_geqp3`, `mxlo_qrp_mul`, `mxlo_qrp_mul_block`).
+through a column-pivoted, rank-revealing one (`mxlo_geqp3`, `mxlo_qrp_mul`, `mxlo_qrp_mul_block`). `opPinv` is the pseudo-inverse of a
+matrix of any rank: the pivoted QR completed to an orthogonal decomposition (`mxlo_cod_factor`, `mxlo_pinv_mul`, `mxlo_pinv_mul_block`).
 """
 from __future__ import annotations
 
@@ -591,7 +592,7 @@ def opQR(A: torch.Tensor, pivot: bool = False, rtol=None):
     nf − r entries exactly zero before the α, β epilogue; the transposed mode gives y = Q[:, 0:r] R11⁻ᵀ u[perm[0:r]]. For r = nf
     these are the unique least-squares / minimum-norm solutions, as without pivoting. For r < nf they are A least-squares
     solution and, when the system is consistent, A solution — NOT the minimum-norm ones that Julia's complete orthogonal
-    decomposition returns (the further `tzrzf` step is not provided). An apply runs the unpivoted apply's kernels on the
+    decomposition returns (the further `tzrzf` step is not provided). `opPinv(A)` returns the minimum-norm ones. An apply runs the unpivoted apply's kernels on the
     leading r columns, `qrp_launches(r)` = `qr_launches(r)` launches (`qrp_block_launches(r, k)` for a matrix operand), with
     every promise of the paragraph above.
 
@@ -647,3 +648,95 @@ def opQR(A: torch.Tensor, pivot: bool = False, rtol=None):
     op._tall = tall
     op._factor = (W, tfac, dinv, work)                  # owned storage (kept alive with the operator)
     return op
+
+
+def pinv_launches(rank: int, nf: int) -> int:
+    """Launches of ONE opPinv apply, in either mode, for a factor with nf columns of numerical rank `rank`. Full rank: the
+    pivoted apply's. rank < nf: two reflector chains of ⌈rank/64⌉ + 1 launches joined by the ⌈rank/64⌉ of the sweep with R₂.
+    It does not depend on the number of rows."""
+    if int(rank) == int(nf):
+        return qrp_launches(rank)
+    return 3 * ((int(rank) + BLOCK - 1) // BLOCK) + 2
+
+
+def pinv_block_launches(rank: int, nf: int, k: int) -> int:
+    """Launches of an opPinv apply to a matrix with k columns: the chain of one vector apply per group of GROUP columns."""
+    return ((int(k) + GROUP - 1) // GROUP) * pinv_launches(rank, nf)
+
+
+def opPinv(A: torch.Tensor, rtol=None):
+    """opPinv(A): the Moore-Penrose pseudo-inverse A⁺ of a dense m x k matrix of ANY rank, a k x m operator — what Julia's
+    `A \\ v` returns for a rectangular A: the MINIMUM-NORM least-squares solution, through a complete orthogonal
+    decomposition computed on the device. prod!: res = α (A⁺ v) + β res; tprod! = ctprod!: res = α ((A⁺)ᵀ u) + β res, the same
+    for Aᵀ, whether or not u is consistent. With β == 0 res is not read.
+
+    Construction: opQR(A, pivot=True, rtol=rtol)'s factorisation F P = Q₁ R of the tall orientation F (mf x nf) with its rank
+    decision r (rtol: None for max(mf, nf)·eps(T), else a real with 0 <= rtol < 1; checked before A is looked at, then
+    opQR's refusals in their order). r == nf: the operator IS the pivoted one — the same kernels, launches and bits, and
+    `op._factor` = (W, T, dinv, work, perm). r < nf: S = [R₁₁ R₁₂]ᵀ (nf x r, full column rank) is taken out of the leading r
+    rows of W and factored S = Q₂ R₂ by the unpivoted block-Householder chain (`mxlo_cod_factor`), so that
+    F⁺ = P Q₂ R₂⁻ᵀ [I_r 0] Q₁ᵀ; `op._factor` = (W, T, dinv, work, perm, W2, T2, dinv2), W2 nf x r column-major: one more nf x r
+    factor and two ⌈r/64⌉·64² Float64 tables. `op._tall`, `op._rank`, `op._perm`, `op._rtol` as opQR(pivot=True)'s, and its
+    exceptions: `SingularException` for A == 0 or a column norm that is not finite; a rank-deficient A raises nothing.
+
+    An apply with r < nf is two reflector chains joined by one sweep with R₂ — Q₁ᵀ, R₂⁻ᵀ, Q₂ with the permutation scattered
+    by the last launch's epilogue; transposed: Q₂ᵀ with the permutation gathered by the first launch, R₂⁻¹, Q₁ —
+    `pinv_launches(r, nf)` = 3⌈r/64⌉ + 2 launches whatever mf is (`pinv_block_launches(r, nf, k)` for a matrix operand, GROUP
+    = 8 columns per chain, each column bit-identical to its vector apply), and nothing else: no allocation, no
+    synchronisation, capturable, bit-reproducible (every sum in a fixed order in Float64). res may be v when m == k. The work
+    space is opQR's. It streams (mf + nf)·r elements twice where the basic solution streams mf·r twice.
+
+    NOT provided: the structured `tzrzf` form of the second stage (reflectors of length 1 + nf − r), `refine`,
+    complex element types, Julia glue, sharding."""
+    rtol = _check_pivot(True, rtol, "opPinv")
+    m, k = _check_rect(A, "opPinv")
+    op = _qr_pivoted(A, m, k, rtol)
+    T = A.dtype
+    tall, r = op._tall, op._rank
+    mf, nf = (m, k) if tall else (k, m)
+    if r == nf:
+        return op
+    W, tfac, dinv, work, perm = op._factor
+    ldw = mf
+    ctx = get_ctx(A.device)
+    nblk = (r + BLOCK - 1) // BLOCK
+    W2 = torch.empty((r, nf), dtype=T, device=A.device).t()            # column-major nf x r, ld = nf
+    tfac2 = torch.zeros(nblk * BLOCK * BLOCK, dtype=torch.float64, device=A.device)
+    dinv2 = torch.empty(nblk * BLOCK * BLOCK, dtype=torch.float64, device=A.device)
+    nscratch = 2 * (QR_SLOTS * BLOCK + BLOCK) + (512 + 2 * nblk) * BLOCK * BLOCK
+    scratch = torch.empty(nscratch, dtype=torch.float64, device=A.device)                   # needed by the factorisation only
+    info_dev = torch.zeros(1, dtype=torch.int32, device=A.device)
+    info = C.c_int32(0)
+    code = dtype_code(T)
+    _lib.call("mxlo_cod_factor", ctx.handle, code, W.data_ptr(), ldw, nf, r, W2.data_ptr(), tfac2.data_ptr(), dinv2.data_ptr(),
+              scratch.data_ptr(), nscratch, info_dev.data_ptr(), C.byref(info))
+    del scratch
+    if info.value != 0:
+        raise SingularException(info.value)
+    pW, pT, pP, pZ = W.data_ptr(), tfac.data_ptr(), perm.data_ptr(), work.data_ptr()
+    pW2, pT2, pD2 = W2.data_ptr(), tfac2.data_ptr(), dinv2.data_ptr()
+
+    def solve(res, v, a, b, mode):
+        _check_operands(res, v, T)
+        _lib.call("mxlo_pinv_mul", ctx_of(res).handle, code, res.data_ptr(), pW, ldw, mf, nf, pT, pP, r, pW2, pT2, pD2, pZ,
+                  v.data_ptr(), mode, float(a), float(b))
+
+    def block(res, V, a, b, mode):
+        nv, nres = (mf, nf) if mode == _lib.OP_N else (nf, mf)
+        ldr, ldv, cols = _check_block_operands(res, V, T, nv, nres)
+        _lib.call("mxlo_pinv_mul_block", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, mf, nf, pT, pP, r, pW2, pT2, pD2, pZ,
+                  V.data_ptr(), ldv, cols, mode, float(a), float(b))
+
+    fwd, bwd = (_lib.OP_N, _lib.OP_T) if tall else (_lib.OP_T, _lib.OP_N)
+    prod = columnwise(lambda res, v, a, b: solve(res, v, a, b, fwd))
+    tprod = columnwise(lambda res, u, a, b: solve(res, u, a, b, bwd))
+    prod._matrix = lambda res, V, a, b: block(res, V, a, b, fwd)
+    tprod._matrix = lambda res, V, a, b: block(res, V, a, b, bwd)
+    pinv = LinearOperator(T, k, m, False, False, prod, tprod, tprod, S=Storage(T, A.device))
+    pinv._deps = (W,)
+    pinv._tall = tall
+    pinv._rank = r
+    pinv._perm = perm
+    pinv._rtol = op._rtol
+    pinv._factor = (W, tfac, dinv, work, perm, W2, tfac2, dinv2)        # owned storage (kept alive with the operator)
+    return pinv

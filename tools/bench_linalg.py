@@ -45,6 +45,13 @@ by its byte model, 2·sizeof(T)·Σ_c (mf − c)(nf − c)) and the vector apply
 kernels; the last column is the time over the unpivoted row's.
 
     python tools/bench_linalg.py --qrp [MFxNF ...] > profiles/linalg_qrp.txt
+
+--pinv: opPinv(A) beside opQR(A, pivot=True) of the same matrix in the same run, on the matrices of --qr made rank-deficient: the
+last quarter of the columns is replaced by Gaussian combinations of the others (rank 3 nf / 4). The construction of both, and
+the apply in both modes on a vector and on k = 8 columns; GB/s by the two-read models — 2·mf·r·sizeof(T) for the basic apply,
+2·(mf + nf)·r·sizeof(T) for opPinv's —, the last column the time over the pivoted row's, to be held against 1 + nf/mf.
+
+    python tools/bench_linalg.py --pinv [MFxNF ...] > profiles/linalg_pinv.txt
 """
 import ctypes as C
 import os
@@ -314,6 +321,58 @@ def qrp_legs():
             torch.cuda.empty_cache()
 
 
+def pinv_legs():
+    """opPinv(A) beside opQR(A, pivot=True) on rank-deficient matrices: see the module docstring"""
+    print(f"# {torch.cuda.get_device_name(0)}; opPinv(A) beside opQR(A, pivot=True), rank 3 nf / 4; ms per call, median of 3 event-timed "
+          f"windows, spread = (max - min) / median")
+    print(f"# construction: allocations and the synchronisations included. apply: two reads of the panels, 2 mf r sizeof(T) (basic) and "
+          f"2 (mf + nf) r sizeof(T) (opPinv), per group of 8 columns; peak {PEAK:.0f} GB/s; x pivoted: to be held against 1 + nf/mf")
+    print(f"{'case':44s} {'mf':>8s} {'nf':>5s} {'rank':>5s} {'k':>2s} {'ms':>10s} {'spread':>6s} {'launch':>6s} {'GB/s':>8s} {'%peak':>6s} "
+          f"{'x pivoted':>9s} {'1+nf/mf':>8s}", flush=True)
+    shapes = [tuple(int(x) for x in a.split("x")) for a in sys.argv[1:] if "x" in a] or [(1000000, 128), (8192, 8192)]
+    for dtype, tag in ((torch.float64, "f64"), (torch.float32, "f32")):
+        es = 8 if dtype is torch.float64 else 4
+        for mf, nf in shapes:
+            gen = torch.Generator(device=dev).manual_seed(mf + nf)
+            A = torch.randn(nf, mf, dtype=dtype, device=dev, generator=gen).t()           # the matrices of --qr
+            if mf == nf:
+                A = A + (nf ** 0.5) * torch.eye(nf, dtype=dtype, device=dev)
+            keep = nf - nf // 4
+            comb = torch.randn(keep, nf - keep, dtype=dtype, device=dev, generator=gen) / keep ** 0.5
+            A[:, keep:] = A[:, :keep] @ comb
+            reps = 10 if mf * nf <= 2 ** 27 else 5
+            base = {}
+
+            def row(name, fn, reps, nbytes, nl, key, r, k):
+                ms = timeit(fn, reps)
+                gbs = nbytes / ms / 1e6 if nbytes else 0.0
+                ratio = f"{ms / base[key]:9.3f} {1 + nf / mf:8.4f}" if key in base else f"{'':9s} {'':8s}"
+                base.setdefault(key, ms)
+                print(f"{name + ' ' + tag:44s} {mf:8d} {nf:5d} {r:5d} {k:2d} {ms:10.4f} {100 * timeit.spread:5.1f}% {nl:6d} {gbs:8.1f} "
+                      f"{100 * gbs / PEAK:6.2f} {ratio}", flush=True)
+
+            piv, pin = lo.opQR(A, pivot=True), lo.opPinv(A)
+            r = pin._rank
+            assert piv._rank == r and r < nf and len(pin._factor) == 8, (piv._rank, r)
+            row("opQR(A, pivot=True) construction", lambda: lo.opQR(A, pivot=True), 1, 0, 0, "f", r, 0)
+            row("opPinv(A) construction", lambda: lo.opPinv(A), 1, 0, 0, "f", r, 0)
+            for k in (1, 8):
+                v = colmajor(mf, k, dtype, 1)[:, 0] if k == 1 else colmajor(mf, k, dtype, 1)
+                u = colmajor(nf, k, dtype, 2)[:, 0] if k == 1 else colmajor(nf, k, dtype, 2)
+                x, y = torch.empty_like(u), torch.empty_like(v)
+                for name, res, wp, wq, rhs in (("apply", x, piv, pin, v), ("transposed apply", y, piv.T, pin.T, u)):
+                    key = (name, k)
+                    row("pivoted " + name, lambda: lo.mul(res, wp, rhs, 1.0, 0.0), reps, 2 * mf * r * es,
+                        launches(lambda: lo.mul(res, wp, rhs, 1.0, 0.0)), key, r, k)
+                    row("opPinv " + name, lambda: lo.mul(res, wq, rhs, 1.0, 0.0), reps, 2 * (mf + nf) * r * es,
+                        launches(lambda: lo.mul(res, wq, rhs, 1.0, 0.0)), key, r, k)
+            del piv, pin, A
+            torch.cuda.empty_cache()
+
+
+if "--pinv" in sys.argv:
+    pinv_legs()
+    sys.exit(0)
 if "--qrp" in sys.argv:
     qrp_legs()
     sys.exit(0)
