@@ -979,59 +979,127 @@ int32_t sweep(mxlo_ctx *ctx, const T *Tm, int64_t ld, int64_t n, bool upper, boo
   return MXLO_OK;
 }
 
-int32_t check_common(mxlo_ctx *ctx, int32_t dtype, const void *A, int64_t ld, int64_t n, const char *what) {
+// ---------------------------------------------------------------------------------------------- the host checks
+// Every entry point below refuses a bad call before anything is launched, through the functions of this section. What an
+// operator adds is a LIST of the buffers it owns ({pointer, bytes, name}), never a check of its own: disjoint() holds a
+// factorisation's buffers against each other, check_operands() res and V of an apply against the operator's.
+struct Buf {
+  const void *p;
+  int64_t bytes;
+  const char *name;
+};
+
+inline int64_t esize(int32_t dtype) { return dtype == MXLO_F64 ? 8 : 4; }
+inline int64_t mat_bytes(int64_t rows, int64_t cols, int64_t ld, int64_t es) { return ((cols - 1) * ld + rows) * es; }
+inline int64_t blocks_bytes(int64_t n) { return (n + NB - 1) / NB * NB2 * 8; }   // one NB x NB block of doubles per block column
+
+// calls f.template operator()<T>() for the element type of dtype, which the entry point has checked
+template <typename F>
+int32_t with_real(int32_t dtype, F &&f) {
+  return dtype == MXLO_F64 ? f.template operator()<double>() : f.template operator()<float>();
+}
+
+int32_t check_real(mxlo_ctx *ctx, int32_t dtype, const char *what) {
   MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
   MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
+  return MXLO_OK;
+}
+
+int32_t check_mode(int32_t op_mode, const char *what) {
+  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "%s: op_mode %d", what, op_mode);
+  return MXLO_OK;
+}
+
+int32_t check_common(mxlo_ctx *ctx, int32_t dtype, const void *A, int64_t ld, int64_t n, const char *what) {
+  MXLO_TRY(check_real(ctx, dtype, what));
   MXLO_REQUIRE(n >= 0 && ld >= (n > 1 ? n : 1), MXLO_ESHAPE, "%s: n = %lld, ld = %lld", what, (long long)n, (long long)ld);
   MXLO_REQUIRE(A || n == 0, MXLO_EINVAL, "%s: null matrix", what);
   return MXLO_OK;
 }
 
-// res and v of an apply: n x k, columns of unit stride, with leading dimensions ldr, ldv. A vector entry point passes
-// vectors(res, v, n): one column in a leading dimension of max(1, n).
+// the buffers of a factorisation may not overlap each other; an operand that may be NULL (M) is skipped when it is
+int32_t disjoint(std::initializer_list<Buf> bufs, const char *what) {
+  for (const Buf *x = bufs.begin(); x != bufs.end(); ++x)
+    for (const Buf *y = x + 1; y != bufs.end(); ++y)
+      MXLO_REQUIRE(!x->p || !y->p || !bytes_overlap(x->p, x->bytes, y->p, y->bytes), MXLO_EINVAL, "%s: %s overlaps %s", what, x->name,
+                   y->name);
+  return MXLO_OK;
+}
+
+// the tail of a factorisation: it reads `count` info words back, the only synchronisation, which a graph capture cannot hold.
+// refuse_capture() is the last check before the device is touched, read_back() the last call of the chain.
+int32_t refuse_capture(const mxlo_ctx *ctx, const char *what) {
+  MXLO_REQUIRE(!ctx->capturing, MXLO_ESTATE, "%s: reads its info words back, which a graph capture cannot hold", what);
+  return MXLO_OK;
+}
+
+int32_t read_back(mxlo_ctx *ctx, const int32_t *info_dev, int32_t *words, int count) {
+  MXLO_HIP(hipMemcpyAsync(words, info_dev, count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MXLO_HIP(hipStreamSynchronize(ctx->stream));
+  return MXLO_OK;
+}
+
+// res (rrows x k, ldr) and V (vrows x k, ldv) of an apply, columns of unit stride. A vector entry point passes vectors():
+// one column in a leading dimension of max(1, rows).
 struct Operands {
   const void *res, *v;
-  int64_t k, ldr, ldv;
-  int64_t res_bytes(int64_t n, int64_t es) const { return ((k - 1) * ldr + n) * es; }
-  int64_t v_bytes(int64_t n, int64_t es) const { return ((k - 1) * ldv + n) * es; }
+  int64_t k, ldr, ldv, rrows, vrows;
 };
-inline Operands vectors(const void *res, const void *v, int64_t n) { return {res, v, 1, n > 1 ? n : 1, n > 1 ? n : 1}; }
+inline Operands vectors(const void *res, const void *v, int64_t rrows, int64_t vrows) {
+  return {res, v, 1, rrows > 1 ? rrows : 1, vrows > 1 ? vrows : 1, rrows, vrows};
+}
 
-// work is n * min(k, KB) doubles. res may be v, as the same matrix: the same pointer and the same leading dimension.
+// res and V against the buffers an operator owns, none of which may be NULL
+int32_t check_owned(int32_t dtype, const Operands &o, std::initializer_list<Buf> own, const char *what) {
+  const int64_t es = esize(dtype), rb = mat_bytes(o.rrows, o.k, o.ldr, es), vb = mat_bytes(o.vrows, o.k, o.ldv, es);
+  for (const Buf &b : own) {
+    MXLO_REQUIRE(b.p, MXLO_EINVAL, "%s: null operand (%s)", what, b.name);
+    MXLO_REQUIRE(!bytes_overlap(o.res, rb, b.p, b.bytes) && !bytes_overlap(o.v, vb, b.p, b.bytes), MXLO_EINVAL,
+                 "%s: res or V overlaps %s", what, b.name);
+  }
+  return MXLO_OK;
+}
+
+// The checks every apply shares once its operator's shape is known to be valid: k and the leading dimensions, the null
+// operands, the rule for res and V, and both against `own`. go: whether there is anything to do — with k == 0, or `empty`
+// (n == 0), the call is MXLO_OK and launches nothing, and what comes after the leading dimensions is not looked at. Every
+// entry point runs the checks it has of its own and then returns on !go. res may be V only as the same matrix: the same
+// pointer, the same leading dimension and the same number of rows, which for a rectangular operator means mf == nf.
+int32_t check_operands(int32_t dtype, const Operands &o, bool empty, std::initializer_list<Buf> own, const char *what, bool &go) {
+  go = false;
+  MXLO_REQUIRE(o.k >= 0 && o.ldr >= (o.rrows > 1 ? o.rrows : 1) && o.ldv >= (o.vrows > 1 ? o.vrows : 1), MXLO_ESHAPE,
+               "%s: k = %lld, ldr = %lld for %lld rows, ldv = %lld for %lld rows", what, (long long)o.k, (long long)o.ldr,
+               (long long)o.rrows, (long long)o.ldv, (long long)o.vrows);
+  if (empty || o.k == 0) return MXLO_OK;
+  MXLO_REQUIRE(o.res && o.v, MXLO_EINVAL, "%s: null operand (res / V)", what);
+  const int64_t es = esize(dtype);
+  MXLO_REQUIRE((o.res == o.v && o.ldr == o.ldv && o.rrows == o.vrows) ||
+                   !bytes_overlap(o.res, mat_bytes(o.rrows, o.k, o.ldr, es), o.v, mat_bytes(o.vrows, o.k, o.ldv, es)),
+               MXLO_EINVAL, "%s: res overlaps V without being V (only mul!(X, op, X) of a square operator, as the same matrix, is defined)",
+               what);
+  MXLO_TRY(check_owned(dtype, o, own, what));
+  go = true;
+  return MXLO_OK;
+}
+
+// a square apply: A (n x n, ld), its block inverses, work of n * min(k, KB) doubles, and what the operator owns besides
 int32_t check_apply(mxlo_ctx *ctx, int32_t dtype, const Operands &o, const void *A, int64_t ld, int64_t n, const double *dinv,
-                    const double *work, const char *what) {
+                    const double *work, const char *what, bool &go, std::initializer_list<Buf> more = {}) {
+  go = false;
   MXLO_TRY(check_common(ctx, dtype, A, ld, n, what));
-  const int64_t ldmin = n > 1 ? n : 1;
-  MXLO_REQUIRE(o.k >= 0 && o.ldr >= ldmin && o.ldv >= ldmin, MXLO_ESHAPE, "%s: k = %lld, ldr = %lld, ldv = %lld for n = %lld", what,
-               (long long)o.k, (long long)o.ldr, (long long)o.ldv, (long long)n);
-  if (n == 0 || o.k == 0) return MXLO_OK;
-  MXLO_REQUIRE(o.res && o.v && dinv && work, MXLO_EINVAL, "%s: null operand", what);
-  const int64_t es = dtype == MXLO_F64 ? 8 : 4, rb = o.res_bytes(n, es), vb = o.v_bytes(n, es);
-  const int64_t ab = ((n - 1) * ld + n) * es, db = (n + NB - 1) / NB * NB2 * 8, wb = n * (o.k < KB ? o.k : KB) * 8;
-  MXLO_REQUIRE((o.res == o.v && o.ldr == o.ldv) || !bytes_overlap(o.res, rb, o.v, vb), MXLO_EINVAL,
-               "%s: res overlaps v without being v (only mul!(x, op, x) is defined)", what);
-  for (const auto &[p, pb] : {std::pair<const void *, int64_t>{o.res, rb}, {o.v, vb}})
-    MXLO_REQUIRE(!bytes_overlap(p, pb, A, ab) && !bytes_overlap(p, pb, dinv, db) && !bytes_overlap(p, pb, work, wb), MXLO_EINVAL,
-                 "%s: res / v overlap the matrix, the block inverses or the work vector", what);
-  return MXLO_OK;
+  MXLO_TRY(check_operands(dtype, o, n == 0,
+                          {{A, mat_bytes(n, n, ld, esize(dtype)), "the matrix"},
+                           {dinv, blocks_bytes(n), "the block inverses"},
+                           {work, n * (o.k < KB ? o.k : KB) * 8, "the work vector"}},
+                          what, go));
+  return go ? check_owned(dtype, o, more, what) : MXLO_OK;
 }
 
-// the further operand `x` of an apply (xb bytes: the pivots, the second block inverses, the permutation) against res and v
-int32_t check_extra(int32_t dtype, const Operands &o, int64_t n, const void *x, int64_t xb, const char *what, const char *name) {
-  const int64_t es = dtype == MXLO_F64 ? 8 : 4;
-  MXLO_REQUIRE(!bytes_overlap(o.res, o.res_bytes(n, es), x, xb) && !bytes_overlap(o.v, o.v_bytes(n, es), x, xb), MXLO_EINVAL,
-               "%s: res / v overlap %s", what, name);
-  return MXLO_OK;
-}
-
-// mxlo_lu_mul: check_apply's rules, extended to the second set of block inverses and to the permutation
+// opLU's applies: the second set of block inverses and the permutation besides
 int32_t check_lu_apply(mxlo_ctx *ctx, int32_t dtype, const Operands &o, const void *W, int64_t ld, int64_t n, const double *dinv_l,
-                       const double *dinv_u, const int32_t *perm, const double *work, const char *what) {
-  MXLO_TRY(check_apply(ctx, dtype, o, W, ld, n, dinv_l, work, what));
-  if (n == 0 || o.k == 0) return MXLO_OK;
-  MXLO_REQUIRE(dinv_u && perm, MXLO_EINVAL, "%s: null operand", what);
-  MXLO_TRY(check_extra(dtype, o, n, dinv_u, (n + NB - 1) / NB * NB2 * 8, what, "the block inverses"));
-  return check_extra(dtype, o, n, perm, n * 4, what, "the permutation");
+                       const double *dinv_u, const int32_t *perm, const double *work, const char *what, bool &go) {
+  return check_apply(ctx, dtype, o, W, ld, n, dinv_l, work, what, go,
+                     {{dinv_u, blocks_bytes(n), "the block inverses of U"}, {perm, n * 4, "the permutation"}});
 }
 
 template <typename T>
@@ -1154,18 +1222,13 @@ int32_t factor(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t
   }
   if (d) MXLO_REQUIRE(!bytes_overlap(d, n * 8, W, wb) && !bytes_overlap(d, n * 8, dinv, (n + NB - 1) / NB * NB2 * 8), MXLO_EINVAL,
                       "%s: the pivots' storage overlaps the factor or the block inverses", what);
-  MXLO_REQUIRE(!ctx->capturing, MXLO_ESTATE, "%s: reads its info word back, which a graph capture cannot hold", what);
+  MXLO_TRY(refuse_capture(ctx, what));
   MXLO_DEVICE_GUARD(ctx);
-  if (d) {
-    if (dtype == MXLO_F64) MXLO_TRY((potrf_t<double, true>(ctx, (const double *)M, ldm, m_rowmajor, (double *)W, ldw, n, dinv, d, info_dev)));
-    else MXLO_TRY((potrf_t<float, true>(ctx, (const float *)M, ldm, m_rowmajor, (float *)W, ldw, n, dinv, d, info_dev)));
-  } else {
-    if (dtype == MXLO_F64) MXLO_TRY((potrf_t<double, false>(ctx, (const double *)M, ldm, m_rowmajor, (double *)W, ldw, n, dinv, d, info_dev)));
-    else MXLO_TRY((potrf_t<float, false>(ctx, (const float *)M, ldm, m_rowmajor, (float *)W, ldw, n, dinv, d, info_dev)));
-  }
-  MXLO_HIP(hipMemcpyAsync(info, info_dev, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  MXLO_HIP(hipStreamSynchronize(ctx->stream));
-  return MXLO_OK;
+  MXLO_TRY(with_real(dtype, [&]<typename T>() {
+    if (d) return potrf_t<T, true>(ctx, (const T *)M, ldm, m_rowmajor, (T *)W, ldw, n, dinv, d, info_dev);
+    return potrf_t<T, false>(ctx, (const T *)M, ldm, m_rowmajor, (T *)W, ldw, n, dinv, d, info_dev);
+  }));
+  return read_back(ctx, info_dev, info, 1);
 }
 }  // namespace
 
@@ -1182,14 +1245,15 @@ MXLO_API int32_t mxlo_ldlt(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t 
 
 MXLO_API int32_t mxlo_trisolve_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *Tm, int64_t ld, int64_t n, int32_t upper,
                                    int32_t op_mode, const double *dinv, double *work, const void *v, double alpha, double beta) {
-  MXLO_TRY(check_apply(ctx, dtype, vectors(res, v, n), Tm, ld, n, dinv, work, "mxlo_trisolve_mul"));
-  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "mxlo_trisolve_mul: op_mode %d", op_mode);
-  if (n == 0) return MXLO_OK;
+  bool go;
+  MXLO_TRY(check_apply(ctx, dtype, vectors(res, v, n, n), Tm, ld, n, dinv, work, "mxlo_trisolve_mul", go));
+  MXLO_TRY(check_mode(op_mode, "mxlo_trisolve_mul"));
+  if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
   const bool tr = op_mode != MXLO_OP_N;
-  if (dtype == MXLO_F64)
-    return sweep<double>(ctx, (const double *)Tm, ld, n, upper != 0, tr, dinv, work, (const double *)v, true, false, true, (double *)res, alpha, beta);
-  return sweep<float>(ctx, (const float *)Tm, ld, n, upper != 0, tr, dinv, work, (const float *)v, true, false, true, (float *)res, alpha, beta);
+  return with_real(dtype, [&]<typename T>() {
+    return sweep<T>(ctx, (const T *)Tm, ld, n, upper != 0, tr, dinv, work, (const T *)v, true, false, true, (T *)res, alpha, beta);
+  });
 }
 
 namespace {
@@ -1207,11 +1271,13 @@ int32_t chol_mul_t(mxlo_ctx *ctx, T *res, const T *L, int64_t ld, int64_t n, con
 
 MXLO_API int32_t mxlo_chol_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *L, int64_t ld, int64_t n, const double *dinv,
                                double *work, const void *v, double alpha, double beta) {
-  MXLO_TRY(check_apply(ctx, dtype, vectors(res, v, n), L, ld, n, dinv, work, "mxlo_chol_mul"));
-  if (n == 0) return MXLO_OK;
+  bool go;
+  MXLO_TRY(check_apply(ctx, dtype, vectors(res, v, n, n), L, ld, n, dinv, work, "mxlo_chol_mul", go));
+  if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
-  if (dtype == MXLO_F64) return chol_mul_t<double>(ctx, (double *)res, (const double *)L, ld, n, dinv, work, (const double *)v, alpha, beta);
-  return chol_mul_t<float>(ctx, (float *)res, (const float *)L, ld, n, dinv, work, (const float *)v, alpha, beta);
+  return with_real(dtype, [&]<typename T>() {
+    return chol_mul_t<T>(ctx, (T *)res, (const T *)L, ld, n, dinv, work, (const T *)v, alpha, beta);
+  });
 }
 
 namespace {
@@ -1230,15 +1296,13 @@ int32_t ldl_mul_t(mxlo_ctx *ctx, T *res, const T *L, int64_t ld, int64_t n, cons
 
 MXLO_API int32_t mxlo_ldl_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *L, int64_t ld, int64_t n, const double *dinv,
                               const double *d, double *work, const void *v, double alpha, double beta) {
-  MXLO_TRY(check_apply(ctx, dtype, vectors(res, v, n), L, ld, n, dinv, work, "mxlo_ldl_mul"));
-  if (n == 0) return MXLO_OK;
-  MXLO_REQUIRE(d, MXLO_EINVAL, "mxlo_ldl_mul: null pivots");
-  const int64_t vb = n * (dtype == MXLO_F64 ? 8 : 4);
-  MXLO_REQUIRE(!bytes_overlap(res, vb, d, n * 8) && !bytes_overlap(v, vb, d, n * 8), MXLO_EINVAL,
-               "mxlo_ldl_mul: res / v overlap the pivots");
+  bool go;
+  MXLO_TRY(check_apply(ctx, dtype, vectors(res, v, n, n), L, ld, n, dinv, work, "mxlo_ldl_mul", go, {{d, n * 8, "the pivots"}}));
+  if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
-  if (dtype == MXLO_F64) return ldl_mul_t<double>(ctx, (double *)res, (const double *)L, ld, n, dinv, d, work, (const double *)v, alpha, beta);
-  return ldl_mul_t<float>(ctx, (float *)res, (const float *)L, ld, n, dinv, d, work, (const float *)v, alpha, beta);
+  return with_real(dtype, [&]<typename T>() {
+    return ldl_mul_t<T>(ctx, (T *)res, (const T *)L, ld, n, dinv, d, work, (const T *)v, alpha, beta);
+  });
 }
 
 MXLO_API int32_t mxlo_getrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, void *W, int64_t ldw, int64_t n, double *dinv_l,
@@ -1250,38 +1314,30 @@ MXLO_API int32_t mxlo_getrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t
   if (n == 0) return MXLO_OK;
   MXLO_REQUIRE(dinv_l && dinv_u && perm && info_dev, MXLO_EINVAL, "%s: null storage for the block inverses / the permutation / the info word", what);
   MXLO_REQUIRE(n < (1LL << 31) - NB, MXLO_ESHAPE, "%s: n = %lld is too large", what, (long long)n);
-  const int64_t es = dtype == MXLO_F64 ? 8 : 4, wb = ((n - 1) * ldw + n) * es, db = (n + NB - 1) / NB * NB2 * 8;
-  if (M) {
-    MXLO_REQUIRE(ldm >= (n > 1 ? n : 1), MXLO_ESHAPE, "%s: ldm = %lld < n", what, (long long)ldm);
-    const int64_t mb = ((n - 1) * ldm + n) * es;
-    MXLO_REQUIRE(!bytes_overlap(M, mb, W, wb), MXLO_EINVAL, "%s: the factor's storage overlaps M", what);
-    MXLO_REQUIRE(!bytes_overlap(M, mb, dinv_l, db) && !bytes_overlap(M, mb, dinv_u, db) && !bytes_overlap(M, mb, perm, 8 * n) &&
-                     !bytes_overlap(M, mb, info_dev, 4),
-                 MXLO_EINVAL, "%s: the block inverses, the permutation or the info word overlap M", what);
-  }
-  MXLO_REQUIRE(!bytes_overlap(perm, 8 * n, W, wb) && !bytes_overlap(perm, 8 * n, dinv_l, db) && !bytes_overlap(perm, 8 * n, dinv_u, db) &&
-                   !bytes_overlap(dinv_l, db, dinv_u, db) && !bytes_overlap(dinv_l, db, W, wb) && !bytes_overlap(dinv_u, db, W, wb),
-               MXLO_EINVAL, "%s: the factor, the block inverses and the permutation overlap", what);
-  MXLO_REQUIRE(!ctx->capturing, MXLO_ESTATE, "%s: reads its info word back, which a graph capture cannot hold", what);
+  if (M) MXLO_REQUIRE(ldm >= (n > 1 ? n : 1), MXLO_ESHAPE, "%s: ldm = %lld < n", what, (long long)ldm);
+  const int64_t es = esize(dtype);
+  const Buf m{M, M ? mat_bytes(n, n, ldm, es) : 0, "M"};   // the permutation counts as 8 n bytes; the info word is held against M only
+  MXLO_TRY(disjoint({m, {W, mat_bytes(n, n, ldw, es), "the factor"}, {dinv_l, blocks_bytes(n), "the block inverses of L"},
+                     {dinv_u, blocks_bytes(n), "the block inverses of U"}, {perm, 8 * n, "the permutation"}}, what));
+  MXLO_TRY(disjoint({m, {info_dev, 4, "the info word"}}, what));
+  MXLO_TRY(refuse_capture(ctx, what));
   MXLO_DEVICE_GUARD(ctx);
-  if (dtype == MXLO_F64) MXLO_TRY(getrf_t<double>(ctx, (const double *)M, ldm, (double *)W, ldw, n, dinv_l, dinv_u, perm, info_dev));
-  else MXLO_TRY(getrf_t<float>(ctx, (const float *)M, ldm, (float *)W, ldw, n, dinv_l, dinv_u, perm, info_dev));
-  MXLO_HIP(hipMemcpyAsync(info, info_dev, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  MXLO_HIP(hipStreamSynchronize(ctx->stream));
-  return MXLO_OK;
+  MXLO_TRY(with_real(dtype, [&]<typename T>() { return getrf_t<T>(ctx, (const T *)M, ldm, (T *)W, ldw, n, dinv_l, dinv_u, perm, info_dev); }));
+  return read_back(ctx, info_dev, info, 1);
 }
 
 MXLO_API int32_t mxlo_lu_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t n, const double *dinv_l,
                              const double *dinv_u, const int32_t *perm, double *work, const void *v, int32_t op_mode, double alpha,
                              double beta) {
-  MXLO_TRY(check_lu_apply(ctx, dtype, vectors(res, v, n), W, ldw, n, dinv_l, dinv_u, perm, work, "mxlo_lu_mul"));
-  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "mxlo_lu_mul: op_mode %d", op_mode);
-  if (n == 0) return MXLO_OK;
+  bool go;
+  MXLO_TRY(check_lu_apply(ctx, dtype, vectors(res, v, n, n), W, ldw, n, dinv_l, dinv_u, perm, work, "mxlo_lu_mul", go));
+  MXLO_TRY(check_mode(op_mode, "mxlo_lu_mul"));
+  if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
   const bool tr = op_mode != MXLO_OP_N;
-  if (dtype == MXLO_F64)
-    return lu_mul_t<double>(ctx, (double *)res, (const double *)W, ldw, n, dinv_l, dinv_u, perm, work, (const double *)v, tr, alpha, beta);
-  return lu_mul_t<float>(ctx, (float *)res, (const float *)W, ldw, n, dinv_l, dinv_u, perm, work, (const float *)v, tr, alpha, beta);
+  return with_real(dtype, [&]<typename T>() {
+    return lu_mul_t<T>(ctx, (T *)res, (const T *)W, ldw, n, dinv_l, dinv_u, perm, work, (const T *)v, tr, alpha, beta);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------- block entry points
@@ -1300,73 +1356,65 @@ int32_t for_groups(T *res, int64_t ldr, const T *V, int64_t ldv, int64_t k, F &&
   }
   return MXLO_OK;
 }
+
+// with_real and for_groups in one: f(res_j, V_j, grp), a generic lambda over the element type, per group of KB columns
+template <typename F>
+int32_t for_real_groups(int32_t dtype, void *res, int64_t ldr, const void *V, int64_t ldv, int64_t k, F &&f) {
+  return with_real(dtype, [&]<typename T>() { return for_groups((T *)res, ldr, (const T *)V, ldv, k, f); });
+}
 }  // namespace
 
 MXLO_API int32_t mxlo_trisolve_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *Tm, int64_t ld, int64_t n,
                                          int32_t upper, int32_t op_mode, const double *dinv, double *work, const void *V, int64_t ldv,
                                          int64_t k, double alpha, double beta) {
-  MXLO_TRY(check_apply(ctx, dtype, Operands{res, V, k, ldr, ldv}, Tm, ld, n, dinv, work, "mxlo_trisolve_mul_block"));
-  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "mxlo_trisolve_mul_block: op_mode %d", op_mode);
-  if (n == 0 || k == 0) return MXLO_OK;
+  bool go;
+  MXLO_TRY(check_apply(ctx, dtype, Operands{res, V, k, ldr, ldv, n, n}, Tm, ld, n, dinv, work, "mxlo_trisolve_mul_block", go));
+  MXLO_TRY(check_mode(op_mode, "mxlo_trisolve_mul_block"));
+  if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
   const bool tr = op_mode != MXLO_OP_N, up = upper != 0;
-  if (dtype == MXLO_F64)
-    return for_groups((double *)res, ldr, (const double *)V, ldv, k, [&](double *r, const double *v, Group grp) {
-      return sweep<double>(ctx, (const double *)Tm, ld, n, up, tr, dinv, work, v, true, false, true, r, alpha, beta, nullptr, nullptr,
-                           nullptr, nullptr, false, grp);
-    });
-  return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
-    return sweep<float>(ctx, (const float *)Tm, ld, n, up, tr, dinv, work, v, true, false, true, r, alpha, beta, nullptr, nullptr, nullptr,
-                        nullptr, false, grp);
+  return for_real_groups(dtype, res, ldr, V, ldv, k, [&]<typename T>(T *r, const T *v, Group grp) {
+    return sweep<T>(ctx, (const T *)Tm, ld, n, up, tr, dinv, work, v, true, false, true, r, alpha, beta, nullptr, nullptr, nullptr, nullptr,
+                    false, grp);
   });
 }
 
 MXLO_API int32_t mxlo_chol_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *L, int64_t ld, int64_t n,
                                      const double *dinv, double *work, const void *V, int64_t ldv, int64_t k, double alpha,
                                      double beta) {
-  MXLO_TRY(check_apply(ctx, dtype, Operands{res, V, k, ldr, ldv}, L, ld, n, dinv, work, "mxlo_chol_mul_block"));
-  if (n == 0 || k == 0) return MXLO_OK;
+  bool go;
+  MXLO_TRY(check_apply(ctx, dtype, Operands{res, V, k, ldr, ldv, n, n}, L, ld, n, dinv, work, "mxlo_chol_mul_block", go));
+  if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
-  if (dtype == MXLO_F64)
-    return for_groups((double *)res, ldr, (const double *)V, ldv, k, [&](double *r, const double *v, Group grp) {
-      return chol_mul_t<double>(ctx, r, (const double *)L, ld, n, dinv, work, v, alpha, beta, grp);
-    });
-  return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
-    return chol_mul_t<float>(ctx, r, (const float *)L, ld, n, dinv, work, v, alpha, beta, grp);
+  return for_real_groups(dtype, res, ldr, V, ldv, k, [&]<typename T>(T *r, const T *v, Group grp) {
+    return chol_mul_t<T>(ctx, r, (const T *)L, ld, n, dinv, work, v, alpha, beta, grp);
   });
 }
 
 MXLO_API int32_t mxlo_ldl_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *L, int64_t ld, int64_t n,
                                     const double *dinv, const double *d, double *work, const void *V, int64_t ldv, int64_t k,
                                     double alpha, double beta) {
-  MXLO_TRY(check_apply(ctx, dtype, Operands{res, V, k, ldr, ldv}, L, ld, n, dinv, work, "mxlo_ldl_mul_block"));
-  if (n == 0 || k == 0) return MXLO_OK;
-  MXLO_REQUIRE(d, MXLO_EINVAL, "mxlo_ldl_mul_block: null pivots");
-  MXLO_TRY(check_extra(dtype, Operands{res, V, k, ldr, ldv}, n, d, n * 8, "mxlo_ldl_mul_block", "the pivots"));
+  bool go;
+  MXLO_TRY(check_apply(ctx, dtype, Operands{res, V, k, ldr, ldv, n, n}, L, ld, n, dinv, work, "mxlo_ldl_mul_block", go,
+                       {{d, n * 8, "the pivots"}}));
+  if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
-  if (dtype == MXLO_F64)
-    return for_groups((double *)res, ldr, (const double *)V, ldv, k, [&](double *r, const double *v, Group grp) {
-      return ldl_mul_t<double>(ctx, r, (const double *)L, ld, n, dinv, d, work, v, alpha, beta, grp);
-    });
-  return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
-    return ldl_mul_t<float>(ctx, r, (const float *)L, ld, n, dinv, d, work, v, alpha, beta, grp);
+  return for_real_groups(dtype, res, ldr, V, ldv, k, [&]<typename T>(T *r, const T *v, Group grp) {
+    return ldl_mul_t<T>(ctx, r, (const T *)L, ld, n, dinv, d, work, v, alpha, beta, grp);
   });
 }
 
 MXLO_API int32_t mxlo_lu_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t n,
                                    const double *dinv_l, const double *dinv_u, const int32_t *perm, double *work, const void *V,
                                    int64_t ldv, int64_t k, int32_t op_mode, double alpha, double beta) {
-  MXLO_TRY(check_lu_apply(ctx, dtype, Operands{res, V, k, ldr, ldv}, W, ldw, n, dinv_l, dinv_u, perm, work, "mxlo_lu_mul_block"));
-  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "mxlo_lu_mul_block: op_mode %d", op_mode);
-  if (n == 0 || k == 0) return MXLO_OK;
+  bool go;
+  MXLO_TRY(check_lu_apply(ctx, dtype, Operands{res, V, k, ldr, ldv, n, n}, W, ldw, n, dinv_l, dinv_u, perm, work, "mxlo_lu_mul_block", go));
+  MXLO_TRY(check_mode(op_mode, "mxlo_lu_mul_block"));
+  if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
   const bool tr = op_mode != MXLO_OP_N;
-  if (dtype == MXLO_F64)
-    return for_groups((double *)res, ldr, (const double *)V, ldv, k, [&](double *r, const double *v, Group grp) {
-      return lu_mul_t<double>(ctx, r, (const double *)W, ldw, n, dinv_l, dinv_u, perm, work, v, tr, alpha, beta, grp);
-    });
-  return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
-    return lu_mul_t<float>(ctx, r, (const float *)W, ldw, n, dinv_l, dinv_u, perm, work, v, tr, alpha, beta, grp);
+  return for_real_groups(dtype, res, ldr, V, ldv, k, [&]<typename T>(T *r, const T *v, Group grp) {
+    return lu_mul_t<T>(ctx, r, (const T *)W, ldw, n, dinv_l, dinv_u, perm, work, v, tr, alpha, beta, grp);
   });
 }
 
@@ -1499,14 +1547,11 @@ __global__ void __launch_bounds__(kBlock) lu_snapshot_kernel(T *__restrict__ A2,
 
 constexpr int MAX_STEPS = 8;         // linalg.py's MAX_REFINE
 
-// the operands every refined apply adds to check_apply's: steps, the 2 n KB doubles of work, the snapshot's further storage
-int32_t check_refine(int32_t dtype, const Operands &o, int64_t n, int32_t steps, const double *work, const void *extra, int64_t eb,
-                     const char *what, const char *name) {
+// what every refined apply adds to check_apply's: steps, the 2 n KB doubles of work, the snapshot's further storage
+int32_t check_refine(int32_t dtype, const Operands &o, int64_t n, int32_t steps, const double *work, const Buf &snapshot, const char *what,
+                     bool go) {
   MXLO_REQUIRE(steps >= 0 && steps <= MAX_STEPS, MXLO_EINVAL, "%s: steps = %d outside 0 .. %d", what, steps, MAX_STEPS);
-  if (n == 0 || o.k == 0) return MXLO_OK;
-  MXLO_REQUIRE(extra, MXLO_EINVAL, "%s: null %s", what, name);
-  MXLO_TRY(check_extra(dtype, o, n, work, 2 * n * KB * 8, what, "the work matrices"));
-  return check_extra(dtype, o, n, extra, eb, what, name);
+  return go ? check_owned(dtype, o, {{work, 2 * n * KB * 8, "the work matrices"}, snapshot}, what) : MXLO_OK;
 }
 
 // one group of a refined apply: solve(v, xmode) runs the operator's chain of sweeps, resid() the residual launch
@@ -1553,20 +1598,16 @@ int32_t lu_refine_t(mxlo_ctx *ctx, T *res, int64_t ldr, const T *W, int64_t ld, 
 int32_t sym_refine(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t n, const double *dinv,
                    const double *d, const void *dg, double *work, const void *V, int64_t ldv, int64_t k, int32_t steps, double alpha,
                    double beta, bool ldl, const char *what) {
-  const Operands o{res, V, k, ldr, ldv};
-  MXLO_TRY(check_apply(ctx, dtype, o, W, ldw, n, dinv, work, what));
-  if (ldl && n > 0 && k > 0) {
-    MXLO_REQUIRE(d, MXLO_EINVAL, "%s: null pivots", what);
-    MXLO_TRY(check_extra(dtype, o, n, d, n * 8, what, "the pivots"));
-  }
-  MXLO_TRY(check_refine(dtype, o, n, steps, work, dg, n * (dtype == MXLO_F64 ? 8 : 4), what, "the diagonal of the snapshot"));
-  if (n == 0 || k == 0) return MXLO_OK;
+  const Operands o{res, V, k, ldr, ldv, n, n};
+  bool go;
+  MXLO_TRY(check_apply(ctx, dtype, o, W, ldw, n, dinv, work, what, go));
+  if (ldl && go) MXLO_TRY(check_owned(dtype, o, {{d, n * 8, "the pivots"}}, what));
+  MXLO_TRY(check_refine(dtype, o, n, steps, work, {dg, n * esize(dtype), "the diagonal of the snapshot"}, what, go));
+  if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
-  if (dtype == MXLO_F64)
-    return chol_refine_t<double>(ctx, (double *)res, ldr, (const double *)W, ldw, n, dinv, d, (const double *)dg, work, (const double *)V,
-                                 ldv, k, steps, alpha, beta);
-  return chol_refine_t<float>(ctx, (float *)res, ldr, (const float *)W, ldw, n, dinv, d, (const float *)dg, work, (const float *)V, ldv, k,
-                              steps, alpha, beta);
+  return with_real(dtype, [&]<typename T>() {
+    return chol_refine_t<T>(ctx, (T *)res, ldr, (const T *)W, ldw, n, dinv, d, (const T *)dg, work, (const T *)V, ldv, k, steps, alpha, beta);
+  });
 }
 
 }  // namespace
@@ -1583,14 +1624,12 @@ MXLO_API int32_t mxlo_sym_snapshot(mxlo_ctx *ctx, int32_t dtype, const void *M, 
                "%s: M, the factor's storage and the diagonal vector overlap", what);
   MXLO_DEVICE_GUARD(ctx);
   const unsigned nb = (unsigned)((n + NB - 1) / NB);
-  if (dtype == MXLO_F64)
-    hipLaunchKernelGGL((sym_snapshot_kernel<double>), dim3(nb, nb), dim3(kBlock), 0, ctx->stream, (double *)W, ldw, (double *)dg,
-                       (const double *)M, ldm, m_rowmajor ? 1 : 0, n);
-  else
-    hipLaunchKernelGGL((sym_snapshot_kernel<float>), dim3(nb, nb), dim3(kBlock), 0, ctx->stream, (float *)W, ldw, (float *)dg,
-                       (const float *)M, ldm, m_rowmajor ? 1 : 0, n);
-  MXLO_LAUNCH_CHECK();
-  return MXLO_OK;
+  return with_real(dtype, [&]<typename T>() -> int32_t {
+    hipLaunchKernelGGL((sym_snapshot_kernel<T>), dim3(nb, nb), dim3(kBlock), 0, ctx->stream, (T *)W, ldw, (T *)dg, (const T *)M, ldm,
+                       m_rowmajor ? 1 : 0, n);
+    MXLO_LAUNCH_CHECK();
+    return MXLO_OK;
+  });
 }
 
 MXLO_API int32_t mxlo_lu_snapshot(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, const int32_t *perm, void *A2, int64_t lda,
@@ -1605,12 +1644,11 @@ MXLO_API int32_t mxlo_lu_snapshot(mxlo_ctx *ctx, int32_t dtype, const void *M, i
                "%s: the snapshot overlaps M or the permutation", what);
   MXLO_DEVICE_GUARD(ctx);
   const dim3 grid((unsigned)((n + kBlock - 1) / kBlock), (unsigned)(n < 1024 ? n : 1024));
-  if (dtype == MXLO_F64)
-    hipLaunchKernelGGL((lu_snapshot_kernel<double>), grid, dim3(kBlock), 0, ctx->stream, (double *)A2, lda, (const double *)M, ldm, n, perm);
-  else
-    hipLaunchKernelGGL((lu_snapshot_kernel<float>), grid, dim3(kBlock), 0, ctx->stream, (float *)A2, lda, (const float *)M, ldm, n, perm);
-  MXLO_LAUNCH_CHECK();
-  return MXLO_OK;
+  return with_real(dtype, [&]<typename T>() -> int32_t {
+    hipLaunchKernelGGL((lu_snapshot_kernel<T>), grid, dim3(kBlock), 0, ctx->stream, (T *)A2, lda, (const T *)M, ldm, n, perm);
+    MXLO_LAUNCH_CHECK();
+    return MXLO_OK;
+  });
 }
 
 namespace {
@@ -1637,21 +1675,21 @@ MXLO_API int32_t mxlo_sym_residual(mxlo_ctx *ctx, int32_t dtype, double *R, cons
   if (n == 0 || k == 0) return MXLO_OK;
   MXLO_REQUIRE(dg, MXLO_EINVAL, "mxlo_sym_residual: null diagonal");
   MXLO_DEVICE_GUARD(ctx);
-  if (dtype == MXLO_F64)
-    return launch_residual<double>(ctx, 0, (const double *)U, ld, (const double *)dg, n, (const double *)V, ldv, nullptr, X, R, (int)k);
-  return launch_residual<float>(ctx, 0, (const float *)U, ld, (const float *)dg, n, (const float *)V, ldv, nullptr, X, R, (int)k);
+  return with_real(dtype, [&]<typename T>() {
+    return launch_residual<T>(ctx, 0, (const T *)U, ld, (const T *)dg, n, (const T *)V, ldv, nullptr, X, R, (int)k);
+  });
 }
 
 MXLO_API int32_t mxlo_gen_residual(mxlo_ctx *ctx, int32_t dtype, double *R, const void *A, int64_t ld, int64_t n, const void *V,
                                    int64_t ldv, const double *X, int64_t k, int32_t op_mode) {
   MXLO_TRY(check_residual(ctx, dtype, R, A, ld, nullptr, n, V, ldv, X, k, "mxlo_gen_residual"));
-  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "mxlo_gen_residual: op_mode %d", op_mode);
+  MXLO_TRY(check_mode(op_mode, "mxlo_gen_residual"));
   if (n == 0 || k == 0) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
   const int mode = op_mode == MXLO_OP_N ? 1 : 2;
-  if (dtype == MXLO_F64)
-    return launch_residual<double>(ctx, mode, (const double *)A, ld, (const double *)nullptr, n, (const double *)V, ldv, nullptr, X, R, (int)k);
-  return launch_residual<float>(ctx, mode, (const float *)A, ld, (const float *)nullptr, n, (const float *)V, ldv, nullptr, X, R, (int)k);
+  return with_real(dtype, [&]<typename T>() {
+    return launch_residual<T>(ctx, mode, (const T *)A, ld, (const T *)nullptr, n, (const T *)V, ldv, nullptr, X, R, (int)k);
+  });
 }
 
 MXLO_API int32_t mxlo_chol_mul_refine(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t n,
@@ -1671,19 +1709,19 @@ MXLO_API int32_t mxlo_lu_mul_refine(mxlo_ctx *ctx, int32_t dtype, void *res, int
                                     double *work, const void *V, int64_t ldv, int64_t k, int32_t steps, int32_t op_mode, double alpha,
                                     double beta) {
   const char *what = "mxlo_lu_mul_refine";
-  const Operands o{res, V, k, ldr, ldv};
-  MXLO_TRY(check_lu_apply(ctx, dtype, o, W, ldw, n, dinv_l, dinv_u, perm, work, what));
-  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "%s: op_mode %d", what, op_mode);
+  const Operands o{res, V, k, ldr, ldv, n, n};
+  bool go;
+  MXLO_TRY(check_lu_apply(ctx, dtype, o, W, ldw, n, dinv_l, dinv_u, perm, work, what, go));
+  MXLO_TRY(check_mode(op_mode, what));
   MXLO_REQUIRE(lda >= (n > 1 ? n : 1), MXLO_ESHAPE, "%s: lda = %lld < n", what, (long long)lda);
-  MXLO_TRY(check_refine(dtype, o, n, steps, work, A2, ((n - 1) * lda + n) * (dtype == MXLO_F64 ? 8 : 4), what, "the snapshot"));
-  if (n == 0 || k == 0) return MXLO_OK;
+  MXLO_TRY(check_refine(dtype, o, n, steps, work, {A2, mat_bytes(n, n, lda, esize(dtype)), "the snapshot"}, what, go));
+  if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
   const bool tr = op_mode != MXLO_OP_N;
-  if (dtype == MXLO_F64)
-    return lu_refine_t<double>(ctx, (double *)res, ldr, (const double *)W, ldw, n, dinv_l, dinv_u, perm, (const double *)A2, lda, work,
-                               (const double *)V, ldv, k, steps, tr, alpha, beta);
-  return lu_refine_t<float>(ctx, (float *)res, ldr, (const float *)W, ldw, n, dinv_l, dinv_u, perm, (const float *)A2, lda, work,
-                            (const float *)V, ldv, k, steps, tr, alpha, beta);
+  return with_real(dtype, [&]<typename T>() {
+    return lu_refine_t<T>(ctx, (T *)res, ldr, (const T *)W, ldw, n, dinv_l, dinv_u, perm, (const T *)A2, lda, work, (const T *)V, ldv, k, steps,
+                          tr, alpha, beta);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------- geqrf / qr_mul
@@ -2154,34 +2192,6 @@ int32_t launch_reflect(mxlo_ctx *ctx, const QrArgs &a) {
   return MXLO_OK;
 }
 
-// N: x = inv(R) (Q' v)[0:nf] — nb + 1 reflector launches, blocks ascending, then the descending sweep with R, which carries the
-// epilogue. T: y = Q [inv(R') u; 0] — the ascending sweep with R' into z, then nb + 1 reflector launches, blocks descending, the
-// last one with the epilogue over all mf entries. 2 nb + 1 launches either way. work: z (mf), then two sets of QG x NB slots.
-template <typename T>
-int32_t qr_mul_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t mf, int64_t nf, const double *tfac, const double *dinv,
-                 double *work, const T *v, bool trans, double alpha, double beta, const int *jpvt = nullptr, int64_t nfull = 0) {
-  const int64_t nb = (nf + NB - 1) / NB;
-  double *pb[2] = {work + mf, work + mf + (int64_t)QG * NB};
-  QrArgs a{};
-  a.W = W; a.ld = ld; a.mf = mf; a.nf = nf; a.z = work; a.res = res; a.alpha = alpha; a.beta = beta; a.tp_trans = trans ? 0 : 1;
-  if (trans) MXLO_TRY(sweep<T>(ctx, W, ld, nf, true, true, dinv, work, v, true, false, false, res, alpha, beta, nullptr, nullptr, jpvt));
-  for (int64_t i = 0; i <= nb; ++i) {                    // launch i reads the slots (i + 1) & 1 and leaves the slots i & 1
-    const int64_t kp = trans ? nb - i : i - 1, kn = trans ? nb - 1 - i : i;
-    a.v = (!trans && i == 0) ? v : nullptr;
-    a.load = i == 0 ? (trans ? 2 : 1) : 0;
-    a.jbp = a.jbn = 0;
-    if (i > 0) { a.jp = kp * NB; a.jbp = (int)(nf - a.jp < NB ? nf - a.jp : NB); a.tp = tfac + kp * NB2; }
-    if (i < nb) { a.jn = kn * NB; a.jbn = (int)(nf - a.jn < NB ? nf - a.jn : NB); }
-    a.pin = pb[(i + 1) & 1]; a.pout = pb[i & 1];
-    a.epi = trans && i == nb;
-    if (jpvt && !trans && i == nb) { a.fill_idx = jpvt; a.fill_lo = nf; a.fill_hi = nfull; }
-    MXLO_TRY(launch_reflect<T>(ctx, a));
-  }
-  if (trans) return MXLO_OK;
-  return sweep<T>(ctx, W, ld, nf, true, false, dinv, work, (const T *)nullptr, true, false, true, res, alpha, beta, nullptr, nullptr,
-                  nullptr, jpvt);
-}
-
 // qr_reflect_kernel carrying a group of kb <= KB right-hand sides, in a workgroup of 16 waves. Per right-hand side the
 // operations and their order are the vector kernel's (qr_quarter and (p0 + p1) + (p2 + p3) for the slots, the four 16-term fma
 // chains for w = T d and for z -= V w, one fma chain per (row, column) over the workgroup's chunks for the new dots, then
@@ -2333,36 +2343,70 @@ int32_t launch_reflect_block(mxlo_ctx *ctx, const QrArgs &a) {
 inline int64_t qr_work(int64_t mf) { return mf + 2 * (int64_t)QG * NB; }
 inline int64_t qr_block_work(int64_t mf, int64_t nf) { return KB * (mf + nf + 2 * (int64_t)QG * NB); }
 
-// qr_mul_t for a group of grp.kb columns: the same 2 nb + 1 launches on the same grids. The sweep with R keeps its own
-// kernel and its own nf x kb matrix zc: N — the last reflector launch writes rows < nf of z there (the others are not needed
-// again); T — the first one reads them from there.
+// One reflector chain, nb + 1 launches over the leading nc columns of a factor with `rows` rows; launch i reads the slots
+// pb[(i + 1) & 1] and leaves the slots pb[i & 1]. a carries what the stages of an apply share (z, res, alpha, beta, the group,
+// zc) and is this chain's own copy. !trans: Q', blocks ascending — launch 0 loads v (through idx if given), the last launch
+// of a group (a.kb > 0) writes rows < nc to zc and, given a fill, the zeros of a rank-deficient solution. trans: Q, blocks
+// descending — launch 0 takes rows < nc from z (zc) and zero below, the last launch writes res (through idx if given).
+struct Fill {
+  const int *idx;
+  int64_t lo, hi;
+};
+
 template <typename T>
-int32_t qr_mul_block_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t mf, int64_t nf, const double *tfac, const double *dinv,
-                       double *work, const T *V, bool trans, double alpha, double beta, Group grp, const int *jpvt = nullptr,
-                       int64_t nfull = 0) {
-  const int64_t nb = (nf + NB - 1) / NB, slots = (int64_t)KB * QG * NB;
-  double *pb[2] = {work + KB * mf, work + KB * mf + slots};
-  QrArgs a{};
-  a.W = W; a.ld = ld; a.mf = mf; a.nf = nf; a.z = work; a.res = res; a.alpha = alpha; a.beta = beta; a.tp_trans = trans ? 0 : 1;
-  a.kb = grp.kb; a.ldr = grp.ldr; a.ldv = grp.ldv; a.zc = pb[1] + slots;
-  if (trans)
-    MXLO_TRY(sweep<T>(ctx, W, ld, nf, true, true, dinv, a.zc, V, true, false, false, res, alpha, beta, nullptr, nullptr, jpvt, nullptr,
-                      false, grp));
-  for (int64_t i = 0; i <= nb; ++i) {                    // launch i reads the slots (i + 1) & 1 and leaves the slots i & 1
+int32_t reflect_chain(mxlo_ctx *ctx, QrArgs a, const T *W, int64_t ld, int64_t rows, int64_t nc, const double *tfac, double *const *pb,
+                      bool trans, const T *v, const int *idx = nullptr, const Fill *fill = nullptr) {
+  const int64_t nb = (nc + NB - 1) / NB;
+  a.W = W; a.ld = ld; a.mf = rows; a.nf = nc; a.tp_trans = trans ? 0 : 1;
+  for (int64_t i = 0; i <= nb; ++i) {
     const int64_t kp = trans ? nb - i : i - 1, kn = trans ? nb - 1 - i : i;
-    a.v = (!trans && i == 0) ? V : nullptr;
+    a.v = (!trans && i == 0) ? v : nullptr;
     a.load = i == 0 ? (trans ? 2 : 1) : 0;
     a.jbp = a.jbn = 0;
-    if (i > 0) { a.jp = kp * NB; a.jbp = (int)(nf - a.jp < NB ? nf - a.jp : NB); a.tp = tfac + kp * NB2; }
-    if (i < nb) { a.jn = kn * NB; a.jbn = (int)(nf - a.jn < NB ? nf - a.jn : NB); }
+    if (i > 0) { a.jp = kp * NB; a.jbp = (int)(nc - a.jp < NB ? nc - a.jp : NB); a.tp = tfac + kp * NB2; }
+    if (i < nb) { a.jn = kn * NB; a.jbn = (int)(nc - a.jn < NB ? nc - a.jn : NB); }
     a.pin = pb[(i + 1) & 1]; a.pout = pb[i & 1];
     a.epi = trans && i == nb;
-    a.zc_out = !trans && i == nb;
-    if (jpvt && !trans && i == nb) { a.fill_idx = jpvt; a.fill_lo = nf; a.fill_hi = nfull; }
-    MXLO_TRY(launch_reflect_block<T>(ctx, a));
+    a.zc_out = a.kb > 0 && !trans && i == nb;
+    a.idx = ((!trans && i == 0) || a.epi) ? idx : nullptr;
+    if (fill && !trans && i == nb) { a.fill_idx = fill->idx; a.fill_lo = fill->lo; a.fill_hi = fill->hi; }   // the last launch: none follows
+    MXLO_TRY(a.kb > 0 ? launch_reflect_block<T>(ctx, a) : launch_reflect<T>(ctx, a));
   }
+  return MXLO_OK;
+}
+
+// what the stages of an apply share, on the vector apply's work (grp.kb == 0: z (mf), then two sets of QG x NB slots) or the
+// block apply's (z (mf x KB), two sets of slots per right-hand side, then zc); zs is what the sweep with R works on
+struct QrStages {
+  QrArgs a{};
+  double *pb[2], *zs;
+  template <typename T>
+  QrStages(T *res, int64_t mf, double *work, double alpha, double beta, Group grp) {
+    const bool blk = grp.kb > 0;
+    const int64_t slots = (int64_t)(blk ? KB : 1) * QG * NB, zlen = (blk ? KB : 1) * mf;
+    pb[0] = work + zlen; pb[1] = work + zlen + slots;
+    a.z = work; a.res = res; a.alpha = alpha; a.beta = beta;
+    a.kb = grp.kb; a.ldr = grp.ldr; a.ldv = grp.ldv; a.zc = blk ? pb[1] + slots : nullptr;
+    zs = blk ? a.zc : work;
+  }
+};
+
+// N: x = inv(R) (Q' v)[0:nf] — the chain with Q', then the descending sweep with R, which carries the epilogue. T: y = Q [inv(R') u;
+// 0] — the ascending sweep with R', then the chain with Q, whose last launch has the epilogue over all mf entries. 2 nb + 1
+// launches either way, for a vector and for a group of grp.kb columns alike; the sweep with R keeps its own kernel and, for a
+// group, its own nf x kb matrix zc. jpvt (the pivoted form): nf is the rank, nfull the number of columns.
+template <typename T>
+int32_t qr_mul_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t mf, int64_t nf, const double *tfac, const double *dinv,
+                 double *work, const T *v, bool trans, double alpha, double beta, Group grp = {}, const int *jpvt = nullptr,
+                 int64_t nfull = 0) {
+  const QrStages s(res, mf, work, alpha, beta, grp);
+  const Fill fill{jpvt, nf, nfull};
+  if (trans)
+    MXLO_TRY(sweep<T>(ctx, W, ld, nf, true, true, dinv, s.zs, v, true, false, false, res, alpha, beta, nullptr, nullptr, jpvt, nullptr, false,
+                      grp));
+  MXLO_TRY(reflect_chain<T>(ctx, s.a, W, ld, mf, nf, tfac, s.pb, trans, v, nullptr, jpvt ? &fill : nullptr));
   if (trans) return MXLO_OK;
-  return sweep<T>(ctx, W, ld, nf, true, false, dinv, a.zc, (const T *)nullptr, true, false, true, res, alpha, beta, nullptr, nullptr,
+  return sweep<T>(ctx, W, ld, nf, true, false, dinv, s.zs, (const T *)nullptr, true, false, true, res, alpha, beta, nullptr, nullptr,
                   nullptr, jpvt, false, grp);
 }
 
@@ -2401,53 +2445,22 @@ int32_t cod_factor_t(mxlo_ctx *ctx, const T *W, int64_t ldw, int64_t nf, int64_t
   return geqrf_chain_t<T>(ctx, W2, nf, nf, rank, tfac2, dinv2, fwork, info_dev);
 }
 
-// One reflector chain of a pinv apply, the nb + 1 launches of qr_mul_t's loop, over the leading nc columns of a factor with
-// `rows` rows. a carries what the two chains share (z, res, alpha, beta, the group). !trans: Q', the FIRST stage — launch 0
-// loads v (through idx if given), the last launch of a group writes rows < nc to zc. trans: Q, the LAST stage — launch 0 takes
-// rows < nc from z (zc) and zero below, the last launch writes res (through idx if given).
-template <typename T>
-int32_t pinv_chain(mxlo_ctx *ctx, QrArgs a, const T *W, int64_t ld, int64_t rows, int64_t nc, const double *tfac, double *const *pb,
-                   bool trans, const T *v, const int *idx) {
-  const int64_t nb = (nc + NB - 1) / NB;
-  a.W = W; a.ld = ld; a.mf = rows; a.nf = nc; a.tp_trans = trans ? 0 : 1;
-  for (int64_t i = 0; i <= nb; ++i) {                    // launch i reads the slots (i + 1) & 1 and leaves the slots i & 1
-    const int64_t kp = trans ? nb - i : i - 1, kn = trans ? nb - 1 - i : i;
-    a.v = (!trans && i == 0) ? v : nullptr;
-    a.load = i == 0 ? (trans ? 2 : 1) : 0;
-    a.jbp = a.jbn = 0;
-    if (i > 0) { a.jp = kp * NB; a.jbp = (int)(nc - a.jp < NB ? nc - a.jp : NB); a.tp = tfac + kp * NB2; }
-    if (i < nb) { a.jn = kn * NB; a.jbn = (int)(nc - a.jn < NB ? nc - a.jn : NB); }
-    a.pin = pb[(i + 1) & 1]; a.pout = pb[i & 1];
-    a.epi = trans && i == nb;
-    a.zc_out = a.kb > 0 && !trans && i == nb;
-    a.idx = ((!trans && i == 0) || a.epi) ? idx : nullptr;
-    MXLO_TRY(a.kb > 0 ? launch_reflect_block<T>(ctx, a) : launch_reflect<T>(ctx, a));
-  }
-  return MXLO_OK;
-}
-
 // The factor of geqp3 (W, tfac; mf x nf, rank r < nf), the permutation and the second factor (W2: nf x r with ld nf, tfac2,
 // dinv2). N: res (nf) — Q1' over the leading r columns of W, w = inv(R2') z[0:r], Q2 [w; 0] over the nf rows of W2 with
 // res[jpvt[i]] written by the epilogue. T: res (mf) — Q2' over W2 with z[i] = u[jpvt[i]] gathered by launch 0, w = inv(R2)
-// z[0:r], Q1 [w; 0]. work is qr_mul_t's (grp.kb == 0) or qr_mul_block_t's: the second chain's z has nf <= mf rows, its sweep
+// z[0:r], Q1 [w; 0]. work is qr_mul_t's, for a vector or for a group: the second chain's z has nf <= mf rows, its sweep
 // matrix r <= nf, and both chains use the same two sets of slots, so nothing more is needed.
 template <typename T>
 int32_t pinv_mul_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t mf, int64_t nf, const double *tfac, const int *jpvt, int64_t r,
                    const T *W2, const double *tfac2, const double *dinv2, double *work, const T *v, bool trans, double alpha, double beta,
                    Group grp = {}) {
-  const bool blk = grp.kb > 0;
-  const int64_t slots = (int64_t)(blk ? KB : 1) * QG * NB, zlen = (blk ? KB : 1) * mf;
-  double *pb[2] = {work + zlen, work + zlen + slots};
-  QrArgs a{};
-  a.z = work; a.res = res; a.alpha = alpha; a.beta = beta;
-  a.kb = grp.kb; a.ldr = grp.ldr; a.ldv = grp.ldv; a.zc = blk ? pb[1] + slots : nullptr;
-  double *zs = blk ? a.zc : work;                        // what the sweep works on: r x kb with column stride r, or z[0:r]
-  if (!trans) MXLO_TRY(pinv_chain<T>(ctx, a, W, ld, mf, r, tfac, pb, false, v, nullptr));
-  else MXLO_TRY(pinv_chain<T>(ctx, a, W2, nf, nf, r, tfac2, pb, false, v, jpvt));
-  MXLO_TRY(sweep<T>(ctx, W2, nf, r, true, !trans, dinv2, zs, (const T *)nullptr, true, false, false, res, alpha, beta, nullptr, nullptr,
+  const QrStages s(res, mf, work, alpha, beta, grp);
+  if (!trans) MXLO_TRY(reflect_chain<T>(ctx, s.a, W, ld, mf, r, tfac, s.pb, false, v));
+  else MXLO_TRY(reflect_chain<T>(ctx, s.a, W2, nf, nf, r, tfac2, s.pb, false, v, jpvt));
+  MXLO_TRY(sweep<T>(ctx, W2, nf, r, true, !trans, dinv2, s.zs, (const T *)nullptr, true, false, false, res, alpha, beta, nullptr, nullptr,
                     nullptr, nullptr, false, grp));
-  if (!trans) return pinv_chain<T>(ctx, a, W2, nf, nf, r, tfac2, pb, true, (const T *)nullptr, jpvt);
-  return pinv_chain<T>(ctx, a, W, ld, mf, r, tfac, pb, true, (const T *)nullptr, nullptr);
+  if (!trans) return reflect_chain<T>(ctx, s.a, W2, nf, nf, r, tfac2, s.pb, true, (const T *)nullptr, jpvt);
+  return reflect_chain<T>(ctx, s.a, W, ld, mf, r, tfac, s.pb, true, (const T *)nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------- geqp3
@@ -2794,96 +2807,133 @@ int32_t geqp3_finish_t(mxlo_ctx *ctx, const T *W, int64_t ldw, int64_t mf, int64
 
 }  // namespace
 
+namespace {
+// the tall orientation every entry point of the rectangular family takes, 1 <= nf <= mf <= ldw, within the index range of the
+// kernels; grid_limit: a factorisation also has the block columns in a grid dimension
+int32_t check_tall(int64_t mf, int64_t nf, int64_t ldw, bool grid_limit, const char *what) {
+  MXLO_REQUIRE(nf >= 1 && mf >= nf && ldw >= mf, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld (1 <= nf <= mf), ldw = %lld", what, (long long)mf,
+               (long long)nf, (long long)ldw);
+  MXLO_REQUIRE(mf < (1LL << 31) - NB && (!grid_limit || (nf + NB - 1) / NB <= 65535), MXLO_ESHAPE, "%s: mf = %lld, nf = %lld is too large",
+               what, (long long)mf, (long long)nf);
+  return MXLO_OK;
+}
+
+int32_t check_scratch(int64_t scratch_len, int64_t needed, const char *what) {
+  MXLO_REQUIRE(scratch_len >= needed, MXLO_ESHAPE, "%s: scratch of %lld doubles, %lld needed", what, (long long)scratch_len, (long long)needed);
+  return MXLO_OK;
+}
+
+// M as mxlo_geqrf and mxlo_geqp3 find it stored: mr x mc, column-major (m_trans: the nf x mf storage of F')
+int32_t check_source(const void *M, int64_t ldm, int32_t m_trans, int64_t mf, int64_t nf, int64_t es, Buf &m, const char *what) {
+  const int64_t mr = m_trans ? nf : mf, mc = m_trans ? mf : nf;
+  MXLO_REQUIRE(ldm >= mr, MXLO_ESHAPE, "%s: ldm = %lld < %lld", what, (long long)ldm, (long long)mr);
+  m = {M, mat_bytes(mr, mc, ldm, es), "M"};
+  return MXLO_OK;
+}
+
+// What the six rectangular applies check first: ctx, dtype, op_mode, the shape and — rank_max >= 0: the pivoted forms — the
+// rank. Sizes that feed a byte extent are computed after this, from a valid shape. A vector entry point then passes
+// k = 1 in the leading dimension mf, which holds either operand.
+int32_t check_qr_shape(mxlo_ctx *ctx, int32_t dtype, int32_t op_mode, int64_t ldw, int64_t mf, int64_t nf, int64_t rank, int64_t rank_max,
+                       const char *what) {
+  MXLO_TRY(check_real(ctx, dtype, what));
+  MXLO_TRY(check_mode(op_mode, what));
+  MXLO_TRY(check_tall(mf, nf, ldw, false, what));
+  MXLO_REQUIRE(rank_max < 0 || (rank >= 1 && rank <= rank_max), MXLO_ESHAPE, "%s: rank = %lld (1 <= rank <= %lld for nf = %lld)", what,
+               (long long)rank, (long long)rank_max, (long long)nf);
+  return MXLO_OK;
+}
+
+inline Operands qr_operands(const void *res, int64_t ldr, const void *V, int64_t ldv, int64_t k, int64_t mf, int64_t nf, int32_t op_mode) {
+  const bool tr = op_mode != MXLO_OP_N;
+  return {res, V, k, ldr, ldv, tr ? mf : nf, tr ? nf : mf};
+}
+
+// mxlo_qr_mul* and, with jpvt and the rank, mxlo_qrp_mul*; block: the work space is qr_block_work's. The T factors and the
+// block inverses count as those of all nf columns, whatever the rank.
+int32_t check_qr_apply(mxlo_ctx *ctx, int32_t dtype, const void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf, int64_t nf,
+                       const double *tfac, const double *dinv, bool pivoted, const int32_t *jpvt, int64_t rank, const double *work,
+                       bool block, const void *V, int64_t ldv, int64_t k, int32_t op_mode, const char *what, bool &go) {
+  go = false;
+  MXLO_TRY(check_qr_shape(ctx, dtype, op_mode, ldw, mf, nf, rank, pivoted ? nf : -1, what));
+  const Operands o = qr_operands(res, ldr, V, ldv, k, mf, nf, op_mode);
+  MXLO_TRY(check_operands(dtype, o, false,
+                          {{W, mat_bytes(mf, nf, ldw, esize(dtype)), "the factor"},
+                           {tfac, blocks_bytes(nf), "the T factors"},
+                           {dinv, blocks_bytes(nf), "the block inverses"},
+                           {work, (block ? qr_block_work(mf, nf) : qr_work(mf)) * 8, "the work space"}},
+                          what, go));
+  return pivoted && go ? check_owned(dtype, o, {{jpvt, nf * 4, "the permutation"}}, what) : MXLO_OK;
+}
+
+// mxlo_pinv_mul*: rank < nf (rank == nf is mxlo_qrp_mul's), and both factors; the T factors and the block inverses of both
+// count as those of `rank` columns
+int32_t check_pinv(mxlo_ctx *ctx, int32_t dtype, const void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf, int64_t nf,
+                   const double *tfac, const int32_t *jpvt, int64_t rank, const void *W2, const double *tfac2, const double *dinv2,
+                   const double *work, bool block, const void *V, int64_t ldv, int64_t k, int32_t op_mode, const char *what, bool &go) {
+  go = false;
+  MXLO_TRY(check_qr_shape(ctx, dtype, op_mode, ldw, mf, nf, rank, nf - 1, what));
+  const int64_t es = esize(dtype);
+  return check_operands(dtype, qr_operands(res, ldr, V, ldv, k, mf, nf, op_mode), false,
+                        {{W, mat_bytes(mf, nf, ldw, es), "the factor"},
+                         {tfac, blocks_bytes(rank), "the T factors"},
+                         {jpvt, nf * 4, "the permutation"},
+                         {W2, nf * rank * es, "the second factor"},
+                         {tfac2, blocks_bytes(rank), "the second T factors"},
+                         {dinv2, blocks_bytes(rank), "the block inverses"},
+                         {work, (block ? qr_block_work(mf, nf) : qr_work(mf)) * 8, "the work space"}},
+                        what, go);
+}
+}  // namespace
+
 MXLO_API int32_t mxlo_geqrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_trans, void *W, int64_t ldw, int64_t mf,
                             int64_t nf, double *tfac, double *dinv, double *scratch, int64_t scratch_len, int32_t *info_dev,
                             int32_t *info) {
   const char *what = "mxlo_geqrf";
-  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
-  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
-  MXLO_REQUIRE(nf >= 1 && mf >= nf && ldw >= mf, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld (1 <= nf <= mf), ldw = %lld", what, (long long)mf,
-               (long long)nf, (long long)ldw);
-  MXLO_REQUIRE(mf < (1LL << 31) - NB && (nf + NB - 1) / NB <= 65535, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld is too large", what,
-               (long long)mf, (long long)nf);
+  MXLO_TRY(check_real(ctx, dtype, what));
+  MXLO_TRY(check_tall(mf, nf, ldw, true, what));
   MXLO_REQUIRE(M && W && tfac && dinv && scratch && info_dev && info, MXLO_EINVAL, "%s: null operand", what);
   *info = 0;
-  const int64_t mr = m_trans ? nf : mf, mc = m_trans ? mf : nf;       // M as it is stored: mr x mc, column-major
-  MXLO_REQUIRE(ldm >= mr, MXLO_ESHAPE, "%s: ldm = %lld < %lld", what, (long long)ldm, (long long)mr);
-  MXLO_REQUIRE(scratch_len >= geqrf_scratch(nf), MXLO_ESHAPE, "%s: scratch of %lld doubles, %lld needed", what, (long long)scratch_len,
-               (long long)geqrf_scratch(nf));
-  const int64_t es = dtype == MXLO_F64 ? 8 : 4, nb = (nf + NB - 1) / NB;
-  const std::pair<const void *, int64_t> bufs[] = {{M, ((mc - 1) * ldm + mr) * es}, {W, ((nf - 1) * ldw + mf) * es}, {tfac, nb * NB2 * 8},
-                                                   {dinv, nb * NB2 * 8},           {scratch, scratch_len * 8},      {info_dev, 4}};
-  for (size_t x = 0; x < 6; ++x)
-    for (size_t y = x + 1; y < 6; ++y)
-      MXLO_REQUIRE(!bytes_overlap(bufs[x].first, bufs[x].second, bufs[y].first, bufs[y].second), MXLO_EINVAL,
-                   "%s: M, the factor, the T factors, the block inverses, the scratch and the info word overlap", what);
-  MXLO_REQUIRE(!ctx->capturing, MXLO_ESTATE, "%s: reads its info word back, which a graph capture cannot hold", what);
+  const int64_t es = esize(dtype);
+  Buf m;
+  MXLO_TRY(check_source(M, ldm, m_trans, mf, nf, es, m, what));
+  MXLO_TRY(check_scratch(scratch_len, geqrf_scratch(nf), what));
+  MXLO_TRY(disjoint({m, {W, mat_bytes(mf, nf, ldw, es), "the factor"}, {tfac, blocks_bytes(nf), "the T factors"},
+                     {dinv, blocks_bytes(nf), "the block inverses"}, {scratch, scratch_len * 8, "the scratch"}, {info_dev, 4, "the info word"}},
+                    what));
+  MXLO_TRY(refuse_capture(ctx, what));
   MXLO_DEVICE_GUARD(ctx);
-  if (dtype == MXLO_F64)
-    MXLO_TRY(geqrf_t<double>(ctx, (const double *)M, ldm, m_trans ? 1 : 0, (double *)W, ldw, mf, nf, tfac, dinv, scratch, info_dev));
-  else MXLO_TRY(geqrf_t<float>(ctx, (const float *)M, ldm, m_trans ? 1 : 0, (float *)W, ldw, mf, nf, tfac, dinv, scratch, info_dev));
-  MXLO_HIP(hipMemcpyAsync(info, info_dev, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  MXLO_HIP(hipStreamSynchronize(ctx->stream));
-  return MXLO_OK;
+  MXLO_TRY(with_real(dtype, [&]<typename T>() {
+    return geqrf_t<T>(ctx, (const T *)M, ldm, m_trans ? 1 : 0, (T *)W, ldw, mf, nf, tfac, dinv, scratch, info_dev);
+  }));
+  return read_back(ctx, info_dev, info, 1);
 }
 
 MXLO_API int32_t mxlo_qr_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t mf, int64_t nf,
                              const double *tfac, const double *dinv, double *work, const void *v, int32_t op_mode, double alpha,
                              double beta) {
-  const char *what = "mxlo_qr_mul";
-  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
-  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
-  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "%s: op_mode %d", what, op_mode);
-  MXLO_REQUIRE(nf >= 1 && mf >= nf && ldw >= mf && mf < (1LL << 31) - NB, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld (1 <= nf <= mf), ldw = %lld",
-               what, (long long)mf, (long long)nf, (long long)ldw);
-  MXLO_REQUIRE(res && W && tfac && dinv && work && v, MXLO_EINVAL, "%s: null operand", what);
-  const bool tr = op_mode != MXLO_OP_N;
-  const int64_t es = dtype == MXLO_F64 ? 8 : 4, nb = (nf + NB - 1) / NB;
-  const int64_t rb = (tr ? mf : nf) * es, vb = (tr ? nf : mf) * es;
-  MXLO_REQUIRE((res == v && mf == nf) || !bytes_overlap(res, rb, v, vb), MXLO_EINVAL,
-               "%s: res overlaps v without being v (only mul!(x, op, x) of a square operator is defined)", what);
-  const std::pair<const void *, int64_t> own[] = {{W, ((nf - 1) * ldw + mf) * es}, {tfac, nb * NB2 * 8}, {dinv, nb * NB2 * 8},
-                                                  {work, qr_work(mf) * 8}};
-  for (const auto &[p, pb] : own)
-    MXLO_REQUIRE(!bytes_overlap(res, rb, p, pb) && !bytes_overlap(v, vb, p, pb), MXLO_EINVAL,
-                 "%s: res / v overlap the factor, the T factors, the block inverses or the work vector", what);
+  bool go;
+  MXLO_TRY(check_qr_apply(ctx, dtype, res, mf, W, ldw, mf, nf, tfac, dinv, false, nullptr, 0, work, false, v, mf, 1, op_mode, "mxlo_qr_mul",
+                          go));
+  if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
-  if (dtype == MXLO_F64)
-    return qr_mul_t<double>(ctx, (double *)res, (const double *)W, ldw, mf, nf, tfac, dinv, work, (const double *)v, tr, alpha, beta);
-  return qr_mul_t<float>(ctx, (float *)res, (const float *)W, ldw, mf, nf, tfac, dinv, work, (const float *)v, tr, alpha, beta);
+  const bool tr = op_mode != MXLO_OP_N;
+  return with_real(dtype, [&]<typename T>() {
+    return qr_mul_t<T>(ctx, (T *)res, (const T *)W, ldw, mf, nf, tfac, dinv, work, (const T *)v, tr, alpha, beta);
+  });
 }
 
 MXLO_API int32_t mxlo_qr_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf,
                                    int64_t nf, const double *tfac, const double *dinv, double *work, const void *V, int64_t ldv,
                                    int64_t k, int32_t op_mode, double alpha, double beta) {
-  const char *what = "mxlo_qr_mul_block";
-  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
-  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
-  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "%s: op_mode %d", what, op_mode);
-  MXLO_REQUIRE(nf >= 1 && mf >= nf && ldw >= mf && mf < (1LL << 31) - NB, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld (1 <= nf <= mf), ldw = %lld",
-               what, (long long)mf, (long long)nf, (long long)ldw);
-  const bool tr = op_mode != MXLO_OP_N;
-  const int64_t rrows = tr ? mf : nf, vrows = tr ? nf : mf;
-  MXLO_REQUIRE(k >= 0 && ldr >= rrows && ldv >= vrows, MXLO_ESHAPE, "%s: k = %lld, ldr = %lld for %lld rows, ldv = %lld for %lld rows", what,
-               (long long)k, (long long)ldr, (long long)rrows, (long long)ldv, (long long)vrows);
-  if (k == 0) return MXLO_OK;
-  MXLO_REQUIRE(res && W && tfac && dinv && work && V, MXLO_EINVAL, "%s: null operand", what);
-  const int64_t es = dtype == MXLO_F64 ? 8 : 4, nb = (nf + NB - 1) / NB;
-  const int64_t rb = ((k - 1) * ldr + rrows) * es, vb = ((k - 1) * ldv + vrows) * es;
-  MXLO_REQUIRE((res == V && ldr == ldv && mf == nf) || !bytes_overlap(res, rb, V, vb), MXLO_EINVAL,
-               "%s: res overlaps V without being V (only mul!(X, op, X) of a square operator, as the same matrix, is defined)", what);
-  const std::pair<const void *, int64_t> own[] = {{W, ((nf - 1) * ldw + mf) * es}, {tfac, nb * NB2 * 8}, {dinv, nb * NB2 * 8},
-                                                  {work, qr_block_work(mf, nf) * 8}};
-  for (const auto &[p, pb] : own)
-    MXLO_REQUIRE(!bytes_overlap(res, rb, p, pb) && !bytes_overlap(V, vb, p, pb), MXLO_EINVAL,
-                 "%s: res or V overlaps the factor, the T factors, the block inverses or the work space", what);
+  bool go;
+  MXLO_TRY(check_qr_apply(ctx, dtype, res, ldr, W, ldw, mf, nf, tfac, dinv, false, nullptr, 0, work, true, V, ldv, k, op_mode,
+                          "mxlo_qr_mul_block", go));
+  if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
-  if (dtype == MXLO_F64)
-    return for_groups((double *)res, ldr, (const double *)V, ldv, k, [&](double *r, const double *v, Group grp) {
-      return qr_mul_block_t<double>(ctx, r, (const double *)W, ldw, mf, nf, tfac, dinv, work, v, tr, alpha, beta, grp);
-    });
-  return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
-    return qr_mul_block_t<float>(ctx, r, (const float *)W, ldw, mf, nf, tfac, dinv, work, v, tr, alpha, beta, grp);
+  const bool tr = op_mode != MXLO_OP_N;
+  return for_real_groups(dtype, res, ldr, V, ldv, k, [&]<typename T>(T *r, const T *v, Group grp) {
+    return qr_mul_t<T>(ctx, r, (const T *)W, ldw, mf, nf, tfac, dinv, work, v, tr, alpha, beta, grp);
   });
 }
 
@@ -2891,199 +2941,110 @@ MXLO_API int32_t mxlo_geqp3(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t
                             int64_t nf, double *tfac, double *dinv, int32_t *jpvt, double rtol, double *scratch, int64_t scratch_len,
                             int32_t *info_dev, int32_t *info, int32_t *rank) {
   const char *what = "mxlo_geqp3";
-  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
-  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
-  MXLO_REQUIRE(nf >= 1 && mf >= nf && ldw >= mf, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld (1 <= nf <= mf), ldw = %lld", what, (long long)mf,
-               (long long)nf, (long long)ldw);
-  MXLO_REQUIRE(mf < (1LL << 31) - NB && (nf + NB - 1) / NB <= 65535, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld is too large", what,
-               (long long)mf, (long long)nf);
+  MXLO_TRY(check_real(ctx, dtype, what));
+  MXLO_TRY(check_tall(mf, nf, ldw, true, what));
   MXLO_REQUIRE(rtol >= 0.0 && rtol < 1.0, MXLO_EINVAL, "%s: rtol = %g (0 <= rtol < 1)", what, rtol);
   MXLO_REQUIRE(M && W && tfac && dinv && jpvt && scratch && info_dev && info && rank, MXLO_EINVAL, "%s: null operand", what);
   *info = 0;
   *rank = 0;
-  const int64_t mr = m_trans ? nf : mf, mc = m_trans ? mf : nf;       // M as it is stored: mr x mc, column-major
-  MXLO_REQUIRE(ldm >= mr, MXLO_ESHAPE, "%s: ldm = %lld < %lld", what, (long long)ldm, (long long)mr);
-  MXLO_REQUIRE(scratch_len >= geqp3_scratch(mf, nf), MXLO_ESHAPE, "%s: scratch of %lld doubles, %lld needed", what, (long long)scratch_len,
-               (long long)geqp3_scratch(mf, nf));
-  const int64_t es = dtype == MXLO_F64 ? 8 : 4, nb = (nf + NB - 1) / NB;
-  const std::pair<const void *, int64_t> bufs[] = {{M, ((mc - 1) * ldm + mr) * es}, {W, ((nf - 1) * ldw + mf) * es}, {tfac, nb * NB2 * 8},
-                                                   {dinv, nb * NB2 * 8},           {jpvt, nf * 4},                  {scratch, scratch_len * 8},
-                                                   {info_dev, 8}};
-  for (size_t x = 0; x < 7; ++x)
-    for (size_t y = x + 1; y < 7; ++y)
-      MXLO_REQUIRE(!bytes_overlap(bufs[x].first, bufs[x].second, bufs[y].first, bufs[y].second), MXLO_EINVAL,
-                   "%s: M, the factor, the T factors, the block inverses, the permutation, the scratch and the info words overlap", what);
-  MXLO_REQUIRE(!ctx->capturing, MXLO_ESTATE, "%s: reads its info word and the rank back, which a graph capture cannot hold", what);
+  const int64_t es = esize(dtype);
+  Buf m;
+  MXLO_TRY(check_source(M, ldm, m_trans, mf, nf, es, m, what));
+  MXLO_TRY(check_scratch(scratch_len, geqp3_scratch(mf, nf), what));
+  MXLO_TRY(disjoint({m, {W, mat_bytes(mf, nf, ldw, es), "the factor"}, {tfac, blocks_bytes(nf), "the T factors"},
+                     {dinv, blocks_bytes(nf), "the block inverses"}, {jpvt, nf * 4, "the permutation"},
+                     {scratch, scratch_len * 8, "the scratch"}, {info_dev, 8, "the info words"}},
+                    what));
+  MXLO_TRY(refuse_capture(ctx, what));
   MXLO_DEVICE_GUARD(ctx);
   const QpScratch l = qp_layout(scratch, mf, nf);
-  if (dtype == MXLO_F64)
-    MXLO_TRY(geqp3_t<double>(ctx, (const double *)M, ldm, m_trans ? 1 : 0, (double *)W, ldw, mf, nf, jpvt, rtol, l, info_dev));
-  else MXLO_TRY(geqp3_t<float>(ctx, (const float *)M, ldm, m_trans ? 1 : 0, (float *)W, ldw, mf, nf, jpvt, rtol, l, info_dev));
+  MXLO_TRY(with_real(dtype, [&]<typename T>() {
+    return geqp3_t<T>(ctx, (const T *)M, ldm, m_trans ? 1 : 0, (T *)W, ldw, mf, nf, jpvt, rtol, l, info_dev);
+  }));
   int32_t words[2] = {0, 0};
-  MXLO_HIP(hipMemcpyAsync(words, info_dev, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
-  MXLO_HIP(hipStreamSynchronize(ctx->stream));
+  MXLO_TRY(read_back(ctx, info_dev, words, 2));
   *info = words[0];
   *rank = words[1];
   if (words[0] != 0 || words[1] < 1) return MXLO_OK;
-  if (dtype == MXLO_F64) return geqp3_finish_t<double>(ctx, (const double *)W, ldw, mf, words[1], tfac, dinv, l);
-  return geqp3_finish_t<float>(ctx, (const float *)W, ldw, mf, words[1], tfac, dinv, l);
+  return with_real(dtype, [&]<typename T>() { return geqp3_finish_t<T>(ctx, (const T *)W, ldw, mf, words[1], tfac, dinv, l); });
 }
 
 MXLO_API int32_t mxlo_qrp_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t mf, int64_t nf,
                               const double *tfac, const double *dinv, const int32_t *jpvt, int64_t rank, double *work, const void *v,
                               int32_t op_mode, double alpha, double beta) {
-  const char *what = "mxlo_qrp_mul";
-  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
-  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
-  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "%s: op_mode %d", what, op_mode);
-  MXLO_REQUIRE(nf >= 1 && mf >= nf && ldw >= mf && mf < (1LL << 31) - NB, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld (1 <= nf <= mf), ldw = %lld",
-               what, (long long)mf, (long long)nf, (long long)ldw);
-  MXLO_REQUIRE(rank >= 1 && rank <= nf, MXLO_ESHAPE, "%s: rank = %lld (1 <= rank <= nf = %lld)", what, (long long)rank, (long long)nf);
-  MXLO_REQUIRE(res && W && tfac && dinv && jpvt && work && v, MXLO_EINVAL, "%s: null operand", what);
-  const bool tr = op_mode != MXLO_OP_N;
-  const int64_t es = dtype == MXLO_F64 ? 8 : 4, nb = (nf + NB - 1) / NB;
-  const int64_t rb = (tr ? mf : nf) * es, vb = (tr ? nf : mf) * es;
-  MXLO_REQUIRE((res == v && mf == nf) || !bytes_overlap(res, rb, v, vb), MXLO_EINVAL,
-               "%s: res overlaps v without being v (only mul!(x, op, x) of a square operator is defined)", what);
-  const std::pair<const void *, int64_t> own[] = {{W, ((nf - 1) * ldw + mf) * es}, {tfac, nb * NB2 * 8}, {dinv, nb * NB2 * 8},
-                                                  {jpvt, nf * 4},                  {work, qr_work(mf) * 8}};
-  for (const auto &[p, pb] : own)
-    MXLO_REQUIRE(!bytes_overlap(res, rb, p, pb) && !bytes_overlap(v, vb, p, pb), MXLO_EINVAL,
-                 "%s: res / v overlap the factor, the T factors, the block inverses, the permutation or the work vector", what);
+  bool go;
+  MXLO_TRY(check_qr_apply(ctx, dtype, res, mf, W, ldw, mf, nf, tfac, dinv, true, jpvt, rank, work, false, v, mf, 1, op_mode, "mxlo_qrp_mul",
+                          go));
+  if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
-  if (dtype == MXLO_F64)
-    return qr_mul_t<double>(ctx, (double *)res, (const double *)W, ldw, mf, rank, tfac, dinv, work, (const double *)v, tr, alpha, beta, jpvt,
-                            nf);
-  return qr_mul_t<float>(ctx, (float *)res, (const float *)W, ldw, mf, rank, tfac, dinv, work, (const float *)v, tr, alpha, beta, jpvt, nf);
+  const bool tr = op_mode != MXLO_OP_N;
+  return with_real(dtype, [&]<typename T>() {
+    return qr_mul_t<T>(ctx, (T *)res, (const T *)W, ldw, mf, rank, tfac, dinv, work, (const T *)v, tr, alpha, beta, Group{}, jpvt, nf);
+  });
 }
 
 MXLO_API int32_t mxlo_qrp_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf,
                                     int64_t nf, const double *tfac, const double *dinv, const int32_t *jpvt, int64_t rank, double *work,
                                     const void *V, int64_t ldv, int64_t k, int32_t op_mode, double alpha, double beta) {
-  const char *what = "mxlo_qrp_mul_block";
-  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
-  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
-  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "%s: op_mode %d", what, op_mode);
-  MXLO_REQUIRE(nf >= 1 && mf >= nf && ldw >= mf && mf < (1LL << 31) - NB, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld (1 <= nf <= mf), ldw = %lld",
-               what, (long long)mf, (long long)nf, (long long)ldw);
-  MXLO_REQUIRE(rank >= 1 && rank <= nf, MXLO_ESHAPE, "%s: rank = %lld (1 <= rank <= nf = %lld)", what, (long long)rank, (long long)nf);
-  const bool tr = op_mode != MXLO_OP_N;
-  const int64_t rrows = tr ? mf : nf, vrows = tr ? nf : mf;
-  MXLO_REQUIRE(k >= 0 && ldr >= rrows && ldv >= vrows, MXLO_ESHAPE, "%s: k = %lld, ldr = %lld for %lld rows, ldv = %lld for %lld rows", what,
-               (long long)k, (long long)ldr, (long long)rrows, (long long)ldv, (long long)vrows);
-  if (k == 0) return MXLO_OK;
-  MXLO_REQUIRE(res && W && tfac && dinv && jpvt && work && V, MXLO_EINVAL, "%s: null operand", what);
-  const int64_t es = dtype == MXLO_F64 ? 8 : 4, nb = (nf + NB - 1) / NB;
-  const int64_t rb = ((k - 1) * ldr + rrows) * es, vb = ((k - 1) * ldv + vrows) * es;
-  MXLO_REQUIRE((res == V && ldr == ldv && mf == nf) || !bytes_overlap(res, rb, V, vb), MXLO_EINVAL,
-               "%s: res overlaps V without being V (only mul!(X, op, X) of a square operator, as the same matrix, is defined)", what);
-  const std::pair<const void *, int64_t> own[] = {{W, ((nf - 1) * ldw + mf) * es}, {tfac, nb * NB2 * 8}, {dinv, nb * NB2 * 8},
-                                                  {jpvt, nf * 4},                  {work, qr_block_work(mf, nf) * 8}};
-  for (const auto &[p, pb] : own)
-    MXLO_REQUIRE(!bytes_overlap(res, rb, p, pb) && !bytes_overlap(V, vb, p, pb), MXLO_EINVAL,
-                 "%s: res or V overlaps the factor, the T factors, the block inverses, the permutation or the work space", what);
+  bool go;
+  MXLO_TRY(check_qr_apply(ctx, dtype, res, ldr, W, ldw, mf, nf, tfac, dinv, true, jpvt, rank, work, true, V, ldv, k, op_mode,
+                          "mxlo_qrp_mul_block", go));
+  if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
-  if (dtype == MXLO_F64)
-    return for_groups((double *)res, ldr, (const double *)V, ldv, k, [&](double *r, const double *v, Group grp) {
-      return qr_mul_block_t<double>(ctx, r, (const double *)W, ldw, mf, rank, tfac, dinv, work, v, tr, alpha, beta, grp, jpvt, nf);
-    });
-  return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
-    return qr_mul_block_t<float>(ctx, r, (const float *)W, ldw, mf, rank, tfac, dinv, work, v, tr, alpha, beta, grp, jpvt, nf);
+  const bool tr = op_mode != MXLO_OP_N;
+  return for_real_groups(dtype, res, ldr, V, ldv, k, [&]<typename T>(T *r, const T *v, Group grp) {
+    return qr_mul_t<T>(ctx, r, (const T *)W, ldw, mf, rank, tfac, dinv, work, v, tr, alpha, beta, grp, jpvt, nf);
   });
 }
 
 MXLO_API int32_t mxlo_cod_factor(mxlo_ctx *ctx, int32_t dtype, const void *W, int64_t ldw, int64_t nf, int64_t rank, void *W2,
                                  double *tfac2, double *dinv2, double *scratch, int64_t scratch_len, int32_t *info_dev, int32_t *info) {
   const char *what = "mxlo_cod_factor";
-  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
-  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
-  MXLO_REQUIRE(nf >= 1 && ldw >= nf, MXLO_ESHAPE, "%s: nf = %lld (nf >= 1), ldw = %lld (ldw >= mf >= nf)", what, (long long)nf,
-               (long long)ldw);
-  MXLO_REQUIRE(nf < (1LL << 31) - NB && (nf + NB - 1) / NB <= 65535, MXLO_ESHAPE, "%s: nf = %lld is too large", what, (long long)nf);
+  MXLO_TRY(check_real(ctx, dtype, what));
+  MXLO_TRY(check_tall(nf, nf, ldw, true, what));         // of the factor's mf rows only the leading nf are read: ldw >= mf >= nf
   MXLO_REQUIRE(rank >= 1 && rank <= nf, MXLO_ESHAPE, "%s: rank = %lld (1 <= rank <= nf = %lld)", what, (long long)rank, (long long)nf);
   MXLO_REQUIRE(W && W2 && tfac2 && dinv2 && scratch && info_dev && info, MXLO_EINVAL, "%s: null operand", what);
   *info = 0;
-  MXLO_REQUIRE(scratch_len >= geqrf_scratch(rank), MXLO_ESHAPE, "%s: scratch of %lld doubles, %lld needed", what, (long long)scratch_len,
-               (long long)geqrf_scratch(rank));
-  const int64_t es = dtype == MXLO_F64 ? 8 : 4, nb = (rank + NB - 1) / NB;
-  const std::pair<const void *, int64_t> bufs[] = {{W, ((nf - 1) * ldw + rank) * es}, {W2, nf * rank * es},  {tfac2, nb * NB2 * 8},
-                                                   {dinv2, nb * NB2 * 8},             {scratch, scratch_len * 8}, {info_dev, 4}};
-  for (size_t x = 0; x < 6; ++x)
-    for (size_t y = x + 1; y < 6; ++y)
-      MXLO_REQUIRE(!bytes_overlap(bufs[x].first, bufs[x].second, bufs[y].first, bufs[y].second), MXLO_EINVAL,
-                   "%s: the factor, the second factor, its T factors, its block inverses, the scratch and the info word overlap", what);
-  MXLO_REQUIRE(!ctx->capturing, MXLO_ESTATE, "%s: reads its info word back, which a graph capture cannot hold", what);
+  MXLO_TRY(check_scratch(scratch_len, geqrf_scratch(rank), what));
+  const int64_t es = esize(dtype);
+  MXLO_TRY(disjoint({{W, mat_bytes(rank, nf, ldw, es), "the factor"}, {W2, nf * rank * es, "the second factor"},
+                     {tfac2, blocks_bytes(rank), "its T factors"}, {dinv2, blocks_bytes(rank), "its block inverses"},
+                     {scratch, scratch_len * 8, "the scratch"}, {info_dev, 4, "the info word"}},
+                    what));
+  MXLO_TRY(refuse_capture(ctx, what));
   MXLO_DEVICE_GUARD(ctx);
-  if (dtype == MXLO_F64)
-    MXLO_TRY(cod_factor_t<double>(ctx, (const double *)W, ldw, nf, rank, (double *)W2, tfac2, dinv2, scratch, info_dev));
-  else MXLO_TRY(cod_factor_t<float>(ctx, (const float *)W, ldw, nf, rank, (float *)W2, tfac2, dinv2, scratch, info_dev));
-  MXLO_HIP(hipMemcpyAsync(info, info_dev, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  MXLO_HIP(hipStreamSynchronize(ctx->stream));
-  return MXLO_OK;
+  MXLO_TRY(with_real(dtype, [&]<typename T>() {
+    return cod_factor_t<T>(ctx, (const T *)W, ldw, nf, rank, (T *)W2, tfac2, dinv2, scratch, info_dev);
+  }));
+  return read_back(ctx, info_dev, info, 1);
 }
-
-namespace {
-// the checks mxlo_pinv_mul and mxlo_pinv_mul_block share, mxlo_qrp_mul_block's with the second factor; a vector is k = 1
-int32_t check_pinv(mxlo_ctx *ctx, int32_t dtype, const void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf, int64_t nf,
-                   const double *tfac, const int32_t *jpvt, int64_t rank, const void *W2, const double *tfac2, const double *dinv2,
-                   const double *work, int64_t work_len, const void *V, int64_t ldv, int64_t k, int32_t op_mode, const char *what) {
-  MXLO_REQUIRE(ctx, MXLO_EINVAL, "%s: null ctx", what);
-  MXLO_REQUIRE(dtype == MXLO_F64 || dtype == MXLO_F32, MXLO_EINVAL, "%s: real Float64 / Float32 only", what);
-  MXLO_REQUIRE(op_mode == MXLO_OP_N || op_mode == MXLO_OP_T || op_mode == MXLO_OP_C, MXLO_EINVAL, "%s: op_mode %d", what, op_mode);
-  MXLO_REQUIRE(nf >= 1 && mf >= nf && ldw >= mf && mf < (1LL << 31) - NB, MXLO_ESHAPE, "%s: mf = %lld, nf = %lld (1 <= nf <= mf), ldw = %lld",
-               what, (long long)mf, (long long)nf, (long long)ldw);
-  MXLO_REQUIRE(rank >= 1 && rank < nf, MXLO_ESHAPE, "%s: rank = %lld (1 <= rank < nf = %lld; rank == nf is mxlo_qrp_mul's)", what,
-               (long long)rank, (long long)nf);
-  const bool tr = op_mode != MXLO_OP_N;
-  const int64_t rrows = tr ? mf : nf, vrows = tr ? nf : mf;
-  MXLO_REQUIRE(k >= 0 && ldr >= rrows && ldv >= vrows, MXLO_ESHAPE, "%s: k = %lld, ldr = %lld for %lld rows, ldv = %lld for %lld rows", what,
-               (long long)k, (long long)ldr, (long long)rrows, (long long)ldv, (long long)vrows);
-  if (k == 0) return MXLO_OK;
-  MXLO_REQUIRE(res && W && tfac && jpvt && W2 && tfac2 && dinv2 && work && V, MXLO_EINVAL, "%s: null operand", what);
-  const int64_t es = dtype == MXLO_F64 ? 8 : 4, nb = (rank + NB - 1) / NB;
-  const int64_t rb = ((k - 1) * ldr + rrows) * es, vb = ((k - 1) * ldv + vrows) * es;
-  MXLO_REQUIRE((res == V && ldr == ldv && mf == nf) || !bytes_overlap(res, rb, V, vb), MXLO_EINVAL,
-               "%s: res overlaps v without being v (only mul!(x, op, x) of a square operator, as the same matrix, is defined)", what);
-  const std::pair<const void *, int64_t> own[] = {{W, ((nf - 1) * ldw + mf) * es}, {tfac, nb * NB2 * 8},  {jpvt, nf * 4},    {W2, nf * rank * es},
-                                                  {tfac2, nb * NB2 * 8},           {dinv2, nb * NB2 * 8}, {work, work_len * 8}};
-  for (const auto &[p, pb] : own)
-    MXLO_REQUIRE(!bytes_overlap(res, rb, p, pb) && !bytes_overlap(V, vb, p, pb), MXLO_EINVAL,
-                 "%s: res / v overlap a factor, its T factors, the block inverses, the permutation or the work space", what);
-  return MXLO_OK;
-}
-}  // namespace
 
 MXLO_API int32_t mxlo_pinv_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t mf, int64_t nf,
                                const double *tfac, const int32_t *jpvt, int64_t rank, const void *W2, const double *tfac2,
                                const double *dinv2, double *work, const void *v, int32_t op_mode, double alpha, double beta) {
-  const int64_t ldmax = mf > 1 ? mf : 1;                 // one column: any leading dimension >= its rows
-  MXLO_TRY(check_pinv(ctx, dtype, res, ldmax, W, ldw, mf, nf, tfac, jpvt, rank, W2, tfac2, dinv2, work, mf >= 0 ? qr_work(mf) : 0, v, ldmax,
-                      1, op_mode, "mxlo_pinv_mul"));
+  bool go;
+  MXLO_TRY(check_pinv(ctx, dtype, res, mf, W, ldw, mf, nf, tfac, jpvt, rank, W2, tfac2, dinv2, work, false, v, mf, 1, op_mode,
+                      "mxlo_pinv_mul", go));
+  if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
   const bool tr = op_mode != MXLO_OP_N;
-  if (dtype == MXLO_F64)
-    return pinv_mul_t<double>(ctx, (double *)res, (const double *)W, ldw, mf, nf, tfac, jpvt, rank, (const double *)W2, tfac2, dinv2, work,
-                              (const double *)v, tr, alpha, beta);
-  return pinv_mul_t<float>(ctx, (float *)res, (const float *)W, ldw, mf, nf, tfac, jpvt, rank, (const float *)W2, tfac2, dinv2, work,
-                           (const float *)v, tr, alpha, beta);
+  return with_real(dtype, [&]<typename T>() {
+    return pinv_mul_t<T>(ctx, (T *)res, (const T *)W, ldw, mf, nf, tfac, jpvt, rank, (const T *)W2, tfac2, dinv2, work, (const T *)v, tr, alpha,
+                         beta);
+  });
 }
 
 MXLO_API int32_t mxlo_pinv_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf,
                                      int64_t nf, const double *tfac, const int32_t *jpvt, int64_t rank, const void *W2,
                                      const double *tfac2, const double *dinv2, double *work, const void *V, int64_t ldv, int64_t k,
                                      int32_t op_mode, double alpha, double beta) {
-  MXLO_TRY(check_pinv(ctx, dtype, res, ldr, W, ldw, mf, nf, tfac, jpvt, rank, W2, tfac2, dinv2, work,
-                      (mf >= 0 && nf >= 0) ? qr_block_work(mf, nf) : 0, V, ldv, k, op_mode, "mxlo_pinv_mul_block"));
-  if (k == 0) return MXLO_OK;
+  bool go;
+  MXLO_TRY(check_pinv(ctx, dtype, res, ldr, W, ldw, mf, nf, tfac, jpvt, rank, W2, tfac2, dinv2, work, true, V, ldv, k, op_mode,
+                      "mxlo_pinv_mul_block", go));
+  if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
   const bool tr = op_mode != MXLO_OP_N;
-  if (dtype == MXLO_F64)
-    return for_groups((double *)res, ldr, (const double *)V, ldv, k, [&](double *r, const double *v, Group grp) {
-      return pinv_mul_t<double>(ctx, r, (const double *)W, ldw, mf, nf, tfac, jpvt, rank, (const double *)W2, tfac2, dinv2, work, v, tr,
-                                alpha, beta, grp);
-    });
-  return for_groups((float *)res, ldr, (const float *)V, ldv, k, [&](float *r, const float *v, Group grp) {
-    return pinv_mul_t<float>(ctx, r, (const float *)W, ldw, mf, nf, tfac, jpvt, rank, (const float *)W2, tfac2, dinv2, work, v, tr, alpha,
-                             beta, grp);
+  return for_real_groups(dtype, res, ldr, V, ldv, k, [&]<typename T>(T *r, const T *v, Group grp) {
+    return pinv_mul_t<T>(ctx, r, (const T *)W, ldw, mf, nf, tfac, jpvt, rank, (const T *)W2, tfac2, dinv2, work, v, tr, alpha, beta, grp);
   });
 }

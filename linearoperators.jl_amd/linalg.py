@@ -140,6 +140,78 @@ _REFINE_DOC = """
     may not improve and nothing reports it. The exceptions of the factorisation are raised as before."""
 
 
+def _two_mode(T, nrows, ncols, symm, herm, solve, block, fwd, bwd, device):
+    """The operator whose applies take an op_mode: prod! is `solve` / `block` (the matrix form) in mode fwd, tprod! = ctprod!
+    in mode bwd."""
+    prod = columnwise(lambda res, v, a, b: solve(res, v, a, b, fwd))       # mulFact!(res, F, v, α, β) — src/linalg.jl:3-9
+    tprod = columnwise(lambda res, u, a, b: solve(res, u, a, b, bwd))      # mulFact!(res, transpose(F), u, α, β)
+    prod._matrix = lambda res, m, a, b: block(res, m, a, b, fwd)
+    tprod._matrix = lambda res, m, a, b: block(res, m, a, b, bwd)
+    return LinearOperator(T, nrows, ncols, bool(symm), bool(herm), prod, tprod, tprod, S=Storage(T, device))
+
+
+def _symmetric(name, stem, factor, pivots, exception, M, check, refine):
+    """opCholesky (`mxlo_potrf`, the `mxlo_chol_mul*` applies) and opLDL (`mxlo_ldlt`, `mxlo_ldl_mul*`, with the pivots d
+    after the block inverses in every call): the checks in the reference's order, the storage, the factorisation, whose
+    info != 0 raises `exception`, and the closures."""
+    refine = _check_refine(refine, name)
+    n = _check_matrix(M, name)
+    T = M.dtype
+    if check:
+        from .utilities import check_hermitian, check_positive_definite
+        if not check_hermitian(M):
+            raise LinearOperatorException("matrix is not Hermitian")
+        if not pivots and not check_positive_definite(M):              # opLDL has no definiteness check
+            raise LinearOperatorException("matrix is not positive definite")
+    St, tr = _stored_colmajor(M)                       # tr: St is the column-major storage of Mᵀ, i.e. M is row-major
+    ldm = max(1, St.stride(1)) if n > 1 else 1
+    ctx = get_ctx(M.device)
+    W = torch.zeros((n, n), dtype=T, device=M.device).t()            # column-major, ld = n; the lower triangle is L (opLDL: L D)
+    ldw = max(1, n)
+    nblk = (n + BLOCK - 1) // BLOCK
+    dinv = torch.empty(max(1, nblk) * BLOCK * BLOCK, dtype=torch.float64, device=M.device)
+    d = torch.empty(n, dtype=torch.float64, device=M.device) if pivots else None
+    work = _work(n, M.device, refine)
+    info_dev = torch.zeros(1, dtype=torch.int32, device=M.device)
+    info = C.c_int32(0)
+    code = dtype_code(T)
+    piv = (d.data_ptr(),) if pivots else ()
+    _lib.call(factor, ctx.handle, code, St.data_ptr(), ldm, 1 if tr else 0, W.data_ptr(), ldw, n, dinv.data_ptr(), *piv,
+              info_dev.data_ptr(), C.byref(info))
+    if info.value != 0:
+        raise exception(info.value)
+    pW, pZ = W.data_ptr(), work.data_ptr()
+    head = (pW, ldw, n, dinv.data_ptr()) + piv
+    mul, mul_block, mul_refine = f"mxlo_{stem}_mul", f"mxlo_{stem}_mul_block", f"mxlo_{stem}_mul_refine"
+    if refine:                                          # the snapshot: after the chain, which leaves the strict upper triangle alone
+        dg = torch.empty(max(1, n), dtype=T, device=M.device)
+        _lib.call("mxlo_sym_snapshot", ctx.handle, code, St.data_ptr(), ldm, 1 if tr else 0, pW, ldw, n, dg.data_ptr())
+        pG = dg.data_ptr()
+
+    def prod(res, v, a, b):                             # mulFact!(res, F, v, α, β) — src/linalg.jl:3-9
+        _check_operands(res, v, T)
+        _lib.call(mul, ctx_of(res).handle, code, res.data_ptr(), *head, pZ, v.data_ptr(), float(a), float(b))
+
+    def block(res, m, a, b):                            # `F \ V`: one chain of launches and one read of L per 8 columns
+        ldr, ldv, k = _check_block_operands(res, m, T, n)
+        _lib.call(mul_block, ctx_of(res).handle, code, res.data_ptr(), ldr, *head, pZ, m.data_ptr(), ldv, k, float(a), float(b))
+
+    if refine:
+        rprod, rblock = _refined(lambda res, ldr, V, ldv, k, a, b: _lib.call(
+            mul_refine, ctx_of(res).handle, code, res.data_ptr(), ldr, *head, pG, pZ, V.data_ptr(), ldv, k, refine, float(a), float(b)))
+        prod = lambda res, v, a, b: rprod(res, v, a, b, T, n)                   # noqa: E731
+        block = lambda res, m, a, b: rblock(res, m, a, b, T, n)                 # noqa: E731
+    columnwise(prod)                                    # `F \ V` takes matrices: k == 1 column by column, else the block form
+    prod._matrix = block
+    op = LinearOperator(T, n, n, True, True, prod, prod, prod, S=Storage(T, M.device))      # isreal(M), hermitian = true
+    op._deps = (W,)
+    if pivots:
+        op._d = d                                       # the pivots; their signs are the inertia of M
+    op._factor = (W, dinv) + ((d,) if pivots else ()) + (work,) + ((dg,) if refine else ())   # owned storage (kept alive with the operator)
+    op._refine = refine
+    return op
+
+
 def opCholesky(M: torch.Tensor, check: bool = False, refine: int = 0):
 
 
@@ -156,58 +228,7 @@ def opCholesky(M: torch.Tensor, check: bool = False, refine: int = 0):
     With refine > 0 the operator keeps a snapshot of M, taken here: its strict upper triangle in the unused strict upper
     triangle of the factor's storage, its diagonal in n further elements — no second n x n buffer; the work space is 2 n x 8
     doubles. A later change of M is not seen, as before."""
-    refine = _check_refine(refine, "opCholesky")
-    n = _check_matrix(M, "opCholesky")
-    T = M.dtype
-    if check:
-        from .utilities import check_hermitian, check_positive_definite
-        if not check_hermitian(M):
-            raise LinearOperatorException("matrix is not Hermitian")
-        if not check_positive_definite(M):
-            raise LinearOperatorException("matrix is not positive definite")
-    St, tr = _stored_colmajor(M)                       # tr: St is the column-major storage of Mᵀ, i.e. M is row-major
-    ldm = max(1, St.stride(1)) if n > 1 else 1
-    ctx = get_ctx(M.device)
-    W = torch.zeros((n, n), dtype=T, device=M.device).t()            # column-major, ld = n; the lower triangle is L
-    ldw = max(1, n)
-    nblk = (n + BLOCK - 1) // BLOCK
-    dinv = torch.empty(max(1, nblk) * BLOCK * BLOCK, dtype=torch.float64, device=M.device)
-    work = _work(n, M.device, refine)
-    info_dev = torch.zeros(1, dtype=torch.int32, device=M.device)
-    info = C.c_int32(0)
-    code = dtype_code(T)
-    _lib.call("mxlo_potrf", ctx.handle, code, St.data_ptr(), ldm, 1 if tr else 0, W.data_ptr(), ldw, n, dinv.data_ptr(),
-              info_dev.data_ptr(), C.byref(info))
-    if info.value != 0:
-        raise PosDefException(info.value)
-    pW, pD, pZ = W.data_ptr(), dinv.data_ptr(), work.data_ptr()
-    if refine:                                          # the snapshot: after the chain, which leaves the strict upper triangle alone
-        dg = torch.empty(max(1, n), dtype=T, device=M.device)
-        _lib.call("mxlo_sym_snapshot", ctx.handle, code, St.data_ptr(), ldm, 1 if tr else 0, pW, ldw, n, dg.data_ptr())
-        pG = dg.data_ptr()
-
-    def prod(res, v, a, b):                             # mulFact!(res, LL, v, α, β) — src/linalg.jl:3-9
-        _check_operands(res, v, T)
-        _lib.call("mxlo_chol_mul", ctx_of(res).handle, code, res.data_ptr(), pW, ldw, n, pD, pZ, v.data_ptr(), float(a), float(b))
-
-    def block(res, m, a, b):                            # `F \ V`: one chain of launches and one read of L per 8 columns
-        ldr, ldv, k = _check_block_operands(res, m, T, n)
-        _lib.call("mxlo_chol_mul_block", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, n, pD, pZ, m.data_ptr(), ldv, k,
-                  float(a), float(b))
-
-    if refine:
-        rprod, rblock = _refined(lambda res, ldr, V, ldv, k, a, b: _lib.call(
-            "mxlo_chol_mul_refine", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, n, pD, pG, pZ, V.data_ptr(), ldv, k, refine,
-            float(a), float(b)))
-        prod = lambda res, v, a, b: rprod(res, v, a, b, T, n)                   # noqa: E731
-        block = lambda res, m, a, b: rblock(res, m, a, b, T, n)                 # noqa: E731
-    columnwise(prod)                                    # `F \ V` takes matrices: k == 1 column by column, else the block form
-    prod._matrix = block
-    op = LinearOperator(T, n, n, True, True, prod, prod, prod, S=Storage(T, M.device))      # isreal(M), hermitian = true
-    op._deps = (W,)
-    op._factor = (W, dinv, work) + ((dg,) if refine else ())     # owned storage (kept alive with the operator)
-    op._refine = refine
-    return op
+    return _symmetric("opCholesky", "chol", "mxlo_potrf", False, PosDefException, M, check, refine)
 
 
 opCholesky.__doc__ += _REFINE_DOC
@@ -235,58 +256,7 @@ def opLDL(M: torch.Tensor, check: bool = False, refine: int = 0):
     backward error from ρ·eps (ρ the growth of |L||D||Lᵀ|) back to the order of n·eps as long as ρ·cond·eps < 1. The
     operator then keeps a snapshot of M, taken here: its strict upper triangle in the unused strict upper triangle of the
     factor's storage, its diagonal in n further elements — no second n x n buffer; the work space is 2 n x 8 doubles."""
-    refine = _check_refine(refine, "opLDL")
-    n = _check_matrix(M, "opLDL")
-    T = M.dtype
-    if check:
-        from .utilities import check_hermitian
-        if not check_hermitian(M):
-            raise LinearOperatorException("matrix is not Hermitian")
-    St, tr = _stored_colmajor(M)
-    ldm = max(1, St.stride(1)) if n > 1 else 1
-    ctx = get_ctx(M.device)
-    W = torch.zeros((n, n), dtype=T, device=M.device).t()            # column-major, ld = n; the lower triangle is L D
-    ldw = max(1, n)
-    nblk = (n + BLOCK - 1) // BLOCK
-    dinv = torch.empty(max(1, nblk) * BLOCK * BLOCK, dtype=torch.float64, device=M.device)
-    d = torch.empty(n, dtype=torch.float64, device=M.device)
-    work = _work(n, M.device, refine)
-    info_dev = torch.zeros(1, dtype=torch.int32, device=M.device)
-    info = C.c_int32(0)
-    code = dtype_code(T)
-    _lib.call("mxlo_ldlt", ctx.handle, code, St.data_ptr(), ldm, 1 if tr else 0, W.data_ptr(), ldw, n, dinv.data_ptr(),
-              d.data_ptr(), info_dev.data_ptr(), C.byref(info))
-    if info.value != 0:
-        raise ZeroPivotException(info.value)
-    pW, pD, pd, pZ = W.data_ptr(), dinv.data_ptr(), d.data_ptr(), work.data_ptr()
-    if refine:
-        dg = torch.empty(max(1, n), dtype=T, device=M.device)
-        _lib.call("mxlo_sym_snapshot", ctx.handle, code, St.data_ptr(), ldm, 1 if tr else 0, pW, ldw, n, dg.data_ptr())
-        pG = dg.data_ptr()
-
-    def prod(res, v, a, b):                             # mulFact!(res, LDL, v, α, β) — src/linalg.jl:3-9
-        _check_operands(res, v, T)
-        _lib.call("mxlo_ldl_mul", ctx_of(res).handle, code, res.data_ptr(), pW, ldw, n, pD, pd, pZ, v.data_ptr(), float(a), float(b))
-
-    def block(res, m, a, b):
-        ldr, ldv, k = _check_block_operands(res, m, T, n)
-        _lib.call("mxlo_ldl_mul_block", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, n, pD, pd, pZ, m.data_ptr(), ldv, k,
-                  float(a), float(b))
-
-    if refine:
-        rprod, rblock = _refined(lambda res, ldr, V, ldv, k, a, b: _lib.call(
-            "mxlo_ldl_mul_refine", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, n, pD, pd, pG, pZ, V.data_ptr(), ldv, k,
-            refine, float(a), float(b)))
-        prod = lambda res, v, a, b: rprod(res, v, a, b, T, n)                   # noqa: E731
-        block = lambda res, m, a, b: rblock(res, m, a, b, T, n)                 # noqa: E731
-    columnwise(prod)
-    prod._matrix = block
-    op = LinearOperator(T, n, n, True, True, prod, prod, prod, S=Storage(T, M.device))      # isreal(M), hermitian = true
-    op._deps = (W,)
-    op._d = d                                           # the pivots; their signs are the inertia of M
-    op._factor = (W, dinv, d, work) + ((dg,) if refine else ())
-    op._refine = refine
-    return op
+    return _symmetric("opLDL", "ldl", "mxlo_ldlt", True, ZeroPivotException, M, check, refine)
 
 
 opLDL.__doc__ += _REFINE_DOC
@@ -343,11 +313,7 @@ def opInverse(M: torch.Tensor, symm: bool = False, herm: bool = False):
                   m.data_ptr(), ldv, k, float(a), float(b))
 
     fwd, bwd = (_lib.OP_T, _lib.OP_N) if tr else (_lib.OP_N, _lib.OP_T)
-    prod = columnwise(lambda res, v, a, b: solve(res, v, a, b, fwd))       # mulFact!(res, M, v, α, β)
-    tprod = columnwise(lambda res, u, a, b: solve(res, u, a, b, bwd))      # mulFact!(res, transpose(M), u, α, β)
-    prod._matrix = lambda res, m, a, b: block(res, m, a, b, fwd)
-    tprod._matrix = lambda res, m, a, b: block(res, m, a, b, bwd)
-    op = LinearOperator(T, n, n, bool(symm), bool(herm), prod, tprod, tprod, S=Storage(T, M.device))
+    op = _two_mode(T, n, n, symm, herm, solve, block, fwd, bwd, M.device)
     op._deps = (M,)
     op._triangle = "lower" if (bits == 0 or st_upper == tr) else "upper"   # of M itself
     op._factor = (St, dinv, work)
@@ -420,11 +386,7 @@ def opLU(M: torch.Tensor, symm: bool = False, herm: bool = False, refine: int = 
         solve = lambda res, v, a, b, mode: rs[mode][0](res, v, a, b, T, n)      # noqa: E731
         block = lambda res, m, a, b, mode: rs[mode][1](res, m, a, b, T, n)      # noqa: E731
     fwd, bwd = (_lib.OP_T, _lib.OP_N) if tr else (_lib.OP_N, _lib.OP_T)
-    prod = columnwise(lambda res, v, a, b: solve(res, v, a, b, fwd))
-    tprod = columnwise(lambda res, u, a, b: solve(res, u, a, b, bwd))
-    prod._matrix = lambda res, m, a, b: block(res, m, a, b, fwd)
-    tprod._matrix = lambda res, m, a, b: block(res, m, a, b, bwd)
-    op = LinearOperator(T, n, n, bool(symm), bool(herm), prod, tprod, tprod, S=Storage(T, M.device))
+    op = _two_mode(T, n, n, symm, herm, solve, block, fwd, bwd, M.device)
     op._deps = (W,)
     op._perm = pbuf[:n]
     op._factor = (W, dinv_l, dinv_u, pbuf, work) + ((A2,) if refine else ())    # owned storage (kept alive with the operator)
@@ -436,6 +398,57 @@ opLU.__doc__ += _REFINE_DOC
 
 
 QR_SLOTS = 512        # most workgroups of a pass over the rows (QG of csrc/linalg.hip): partial slots per column
+QRP_SLOTS = 64        # most row groups of a step of the pivoted factorisation (QPG of csrc/linalg.hip)
+
+
+def geqrf_scratch(nf: int) -> int:
+    """Doubles of the scratch of `mxlo_geqrf` (and of `mxlo_cod_factor`, with nf := rank): geqrf_scratch() of csrc/linalg.hip."""
+    return 2 * (QR_SLOTS * BLOCK + BLOCK) + (QR_SLOTS + 2 * ((nf + BLOCK - 1) // BLOCK)) * BLOCK * BLOCK
+
+
+def geqp3_scratch(mf: int, nf: int) -> int:
+    """Doubles of the scratch of `mxlo_geqp3`: geqp3_scratch() of csrc/linalg.hip."""
+    return 2 * QRP_SLOTS * nf + QRP_SLOTS + 2 * nf + 2 * mf + 2 + QRP_SLOTS * BLOCK * BLOCK
+
+
+def qr_block_work(mf: int, nf: int) -> int:
+    """Doubles of the work space of the rectangular applies — the block apply's: z (mf x GROUP), two sets of partial slots per
+    column, the sweep's nf x GROUP; the vector apply uses a prefix: qr_block_work() of csrc/linalg.hip."""
+    return GROUP * (mf + nf + 2 * QR_SLOTS * BLOCK)
+
+
+def _rect_storage(T, rows, cols, device, zero_dinv=False, work=True, info_words=1):
+    """What a factorisation of the rectangular family fills and its operator owns: W (rows x cols column-major, ld = rows), the
+    T factors (zero where no block column writes them), the block inverses of R, the applies' work space, the info words."""
+    nblk = (cols + BLOCK - 1) // BLOCK
+    W = torch.empty((cols, rows), dtype=T, device=device).t()
+    tfac = torch.zeros(nblk * BLOCK * BLOCK, dtype=torch.float64, device=device)
+    dinv = (torch.zeros if zero_dinv else torch.empty)(nblk * BLOCK * BLOCK, dtype=torch.float64, device=device)
+    wk = torch.empty(qr_block_work(rows, cols), dtype=torch.float64, device=device) if work else None
+    info_dev = torch.zeros(info_words, dtype=torch.int32, device=device)
+    return W, tfac, dinv, wk, info_dev
+
+
+def _rect_operator(T, m, k, tall, mf, nf, vec_name, block_name, W, mid, work):
+    """The k x m operator of a factored tall orientation F (mf x nf; W with ld = mf): `vec_name` and `block_name` are its
+    entry points, `mid` the arguments between `ldw, mf, nf` and the work pointer."""
+    code = dtype_code(T)
+    head = (W.data_ptr(), mf, mf, nf) + tuple(mid) + (work.data_ptr(),)
+
+    def solve(res, v, a, b, mode):                      # mulFact!(res, qr(F), v, α, β) — src/linalg.jl:3-9
+        _check_operands(res, v, T)
+        _lib.call(vec_name, ctx_of(res).handle, code, res.data_ptr(), *head, v.data_ptr(), mode, float(a), float(b))
+
+    def block(res, V, a, b, mode):
+        nv, nres = (mf, nf) if mode == _lib.OP_N else (nf, mf)
+        ldr, ldv, cols = _check_block_operands(res, V, T, nv, nres)
+        _lib.call(block_name, ctx_of(res).handle, code, res.data_ptr(), ldr, *head, V.data_ptr(), ldv, cols, mode, float(a), float(b))
+
+    fwd, bwd = (_lib.OP_N, _lib.OP_T) if tall else (_lib.OP_T, _lib.OP_N)
+    op = _two_mode(T, k, m, False, False, solve, block, fwd, bwd, W.device)
+    op._deps = (W,)
+    op._tall = tall
+    return op
 
 
 def qr_launches(nf: int) -> int:
@@ -490,9 +503,6 @@ def _check_pivot(pivot, rtol, name: str):
     return float(rtol)
 
 
-QRP_SLOTS = 64        # most row groups of a step of the pivoted factorisation (QPG of csrc/linalg.hip)
-
-
 def _qr_pivoted(A, m, k, rtol):
     """opQR(A, pivot=True) once the checks have passed; the storage is opQR's, with the permutation"""
     T = A.dtype
@@ -504,48 +514,22 @@ def _qr_pivoted(A, m, k, rtol):
     m_trans = tall == tr
     ldm = St.stride(1) if St.shape[1] > 1 else max(1, St.shape[0])
     ctx = get_ctx(A.device)
-    W = torch.empty((nf, mf), dtype=T, device=A.device).t()           # column-major mf x nf, ld = mf
-    ldw = mf
-    nblk = (nf + BLOCK - 1) // BLOCK
-    tfac = torch.zeros(nblk * BLOCK * BLOCK, dtype=torch.float64, device=A.device)
-    dinv = torch.zeros(nblk * BLOCK * BLOCK, dtype=torch.float64, device=A.device)
+    W, tfac, dinv, work, info_dev = _rect_storage(T, mf, nf, A.device, zero_dinv=True, info_words=2)
     perm = torch.empty(nf, dtype=torch.int32, device=A.device)
-    work = torch.empty(GROUP * (mf + nf + 2 * QR_SLOTS * BLOCK), dtype=torch.float64, device=A.device)
-    nscratch = 2 * QRP_SLOTS * nf + QRP_SLOTS + 2 * nf + 2 * mf + 2 + QRP_SLOTS * BLOCK * BLOCK
+    nscratch = geqp3_scratch(mf, nf)
     scratch = torch.empty(nscratch, dtype=torch.float64, device=A.device)                   # needed by the factorisation only
-    info_dev = torch.zeros(2, dtype=torch.int32, device=A.device)
     info, rank = C.c_int32(0), C.c_int32(0)
-    code = dtype_code(T)
-    _lib.call("mxlo_geqp3", ctx.handle, code, St.data_ptr(), ldm, 1 if m_trans else 0, W.data_ptr(), ldw, mf, nf, tfac.data_ptr(),
-              dinv.data_ptr(), perm.data_ptr(), rtol, scratch.data_ptr(), nscratch, info_dev.data_ptr(), C.byref(info),
-              C.byref(rank))
+    _lib.call("mxlo_geqp3", ctx.handle, dtype_code(T), St.data_ptr(), ldm, 1 if m_trans else 0, W.data_ptr(), mf, mf, nf,
+              tfac.data_ptr(), dinv.data_ptr(), perm.data_ptr(), rtol, scratch.data_ptr(), nscratch, info_dev.data_ptr(),
+              C.byref(info), C.byref(rank))
     if info.value != 0:
         raise SingularException(info.value)
     r = int(rank.value)
     # the T factors and the block inverses are made after the read-back, out of the scratch, on the stream the scratch was
     # allocated on: the allocator hands its memory only to work that this stream runs later
     del scratch
-    pW, pT, pD, pP, pZ = W.data_ptr(), tfac.data_ptr(), dinv.data_ptr(), perm.data_ptr(), work.data_ptr()
-
-    def solve(res, v, a, b, mode):                      # mulFact!(res, qr(F, ColumnNorm()), v, α, β) — src/linalg.jl:3-9
-        _check_operands(res, v, T)
-        _lib.call("mxlo_qrp_mul", ctx_of(res).handle, code, res.data_ptr(), pW, ldw, mf, nf, pT, pD, pP, r, pZ, v.data_ptr(), mode,
-                  float(a), float(b))
-
-    def block(res, V, a, b, mode):
-        nv, nres = (mf, nf) if mode == _lib.OP_N else (nf, mf)
-        ldr, ldv, cols = _check_block_operands(res, V, T, nv, nres)
-        _lib.call("mxlo_qrp_mul_block", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, mf, nf, pT, pD, pP, r, pZ, V.data_ptr(),
-                  ldv, cols, mode, float(a), float(b))
-
-    fwd, bwd = (_lib.OP_N, _lib.OP_T) if tall else (_lib.OP_T, _lib.OP_N)
-    prod = columnwise(lambda res, v, a, b: solve(res, v, a, b, fwd))
-    tprod = columnwise(lambda res, u, a, b: solve(res, u, a, b, bwd))
-    prod._matrix = lambda res, V, a, b: block(res, V, a, b, fwd)
-    tprod._matrix = lambda res, V, a, b: block(res, V, a, b, bwd)
-    op = LinearOperator(T, k, m, False, False, prod, tprod, tprod, S=Storage(T, A.device))
-    op._deps = (W,)
-    op._tall = tall
+    op = _rect_operator(T, m, k, tall, mf, nf, "mxlo_qrp_mul", "mxlo_qrp_mul_block", W,
+                        (tfac.data_ptr(), dinv.data_ptr(), perm.data_ptr(), r), work)
     op._rank = r
     op._perm = perm
     op._rtol = rtol
@@ -608,44 +592,16 @@ def opQR(A: torch.Tensor, pivot: bool = False, rtol=None):
     m_trans = tall == tr                                # St holds Fᵀ: transpose while copying
     ldm = St.stride(1) if St.shape[1] > 1 else max(1, St.shape[0])
     ctx = get_ctx(A.device)
-    W = torch.empty((nf, mf), dtype=T, device=A.device).t()           # column-major mf x nf, ld = mf
-    ldw = mf
-    nblk = (nf + BLOCK - 1) // BLOCK
-    tfac = torch.zeros(nblk * BLOCK * BLOCK, dtype=torch.float64, device=A.device)
-    dinv = torch.empty(nblk * BLOCK * BLOCK, dtype=torch.float64, device=A.device)
-    # the block apply's: z (mf x GROUP), two sets of partial slots per column, the sweep's nf x GROUP; the vector apply uses a prefix
-    work = torch.empty(GROUP * (mf + nf + 2 * QR_SLOTS * BLOCK), dtype=torch.float64, device=A.device)
-    nscratch = 2 * (QR_SLOTS * BLOCK + BLOCK) + (512 + 2 * nblk) * BLOCK * BLOCK
+    W, tfac, dinv, work, info_dev = _rect_storage(T, mf, nf, A.device)
+    nscratch = geqrf_scratch(nf)
     scratch = torch.empty(nscratch, dtype=torch.float64, device=A.device)                   # needed by the factorisation only
-    info_dev = torch.zeros(1, dtype=torch.int32, device=A.device)
     info = C.c_int32(0)
-    code = dtype_code(T)
-    _lib.call("mxlo_geqrf", ctx.handle, code, St.data_ptr(), ldm, 1 if m_trans else 0, W.data_ptr(), ldw, mf, nf, tfac.data_ptr(),
-              dinv.data_ptr(), scratch.data_ptr(), nscratch, info_dev.data_ptr(), C.byref(info))
+    _lib.call("mxlo_geqrf", ctx.handle, dtype_code(T), St.data_ptr(), ldm, 1 if m_trans else 0, W.data_ptr(), mf, mf, nf,
+              tfac.data_ptr(), dinv.data_ptr(), scratch.data_ptr(), nscratch, info_dev.data_ptr(), C.byref(info))
     del scratch
     if info.value != 0:
         raise SingularException(info.value)
-    pW, pT, pD, pZ = W.data_ptr(), tfac.data_ptr(), dinv.data_ptr(), work.data_ptr()
-
-    def solve(res, v, a, b, mode):                      # mulFact!(res, qr(F), v, α, β) — src/linalg.jl:3-9
-        _check_operands(res, v, T)
-        _lib.call("mxlo_qr_mul", ctx_of(res).handle, code, res.data_ptr(), pW, ldw, mf, nf, pT, pD, pZ, v.data_ptr(), mode, float(a),
-                  float(b))
-
-    def block(res, V, a, b, mode):
-        nv, nres = (mf, nf) if mode == _lib.OP_N else (nf, mf)
-        ldr, ldv, cols = _check_block_operands(res, V, T, nv, nres)
-        _lib.call("mxlo_qr_mul_block", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, mf, nf, pT, pD, pZ, V.data_ptr(), ldv,
-                  cols, mode, float(a), float(b))
-
-    fwd, bwd = (_lib.OP_N, _lib.OP_T) if tall else (_lib.OP_T, _lib.OP_N)
-    prod = columnwise(lambda res, v, a, b: solve(res, v, a, b, fwd))
-    tprod = columnwise(lambda res, u, a, b: solve(res, u, a, b, bwd))
-    prod._matrix = lambda res, V, a, b: block(res, V, a, b, fwd)
-    tprod._matrix = lambda res, V, a, b: block(res, V, a, b, bwd)
-    op = LinearOperator(T, k, m, False, False, prod, tprod, tprod, S=Storage(T, A.device))
-    op._deps = (W,)
-    op._tall = tall
+    op = _rect_operator(T, m, k, tall, mf, nf, "mxlo_qr_mul", "mxlo_qr_mul_block", W, (tfac.data_ptr(), dinv.data_ptr()), work)
     op._factor = (W, tfac, dinv, work)                  # owned storage (kept alive with the operator)
     return op
 
@@ -697,44 +653,18 @@ def opPinv(A: torch.Tensor, rtol=None):
     if r == nf:
         return op
     W, tfac, dinv, work, perm = op._factor
-    ldw = mf
     ctx = get_ctx(A.device)
-    nblk = (r + BLOCK - 1) // BLOCK
-    W2 = torch.empty((r, nf), dtype=T, device=A.device).t()            # column-major nf x r, ld = nf
-    tfac2 = torch.zeros(nblk * BLOCK * BLOCK, dtype=torch.float64, device=A.device)
-    dinv2 = torch.empty(nblk * BLOCK * BLOCK, dtype=torch.float64, device=A.device)
-    nscratch = 2 * (QR_SLOTS * BLOCK + BLOCK) + (512 + 2 * nblk) * BLOCK * BLOCK
+    W2, tfac2, dinv2, _, info_dev = _rect_storage(T, nf, r, A.device, work=False)           # column-major nf x r, ld = nf
+    nscratch = geqrf_scratch(r)
     scratch = torch.empty(nscratch, dtype=torch.float64, device=A.device)                   # needed by the factorisation only
-    info_dev = torch.zeros(1, dtype=torch.int32, device=A.device)
     info = C.c_int32(0)
-    code = dtype_code(T)
-    _lib.call("mxlo_cod_factor", ctx.handle, code, W.data_ptr(), ldw, nf, r, W2.data_ptr(), tfac2.data_ptr(), dinv2.data_ptr(),
+    _lib.call("mxlo_cod_factor", ctx.handle, dtype_code(T), W.data_ptr(), mf, nf, r, W2.data_ptr(), tfac2.data_ptr(), dinv2.data_ptr(),
               scratch.data_ptr(), nscratch, info_dev.data_ptr(), C.byref(info))
     del scratch
     if info.value != 0:
         raise SingularException(info.value)
-    pW, pT, pP, pZ = W.data_ptr(), tfac.data_ptr(), perm.data_ptr(), work.data_ptr()
-    pW2, pT2, pD2 = W2.data_ptr(), tfac2.data_ptr(), dinv2.data_ptr()
-
-    def solve(res, v, a, b, mode):
-        _check_operands(res, v, T)
-        _lib.call("mxlo_pinv_mul", ctx_of(res).handle, code, res.data_ptr(), pW, ldw, mf, nf, pT, pP, r, pW2, pT2, pD2, pZ,
-                  v.data_ptr(), mode, float(a), float(b))
-
-    def block(res, V, a, b, mode):
-        nv, nres = (mf, nf) if mode == _lib.OP_N else (nf, mf)
-        ldr, ldv, cols = _check_block_operands(res, V, T, nv, nres)
-        _lib.call("mxlo_pinv_mul_block", ctx_of(res).handle, code, res.data_ptr(), ldr, pW, ldw, mf, nf, pT, pP, r, pW2, pT2, pD2, pZ,
-                  V.data_ptr(), ldv, cols, mode, float(a), float(b))
-
-    fwd, bwd = (_lib.OP_N, _lib.OP_T) if tall else (_lib.OP_T, _lib.OP_N)
-    prod = columnwise(lambda res, v, a, b: solve(res, v, a, b, fwd))
-    tprod = columnwise(lambda res, u, a, b: solve(res, u, a, b, bwd))
-    prod._matrix = lambda res, V, a, b: block(res, V, a, b, fwd)
-    tprod._matrix = lambda res, V, a, b: block(res, V, a, b, bwd)
-    pinv = LinearOperator(T, k, m, False, False, prod, tprod, tprod, S=Storage(T, A.device))
-    pinv._deps = (W,)
-    pinv._tall = tall
+    pinv = _rect_operator(T, m, k, tall, mf, nf, "mxlo_pinv_mul", "mxlo_pinv_mul_block", W,
+                          (tfac.data_ptr(), perm.data_ptr(), r, W2.data_ptr(), tfac2.data_ptr(), dinv2.data_ptr()), work)
     pinv._rank = r
     pinv._perm = perm
     pinv._rtol = op._rtol
