@@ -56,13 +56,14 @@ def four_metrics(F, nF, v, u, x, y):
     return (lsq_error(F, nF, v, x), lsq_error(F.T, nF, u, y), space_distance(F.T, x), space_distance(F, y))
 
 
-def host_cod(F, npd):
-    """the device's algorithm on the host in the precision npd: geqp3, the rank rule, QR of [R11 R12]'; (rank, solve, solve_t)"""
+def host_cod(F, npd, rtol=None):
+    """the device's algorithm on the host in the precision npd: geqp3, the rank rule (rtol: None for the default max(m, n) eps),
+    QR of [R11 R12]'; (rank, solve, solve_t)"""
     from scipy.linalg import qr, solve_triangular
     m, n = F.shape
     Q1, R, perm = qr(F.astype(npd), mode="economic", pivoting=True)
     d = np.abs(np.diag(R)).astype(np.float64)
-    ok = d > max(m, n) * float(np.finfo(npd).eps) * d[0]
+    ok = d > (max(m, n) * float(np.finfo(npd).eps) if rtol is None else rtol) * d[0]
     r = int(n if ok.all() else np.argmin(ok))
     Q2, R2 = qr(np.ascontiguousarray(R[:r, :].T), mode="economic")
 

@@ -98,15 +98,22 @@ def held(tag, observed, bound):
     assert observed <= bound, (tag, observed / bound)
 
 
+def lsq_error(A, nA, v, x):
+    return float(np.linalg.norm(A.T @ (v - A @ x)) / (nA * (nA * np.linalg.norm(x) + np.linalg.norm(v))))
+
+
+def minimum_norm_residual(A, nA, u, y):
+    return float(np.linalg.norm(A.T @ y - u) / (nA * np.linalg.norm(y)))
+
+
 def check_least_squares(tag, A, nA, v, x, eps):
     m = A.shape[0]
-    e = np.linalg.norm(A.T @ (v - A @ x)) / (nA * (nA * np.linalg.norm(x) + np.linalg.norm(v)))
-    held(f"lsq {tag}", float(e), m * eps)
+    held(f"lsq {tag}", lsq_error(A, nA, v, x), m * eps)
 
 
 def check_minimum_norm(tag, A, nA, u, y, eps):
     m = A.shape[0]
-    held(f"minnorm residual {tag}", float(np.linalg.norm(A.T @ y - u) / (nA * np.linalg.norm(y))), m * eps)
+    held(f"minnorm residual {tag}", minimum_norm_residual(A, nA, u, y), m * eps)
     proj = A @ np.linalg.lstsq(A, y, rcond=None)[0]
     held(f"minnorm range {tag}", float(np.linalg.norm(y - proj) / np.linalg.norm(y)), m * eps)
 
