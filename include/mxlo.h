@@ -1089,6 +1089,39 @@ int32_t mxlo_pinv_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr
                             const double *dinv2, double *work, const void *V, int64_t ldv, int64_t k, int32_t op_mode, double alpha,
                             double beta);
 
+/* opLDL(M, pivot=true): P' M P = L D L' by BUNCH-KAUFMAN partial pivoting (LAPACK's sytrf strategy, alpha = (1 + sqrt 17) / 8)
+ * for a dense symmetric M of which, as in mxlo_ldlt, only the upper triangle is read (column- or row-major, m_rowmajor; M ==
+ * NULL: the lower triangle is already in W). L is unit lower triangular, D block diagonal with 1 x 1 and 2 x 2 blocks. W's strict
+ * lower triangle receives the FULLY PERMUTED L (every interchange is also applied to the rows of the columns left of it,
+ * not LAPACK's interleaved ipiv form; the entry below the diagonal inside a 2 x 2 block is 0), its diagonal the diagonal
+ * of D; d (n doubles) the diagonal of D, e (n doubles) its sub-diagonal: e[k] != 0 exactly where a 2 x 2 block occupies k,
+ * k + 1; dinv the inverses of the unit lower 64 x 64 diagonal blocks of L. perm is 2 n + ceil(n/64) + 1 int32 on the device:
+ * perm[0 .. n) is the permutation, M[perm[i], perm[j]] = (L D L')[i, j], 0-based; then LAPACK-style interchanges (row i changed
+ * places with row perm[n + i]); then the columns at which the panels start. panel: n x 65 elements of the element type.
+ * Right-looking in panels of 64 or 65 columns (a 2 x 2 pivot chosen at a panel's 64th column takes the 65th with it; the next
+ * panel's start is a device word the following launches read), ceil(n/64) rounds of at most three launches whatever the
+ * data is: (a) ONE workgroup factors the panel, left-looking as lasyf, with the pivot search over the whole remaining
+ * height (first row on a tie, a NaN before any number) and the L D panel kept beside the L panel; (b) the panel's
+ * interchanges on the columns left of it; (c) C -= L21 (L21 D)' on the lower triangle with v_mfma_f64_16x16x4_f64 (f32 data: the
+ * f32 MFMA). 3 ceil(n/64) + 1 launches with the pack, the initialisation and the block inverses, nothing read back in between. A 1 x 1 step whose max(|a_kk|, lambda) is exactly
+ * zero or not finite, or a 2 x 2 step whose determinant is, stores the 1-BASED index of the step's first column in *info_dev;
+ * every later launch returns at once; *info (host) = that word, copied once after the last launch. Not capturable. */
+int32_t mxlo_sytrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_rowmajor, void *W, int64_t ldw, int64_t n,
+                   double *dinv, double *d, double *e, int32_t *perm, void *panel, int32_t *info_dev, int32_t *info);
+/* res = alpha * M^{-1} v + beta * res with W, dinv, d, e and perm (its first n entries) from mxlo_sytrf: the first launch gathers
+ * v[perm[i]] into the f64 work vector, the unit lower sweep ascends (ceil(n/64) launches), ONE element-wise launch solves with D
+ * (the thread of a pivot block's first index handles both entries of a 2 x 2 block, so no launch reads what another
+ * workgroup of it writes), the transposed sweep descends (ceil(n/64) launches) and its last launch scatters the epilogue,
+ * res[perm[i]] = alpha z[i] + beta res[perm[i]]. EXACTLY 2 ceil(n/64) + 1 launches and nothing else; capturable,
+ * bit-reproducible. res == v is allowed; res / v may not overlap W, dinv, d, e, perm or work. */
+int32_t mxlo_ldlp_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *L, int64_t ld, int64_t n, const double *dinv,
+                      const double *d, const double *e, const int32_t *perm, double *work, const void *v, double alpha, double beta);
+/* mxlo_ldlp_mul on k columns, as the other block forms: groups of 8, ceil(k/8) (2 ceil(n/64) + 1) launches, column j BIT FOR
+ * BIT the vector apply of column j; work holds n * min(k, 8) doubles. */
+int32_t mxlo_ldlp_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *L, int64_t ld, int64_t n,
+                            const double *dinv, const double *d, const double *e, const int32_t *perm, double *work, const void *V,
+                            int64_t ldv, int64_t k, double alpha, double beta);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ from .graph import CapturedSequence, capture_mul
 from .utilities import check_ctranspose, check_hermitian, check_positive_definite, normest
 from .opnorm import estimate_opnorm
 from .linalg import PosDefException, SingularException, ZeroPivotException, opCholesky, opInverse, opLDL, opLU, opPinv, opQR
+from .linalg import ldl_inertia, ldlp_launches
 
 try:
     from . import sharded

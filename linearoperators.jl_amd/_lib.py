@@ -216,6 +216,10 @@ _PROTOS = {
     "mxlo_pinv_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _dbl, _dbl],
     "mxlo_pinv_mul_block": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32,
                             _dbl, _dbl],
+    # opLDL(pivot=True): mxlo_ldlt's with (e, perm, panel) after d / mxlo_ldl_mul's with (e, perm) after d
+    "mxlo_sytrf": [_vp, _i32, _vp, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32)],
+    "mxlo_ldlp_mul": [_vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl],
+    "mxlo_ldlp_mul_block": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _dbl, _dbl],
 }
 
 

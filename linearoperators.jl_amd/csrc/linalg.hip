@@ -3048,3 +3048,414 @@ MXLO_API int32_t mxlo_pinv_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, in
     return pinv_mul_t<T>(ctx, r, (const T *)W, ldw, mf, nf, tfac, jpvt, rank, (const T *)W2, tfac2, dinv2, work, v, tr, alpha, beta, grp);
   });
 }
+
+// ---------------------------------------------------------------------------------------------- sytrf (Bunch-Kaufman)
+// P' M P = L D L' with L unit lower triangular and D block diagonal with 1 x 1 and 2 x 2 blocks, by Bunch-Kaufman partial
+// pivoting on the lower triangle, right-looking in panels. A panel is 64 or 65 columns wide: it takes columns while fewer
+// than 64 are done, and a 2 x 2 pivot chosen at its 64th column takes the 65th with it. Where panel k starts is therefore
+// known on the device only: starts[k], written by panel k - 1 and read by every launch of round k; the chain itself is
+// ceil(n / 64) rounds whatever the data is, and a round whose start is n does nothing. Per round: (a) ONE workgroup factors the
+// panel, left-looking as LAPACK's lasyf: the trailing columns of A stay as the round found them, the panel's columns are
+// brought up to date one by one against the finished ones, into the n x 65 workspace Wk, which ends up holding L D beside
+// the panel of L in A; (b) the panel's interchanges, in order, on the rows of every column left of it, so that L is the
+// factor of the fully permuted matrix; (c) C -= L21 (L21 D)' on the lower triangle of the trailing matrix, on MFMA. One last
+// launch inverts the unit lower diagonal blocks of L for the sweeps, whose blocks stay at multiples of 64.
+namespace {
+constexpr int SNB = NB + 1;                              // the widest panel
+constexpr double BK_ALPHA = 0.6403882032022076;          // (1 + sqrt(17)) / 8
+
+// the best (|a|, row) of the workgroup, in every thread; a thread without a candidate brings (-1, 0x7fffffff)
+__device__ __forceinline__ void panel_argmax(double &best, int &bi, double *s_val, int *s_idx, int lane, int wave) {
+  for (int o = 32; o; o >>= 1) {
+    const double ob = __shfl_xor(best, o);
+    const int oi = __shfl_xor(bi, o);
+    if (pivot_better(ob, oi, best, bi)) { best = ob; bi = oi; }
+  }
+  if (lane == 0) { s_val[wave] = best; s_idx[wave] = bi; }
+  __syncthreads();
+  best = s_val[0]; bi = s_idx[0];
+  for (int w = 1; w < PT / 64; ++w)
+    if (pivot_better(s_val[w], s_idx[w], best, bi)) { best = s_val[w]; bi = s_idx[w]; }
+  __syncthreads();
+}
+
+// wc[k .. n) = column c of the symmetric trailing matrix, brought up to date against the panel's kw finished columns:
+// entry i is A[i, c] (i >= c) or A[c, i] (i < c) minus sum_j A[i, j0 + j] s_u[j], s_u = row c of L D. The thread's largest
+// |entry| and its row come back, row `c` itself left out (the first row on a tie, a NaN before any number).
+template <typename T>
+__device__ __forceinline__ void bk_column(const T *A, int64_t ld, T *wc, int64_t n, int64_t j0, int64_t k, int kw, int64_t c,
+                                          const double *s_u, int tid, double &best, int &bi) {
+  best = -1.0;
+  bi = 0x7fffffff;
+  for (int64_t i = k + tid; i < n; i += PT) {
+    double x = i < c ? (double)A[c + i * ld] : (double)A[i + c * ld];
+    const T *row = A + i + j0 * ld;
+    for (int j = 0; j < kw; ++j) x = fma(-(double)row[(int64_t)j * ld], s_u[j], x);
+    const T xt = (T)x;
+    wc[i] = xt;
+    const double a = fabs((double)xt);
+    if (i != c && !(a <= best) && best == best) { best = a; bi = (int)i; }   // a NaN is taken and then kept
+  }
+}
+
+__device__ __forceinline__ bool usable(double x) { return x != 0.0 && fabs(x) < __builtin_inf(); }
+
+// perm = ipiv = 0 .. n - 1, e = 0, starts = 0, n, n, ...
+__global__ void __launch_bounds__(kBlock) sytrf_init_kernel(int *__restrict__ perm, double *__restrict__ e, int64_t n, int64_t nb) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) { perm[i] = perm[n + i] = (int)i; e[i] = 0.0; }
+  if (i <= nb) perm[2 * n + i] = i == 0 ? 0 : (int)n;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(PT) sytrf_panel_kernel(T *A, int64_t ld, int64_t n, T *Wk, int *starts, int round, int *perm,
+                                                         double *d, double *e, int *info) {
+  __shared__ double s_val[PT / 64], s_u[SNB];
+  __shared__ int s_idx[PT / 64];
+  if (*info != 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int *ipiv = perm + n;
+  const int64_t j0 = starts[round];
+  if (j0 < 0 || j0 >= n) return;                         // the rounds before took every column: starts[round + 1] is n already
+  int64_t k = j0;
+  for (int step = 0; step < NB && k - j0 < NB && k < n; ++step) {
+    const int kw = (int)(k - j0);
+    T *w0 = Wk + (int64_t)kw * n, *w1 = w0 + n;
+    if (tid < kw) s_u[tid] = (double)Wk[k + (int64_t)tid * n];
+    __syncthreads();
+    double cm;
+    int im;
+    bk_column<T>(A, ld, w0, n, j0, k, kw, k, s_u, tid, cm, im);
+    panel_argmax(cm, im, s_val, s_idx, lane, wave);
+    const bool below = im > k && im < n;                 // false for column n - 1 only; an index taken from data is a row
+    const int64_t imax = below ? im : k;
+    const double colmax = below ? cm : 0.0, absakk = fabs((double)w0[k]);
+    if (!(absakk < __builtin_inf()) || !(colmax < __builtin_inf()) || (absakk == 0.0 && colmax == 0.0)) {
+      if (tid == 0) *info = (int)(k + 1);
+      return;
+    }
+    int kstep = 1;
+    int64_t kp = k;
+    if (!(absakk >= BK_ALPHA * colmax)) {                // only with colmax > 0, so imax is a row below k
+      if (tid < kw) s_u[tid] = (double)Wk[imax + (int64_t)tid * n];
+      __syncthreads();
+      double rm;
+      int jm;
+      bk_column<T>(A, ld, w1, n, j0, k, kw, imax, s_u, tid, rm, jm);
+      panel_argmax(rm, jm, s_val, s_idx, lane, wave);
+      const double rowmax = (jm >= k && jm < n) ? rm : 0.0;
+      if (absakk >= BK_ALPHA * colmax * (colmax / rowmax)) {
+        kp = k;
+      } else if (fabs((double)w1[imax]) >= BK_ALPHA * rowmax) {
+        kp = imax;                                       // the diagonal entry of column imax is the 1 x 1 pivot
+        for (int64_t i = k + tid; i < n; i += PT) w0[i] = w1[i];
+        __syncthreads();
+      } else {
+        kp = imax;
+        kstep = 2;
+      }
+    }
+    const int64_t kk = k + kstep - 1;
+    if (kp != kk) {                                      // kk < kp < n. Column kk of A, as the round found it, moves to place kp ...
+      if (tid == 0) A[kp + kp * ld] = A[kk + kk * ld];
+      for (int64_t i = kk + 1 + tid; i < kp; i += PT) A[kp + i * ld] = A[i + kk * ld];
+      for (int64_t i = kp + 1 + tid; i < n; i += PT) A[i + kp * ld] = A[i + kk * ld];
+      if (tid < kw) {                                    // ... rows kk and kp change places in the panel's finished columns ...
+        T *c = A + (j0 + tid) * ld;
+        const T x = c[kk];
+        c[kk] = c[kp];
+        c[kp] = x;
+      }
+      const int cw = tid - 2 * NB;                       // ... and in the columns 0 .. kk - j0 of L D
+      if (cw >= 0 && cw <= (int)(kk - j0)) {
+        T *c = Wk + (int64_t)cw * n;
+        const T x = c[kk];
+        c[kk] = c[kp];
+        c[kp] = x;
+      }
+      if (tid == PT - 1) {
+        const int t = perm[kk];
+        perm[kk] = perm[kp];
+        perm[kp] = t;
+      }
+    }
+    if (tid == 0) {
+      ipiv[k] = (int)k;
+      ipiv[kk] = (int)kp;
+    }
+    __syncthreads();
+    if (kstep == 1) {
+      const T dt = w0[k];
+      const double dk = (double)dt;
+      if (!usable(dk)) {
+        if (tid == 0) *info = (int)(k + 1);
+        return;
+      }
+      for (int64_t i = k + 1 + tid; i < n; i += PT) A[i + k * ld] = (T)((double)w0[i] / dk);
+      if (tid == 0) { A[k + k * ld] = dt; d[k] = dk; e[k] = 0.0; }
+    } else {                                             // the 2 x 2 block [d0 e0; e0 d1]; L = (L D) inv(block) as in LAPACK
+      const T t0 = w0[k], t1 = w1[k + 1], te = w0[k + 1];
+      const double e0 = (double)te, d11 = (double)t1 / e0, d22 = (double)t0 / e0, t = d11 * d22 - 1.0;
+      if (!usable(e0) || !usable(t)) {
+        if (tid == 0) *info = (int)(k + 1);
+        return;
+      }
+      const double s = (1.0 / t) / e0;
+      for (int64_t i = k + 2 + tid; i < n; i += PT) {
+        const double a = (double)w0[i], b = (double)w1[i];
+        A[i + k * ld] = (T)(s * (d11 * a - b));
+        A[i + (k + 1) * ld] = (T)(s * (d22 * b - a));
+      }
+      if (tid == 0) {
+        A[k + k * ld] = t0;
+        A[(k + 1) + k * ld] = T(0);                      // L is unit lower: the block's off-diagonal entry lives in e
+        A[(k + 1) + (k + 1) * ld] = t1;
+        d[k] = (double)t0; d[k + 1] = (double)t1; e[k] = e0; e[k + 1] = 0.0;
+      }
+    }
+    __syncthreads();
+    k += kstep;
+  }
+  if (tid == 0) starts[round + 1] = (int)k;
+}
+
+// the columns [s, j1) of round `round`, or false when there is nothing to do; both words are checked before they index anything
+__device__ __forceinline__ bool panel_range(const int *starts, int round, int64_t n, int64_t &s, int64_t &j1) {
+  s = starts[round];
+  j1 = starts[round + 1];
+  return s >= 0 && j1 > s && j1 <= n && j1 - s <= SNB;
+}
+
+// phase (b): the panel's interchanges, in order, on every column left of it; one thread a column
+template <typename T>
+__global__ void __launch_bounds__(kBlock) sytrf_swap_kernel(T *A, int64_t ld, int64_t n, const int *starts, int round, const int *perm,
+                                                            const int *info) {
+  __shared__ int sp[SNB];
+  if (*info != 0) return;
+  int64_t s, j1;
+  if (!panel_range(starts, round, n, s, j1)) return;
+  const int jb = (int)(j1 - s);
+  if ((int)threadIdx.x < jb) sp[threadIdx.x] = perm[n + s + threadIdx.x];
+  __syncthreads();
+  const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (idx >= s) return;
+  T *col = A + idx * ld;
+  for (int p = 0; p < jb; ++p) {
+    const int64_t r = sp[p];
+    if (r > s + p && r < n) {
+      const T x = col[s + p];
+      col[s + p] = col[r];
+      col[r] = x;
+    }
+  }
+}
+
+// phase (c): C -= P Q' on the lower triangle of the trailing matrix, P the panel of L (in A) and Q the panel of L D (in Wk):
+// potrf_syrk_kernel with two operands, its sizes read from the device
+template <typename T>
+__global__ void __launch_bounds__(kBlock) sytrf_update_kernel(T *A, int64_t ld, int64_t n, const T *Wk, const int *starts, int round,
+                                                              const int *info) {
+  if (blockIdx.y > blockIdx.x) return;
+  if (*info != 0) return;
+  int64_t s, j1;
+  if (!panel_range(starts, round, n, s, j1)) return;
+  const int K = (int)(j1 - s), M = (int)(n - j1);
+  const int bm = blockIdx.x * NB, bn = blockIdx.y * NB;
+  if (bm >= M) return;
+  T *C = A + j1 + j1 * ld;
+  const T *P = A + j1 + s * ld, *Q = Wk + j1;
+  __shared__ T sA[SK][SLD], sB[SK][SLD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
+  using Acc = typename Mfma<T>::Acc;
+  Acc acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[a][b][r] = 0;
+  for (int k0 = 0; k0 < K; k0 += SK) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int el = tid + t * kBlock, i = el & 63, k = el >> 6, gk = k0 + k;
+      sA[k][i] = (bm + i < M && gk < K) ? P[(bm + i) + (int64_t)gk * ld] : T(0);
+      sB[k][i] = (bn + i < M && gk < K) ? Q[(bn + i) + (int64_t)gk * n] : T(0);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kq = 0; kq < SK; kq += 4) {
+      const int kr = kq + (lane >> 4);
+      const T a0 = sA[kr][wm + (lane & 15)], a1 = sA[kr][wm + 16 + (lane & 15)];
+      const T b0 = sB[kr][wn + (lane & 15)], b1 = sB[kr][wn + 16 + (lane & 15)];
+      acc[0][0] = Mfma<T>::run(a0, b0, acc[0][0]);
+      acc[0][1] = Mfma<T>::run(a0, b1, acc[0][1]);
+      acc[1][0] = Mfma<T>::run(a1, b0, acc[1][0]);
+      acc[1][1] = Mfma<T>::run(a1, b1, acc[1][1]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int gi = bm + wm + a * 16 + Mfma<T>::row(lane, r), gj = bn + wn + b * 16 + (lane & 15);
+        if (gi < M && gj <= gi) {
+          T *p = C + gi + (int64_t)gj * ld;
+          *p = *p - acc[a][b][r];
+        }
+      }
+}
+
+// the inverses of all unit lower diagonal blocks of L, one workgroup each (the lower half of getrf_inv_kernel)
+template <typename T>
+__global__ void __launch_bounds__(kBlock) sytrf_inv_kernel(const T *__restrict__ A, int64_t ld, int64_t n, double *__restrict__ dinv,
+                                                           const int *info) {
+  __shared__ double sL[NB2], sX[NB2];
+  if (*info != 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+  const int64_t j0 = (int64_t)blockIdx.x * NB;
+  const int jb = (int)(n - j0 < NB ? n - j0 : NB);
+  for (int c = q; c < NB; c += 4) {
+    double x = lane == c ? 1.0 : 0.0;
+    if (lane < jb && lane > c) x = (double)A[(j0 + lane) + (j0 + c) * ld];
+    sL[c * NB + lane] = x;
+  }
+  __syncthreads();
+  invert_block(sL, sX, tid, lane, q);
+  double *out = dinv + (int64_t)blockIdx.x * NB2;
+  for (int c = q; c < NB; c += 4) out[c * NB + lane] = sX[c * NB + lane];
+}
+
+template <typename T>
+int32_t sytrf_t(mxlo_ctx *ctx, const T *M, int64_t ldm, int rowmajor, T *W, int64_t ldw, int64_t n, double *dinv, double *d, double *e,
+                int *perm, T *wk, int *info_dev) {
+  const int64_t nb = (n + NB - 1) / NB;
+  int *starts = perm + 2 * n;
+  MXLO_HIP(hipMemsetAsync(info_dev, 0, sizeof(int), ctx->stream));
+  if (M) {
+    hipLaunchKernelGGL((pack_upper_kernel<T>), dim3((unsigned)nb, (unsigned)nb), dim3(kBlock), 0, ctx->stream, W, ldw, M, ldm,
+                       rowmajor, n);
+    MXLO_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(sytrf_init_kernel, dim3((unsigned)((n + kBlock) / kBlock)), dim3(kBlock), 0, ctx->stream, perm, e, n, nb);
+  MXLO_LAUNCH_CHECK();
+  for (int64_t k = 0; k < nb; ++k) {
+    hipLaunchKernelGGL((sytrf_panel_kernel<T>), dim3(1), dim3(PT), 0, ctx->stream, W, ldw, n, wk, starts, (int)k, perm, d, e, info_dev);
+    MXLO_LAUNCH_CHECK();
+    const int64_t left = k * SNB < n ? k * SNB : n;       // round k starts at column 65 k at the latest ...
+    if (left > 0) {
+      hipLaunchKernelGGL((sytrf_swap_kernel<T>), dim3((unsigned)((left + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, W, ldw, n,
+                         (const int *)starts, (int)k, (const int *)perm, (const int *)info_dev);
+      MXLO_LAUNCH_CHECK();
+    }
+    const int64_t m = n - (k + 1) * NB;                   // ... and ends at column 64 (k + 1) at the earliest, or at n
+    if (m > 0) {
+      const unsigned tiles = (unsigned)((m + NB - 1) / NB);
+      hipLaunchKernelGGL((sytrf_update_kernel<T>), dim3(tiles, tiles), dim3(kBlock), 0, ctx->stream, W, ldw, n, (const T *)wk,
+                         (const int *)starts, (int)k, (const int *)info_dev);
+      MXLO_LAUNCH_CHECK();
+    }
+  }
+  hipLaunchKernelGGL((sytrf_inv_kernel<T>), dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream, (const T *)W, ldw, n, dinv,
+                     (const int *)info_dev);
+  MXLO_LAUNCH_CHECK();
+  return MXLO_OK;
+}
+
+// z <- inv(D) z on the kb columns of z (column stride n), one launch between the two sweeps. The thread of the FIRST index of a
+// pivot block handles all of it, so no thread reads an entry that another one writes; a 2 x 2 block is solved with the
+// scaled explicit inverse of LAPACK's sytrs. Per entry the operations do not depend on kb.
+__global__ void __launch_bounds__(kBlock) ldlp_dsolve_kernel(double *__restrict__ z, int64_t n, const double *__restrict__ d,
+                                                             const double *__restrict__ e, int kb) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  if (i > 0 && e[i - 1] != 0.0) return;                  // the second index of a 2 x 2 block
+  const double ei = i + 1 < n ? e[i] : 0.0;
+  if (ei == 0.0) {
+    const double di = d[i];
+    for (int j = 0; j < kb; ++j) z[i + (int64_t)j * n] /= di;
+    return;
+  }
+  const double akm1 = d[i] / ei, ak = d[i + 1] / ei, denom = akm1 * ak - 1.0;
+  for (int j = 0; j < kb; ++j) {
+    double *zj = z + i + (int64_t)j * n;
+    const double bkm1 = zj[0] / ei, bk = zj[1] / ei;
+    zj[0] = (ak * bkm1 - bk) / denom;
+    zj[1] = (akm1 * bk - bkm1) / denom;
+  }
+}
+
+// x = P L^{-T} inv(D) L^{-1} P' v: v gathered by perm, the unit lower sweep up, inv(D), the transposed sweep down with the
+// epilogue scattered by perm. ceil(n / 64) + 1 + ceil(n / 64) launches.
+template <typename T>
+int32_t ldlp_mul_t(mxlo_ctx *ctx, T *res, const T *L, int64_t ld, int64_t n, const double *dinv, const double *d, const double *e,
+                   const int *perm, double *work, const T *v, double alpha, double beta, Group grp = {}) {
+  MXLO_TRY(sweep<T>(ctx, L, ld, n, false, false, dinv, work, v, true, false, false, res, alpha, beta, nullptr, nullptr, perm, nullptr,
+                    true, grp));
+  hipLaunchKernelGGL(ldlp_dsolve_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, work, n, d, e,
+                     grp.kb > 0 ? grp.kb : 1);
+  MXLO_LAUNCH_CHECK();
+  return sweep<T>(ctx, L, ld, n, false, true, dinv, work, (const T *)nullptr, true, false, true, res, alpha, beta, nullptr, nullptr,
+                  nullptr, perm, true, grp);
+}
+
+inline int64_t sytrf_perm_bytes(int64_t n) { return (2 * n + (n + NB - 1) / NB + 1) * 4; }
+
+int32_t check_ldlp_apply(mxlo_ctx *ctx, int32_t dtype, const Operands &o, const void *L, int64_t ld, int64_t n, const double *dinv,
+                         const double *d, const double *e, const int32_t *perm, const double *work, const char *what, bool &go) {
+  return check_apply(ctx, dtype, o, L, ld, n, dinv, work, what, go,
+                     {{d, n * 8, "the diagonal of D"}, {e, n * 8, "the sub-diagonal of D"}, {perm, n * 4, "the permutation"}});
+}
+}  // namespace
+
+MXLO_API int32_t mxlo_sytrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_rowmajor, void *W, int64_t ldw, int64_t n,
+                            double *dinv, double *d, double *e, int32_t *perm, void *panel, int32_t *info_dev, int32_t *info) {
+  const char *what = "mxlo_sytrf";
+  MXLO_TRY(check_common(ctx, dtype, W, ldw, n, what));
+  MXLO_REQUIRE(info, MXLO_EINVAL, "%s: null info", what);
+  *info = 0;
+  if (n == 0) return MXLO_OK;
+  MXLO_REQUIRE(dinv && d && e && perm && panel && info_dev, MXLO_EINVAL,
+               "%s: null storage for the block inverses / D / the permutation / the panel workspace / the info word", what);
+  MXLO_REQUIRE(n < (1LL << 31) - NB, MXLO_ESHAPE, "%s: n = %lld is too large", what, (long long)n);
+  if (M) MXLO_REQUIRE(ldm >= (n > 1 ? n : 1), MXLO_ESHAPE, "%s: ldm = %lld < n", what, (long long)ldm);
+  const int64_t es = esize(dtype);
+  const Buf m{M, M ? mat_bytes(n, n, ldm, es) : 0, "M"};
+  MXLO_TRY(disjoint({m, {W, mat_bytes(n, n, ldw, es), "the factor"}, {dinv, blocks_bytes(n), "the block inverses"},
+                     {d, n * 8, "the diagonal of D"}, {e, n * 8, "the sub-diagonal of D"}, {perm, sytrf_perm_bytes(n), "the permutation"},
+                     {panel, n * SNB * es, "the panel workspace"}}, what));
+  MXLO_TRY(disjoint({m, {info_dev, 4, "the info word"}}, what));
+  MXLO_TRY(refuse_capture(ctx, what));
+  MXLO_DEVICE_GUARD(ctx);
+  MXLO_TRY(with_real(dtype, [&]<typename T>() {
+    return sytrf_t<T>(ctx, (const T *)M, ldm, m_rowmajor ? 1 : 0, (T *)W, ldw, n, dinv, d, e, perm, (T *)panel, info_dev);
+  }));
+  return read_back(ctx, info_dev, info, 1);
+}
+
+MXLO_API int32_t mxlo_ldlp_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *L, int64_t ld, int64_t n, const double *dinv,
+                               const double *d, const double *e, const int32_t *perm, double *work, const void *v, double alpha,
+                               double beta) {
+  bool go;
+  MXLO_TRY(check_ldlp_apply(ctx, dtype, vectors(res, v, n, n), L, ld, n, dinv, d, e, perm, work, "mxlo_ldlp_mul", go));
+  if (!go) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  return with_real(dtype, [&]<typename T>() {
+    return ldlp_mul_t<T>(ctx, (T *)res, (const T *)L, ld, n, dinv, d, e, perm, work, (const T *)v, alpha, beta);
+  });
+}
+
+MXLO_API int32_t mxlo_ldlp_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *L, int64_t ld, int64_t n,
+                                     const double *dinv, const double *d, const double *e, const int32_t *perm, double *work,
+                                     const void *V, int64_t ldv, int64_t k, double alpha, double beta) {
+  bool go;
+  MXLO_TRY(check_ldlp_apply(ctx, dtype, Operands{res, V, k, ldr, ldv, n, n}, L, ld, n, dinv, d, e, perm, work, "mxlo_ldlp_mul_block", go));
+  if (!go) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  return for_real_groups(dtype, res, ldr, V, ldv, k, [&]<typename T>(T *r, const T *v, Group grp) {
+    return ldlp_mul_t<T>(ctx, r, (const T *)L, ld, n, dinv, d, e, perm, work, v, alpha, beta, grp);
+  });
+}

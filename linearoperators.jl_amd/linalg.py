@@ -6,7 +6,8 @@ The factorisation, the inverses of the diagonal blocks and the block substitutio
 Real Float64 / Float32 only. `mul!` on an n x k matrix (`F \\ V`, src/operations.jl:34-36) takes the block form of the sweeps for k > 1
 (`mxlo_*_mul_block`): the chain of launches of one vector apply and one read of the factor per GROUP = 8 columns, each column
 bit-identical to its vector apply. The inverse of a general dense matrix is `opLU` (partially pivoted LU); `opInverse` itself
-stays triangular-only. A pivoted (Bunch–Kaufman) or sparse LDLᵀ are not provided. `refine=r` on the three
+stays triangular-only. `opLDL(M, pivot=True)` is the Bunch–Kaufman form Pᵀ M P = L D Lᵀ with 1 x 1 and 2 x 2 pivots (`mxlo_sytrf`,
+`mxlo_ldlp_mul`, `mxlo_ldlp_mul_block`), `ldl_inertia` the inertia it reveals; a sparse LDLᵀ is not provided. `refine=r` on the three
 factorisation operators adds r steps of iterative refinement to every apply (`mxlo_*_mul_refine`), with the residual and the
 iterate in Float64 and a snapshot of M the operator keeps. `opQR` is the rectangular `M \\ v`: least-squares and minimum-norm
 solves through an unpivoted Householder QR (`mxlo_geqrf`, `mxlo_qr_mul`, and `mxlo_qr_mul_block` for matrix operands), or — `pivot=True` —
@@ -234,14 +235,28 @@ def opCholesky(M: torch.Tensor, check: bool = False, refine: int = 0):
 opCholesky.__doc__ += _REFINE_DOC
 
 
-def opLDL(M: torch.Tensor, check: bool = False, refine: int = 0):
+def opLDL(M: torch.Tensor, check: bool = False, refine: int = 0, pivot: bool = False):
     """opLDL(M; check=false) — ext/LinearOperatorsLDLFactorizationsExt.jl:5-18 (docstring: src/linalg.jl:60-73) for a DENSE
     symmetric M: its inverse through M = L D Lᵀ (L unit lower triangular, D diagonal), computed ONCE here, on the device,
     into storage the operator owns (M is not modified). Only the UPPER triangle of M is read (`Symmetric(M, :U)`);
     column-major and row-major M are read in place, anything else is copied to column-major first. `check=True` runs
     `check_hermitian` first; there is no definiteness check.
 
-    There is NO pivoting: no symmetric permutation and no 2 x 2 (Bunch–Kaufman) pivots. The factorisation is taken "if it
+    pivot=True (a bool, checked before M is looked at): Pᵀ M P = L D Lᵀ by Bunch–Kaufman partial pivoting, LAPACK's `sytrf`
+    strategy with α = (1 + √17)/8: D is block diagonal with 1 x 1 and 2 x 2 blocks, |L| stays bounded, and the solve is
+    backward stable for ANY symmetric M that is not singular — [[0, 1], [1, 0]] and saddle-point matrices [0 B; Bᵀ A]
+    included. The pivot search, the four-way decision and the symmetric interchanges happen on the device inside a chain
+    of 3⌈n/64⌉ + 1 launches that depends on n only (`mxlo_sytrf`; panels of 64 or 65 columns); an n x 65
+    workspace lives during the construction. `op._perm` (int32, device): M[perm][:, perm] = L D Lᵀ; `op._d` the diagonal of
+    D and `op._e` its sub-diagonal (Float64; e[k] ≠ 0 exactly where a 2 x 2 block occupies k, k + 1); `op._factor[0]` holds the
+    fully permuted L strictly below its diagonal. `ldl_inertia(op)` counts the inertia of M from d and e.
+    `ZeroPivotException(info)`: at the step that starts at the 1-based column info, max(|a_kk|, λ) of a 1 x 1 step, or the
+    determinant of a 2 x 2 step, is exactly zero or not finite. An apply is `ldlp_launches(n)` = 2⌈n/64⌉ + 1 launches (gather
+    by perm, the sweep with L, one element-wise launch for D⁻¹, the sweep with Lᵀ, the epilogue scattered by perm), with
+    every promise below; matrix operands take the block form (`mxlo_ldlp_mul_block`). refine > 0 with pivot=True is a
+    ValueError. What follows describes pivot=False, which is unchanged.
+
+    Without pivot=True there is NO pivoting: no symmetric permutation and no 2 x 2 (Bunch–Kaufman) pivots. The factorisation is taken "if it
     exists", in the order the rows come, which keeps it a fixed chain of launches without a host round trip. Negative
     pivots and tiny non-zero pivots are legitimate and are used as they come; a pivot that is exactly zero or not finite
     raises `ZeroPivotException(info)` with its 1-based index. The solve is backward stable when
@@ -256,10 +271,100 @@ def opLDL(M: torch.Tensor, check: bool = False, refine: int = 0):
     backward error from ρ·eps (ρ the growth of |L||D||Lᵀ|) back to the order of n·eps as long as ρ·cond·eps < 1. The
     operator then keeps a snapshot of M, taken here: its strict upper triangle in the unused strict upper triangle of the
     factor's storage, its diagonal in n further elements — no second n x n buffer; the work space is 2 n x 8 doubles."""
-    return _symmetric("opLDL", "ldl", "mxlo_ldlt", True, ZeroPivotException, M, check, refine)
+    if not isinstance(pivot, bool):                     # before M is looked at, as _check_refine / _check_pivot
+        raise TypeError(f"opLDL: pivot must be a bool, got {type(pivot).__name__}")
+    if not pivot:
+        return _symmetric("opLDL", "ldl", "mxlo_ldlt", True, ZeroPivotException, M, check, refine)
+    if _check_refine(refine, "opLDL"):
+        raise ValueError("opLDL: refine > 0 is not provided for pivot=True (DESIGN.md §8)")
+    return _ldl_pivoted(M, check)
 
 
 opLDL.__doc__ += _REFINE_DOC
+
+
+def ldlp_launches(n: int) -> int:
+    """Launches of ONE apply of opLDL(M, pivot=True) of order n: the ⌈n/64⌉ of the sweep with L, one for D⁻¹, the ⌈n/64⌉ of the
+    sweep with Lᵀ. It depends on n only, whatever the pivots are."""
+    n = int(n)
+    return 0 if n <= 0 else 2 * ((n + BLOCK - 1) // BLOCK) + 1
+
+
+def ldlp_block_launches(n: int, k: int) -> int:
+    """Launches of a pivoted apply to a matrix with k columns: the chain of one vector apply per group of GROUP columns."""
+    return ((int(k) + GROUP - 1) // GROUP) * ldlp_launches(n)
+
+
+def _ldl_pivoted(M, check):
+    """opLDL(M, pivot=True) once `pivot` and `refine` have been checked: `_symmetric`'s order of checks, the storage, `mxlo_sytrf`,
+    the closures over `mxlo_ldlp_mul` / `mxlo_ldlp_mul_block`."""
+    n = _check_matrix(M, "opLDL")
+    T = M.dtype
+    if check:
+        from .utilities import check_hermitian
+        if not check_hermitian(M):
+            raise LinearOperatorException("matrix is not Hermitian")
+    St, tr = _stored_colmajor(M)
+    ldm = max(1, St.stride(1)) if n > 1 else 1
+    ctx = get_ctx(M.device)
+    W = torch.zeros((n, n), dtype=T, device=M.device).t()            # column-major, ld = n: L strictly below the diagonal
+    ldw = max(1, n)
+    nblk = (n + BLOCK - 1) // BLOCK
+    dinv = torch.empty(max(1, nblk) * BLOCK * BLOCK, dtype=torch.float64, device=M.device)
+    de = torch.zeros((2, max(1, n)), dtype=torch.float64, device=M.device)    # the diagonal and the sub-diagonal of D
+    pbuf = torch.empty(2 * n + nblk + 1, dtype=torch.int32, device=M.device)  # the permutation, the interchanges, the panel starts
+    panel = torch.empty(max(1, n) * (BLOCK + 1), dtype=T, device=M.device)    # L D of one panel: needed by the factorisation only
+    work = _work(n, M.device)
+    info_dev = torch.zeros(1, dtype=torch.int32, device=M.device)
+    info = C.c_int32(0)
+    code = dtype_code(T)
+    _lib.call("mxlo_sytrf", ctx.handle, code, St.data_ptr(), ldm, 1 if tr else 0, W.data_ptr(), ldw, n, dinv.data_ptr(),
+              de[0].data_ptr(), de[1].data_ptr(), pbuf.data_ptr(), panel.data_ptr(), info_dev.data_ptr(), C.byref(info))
+    del panel                                           # after the read-back of info, which is the end of the chain
+    if info.value != 0:
+        raise ZeroPivotException(info.value)
+    head = (W.data_ptr(), ldw, n, dinv.data_ptr(), de[0].data_ptr(), de[1].data_ptr(), pbuf.data_ptr(), work.data_ptr())
+
+    def prod(res, v, a, b):                             # mulFact!(res, F, v, α, β) — src/linalg.jl:3-9
+        _check_operands(res, v, T)
+        _lib.call("mxlo_ldlp_mul", ctx_of(res).handle, code, res.data_ptr(), *head, v.data_ptr(), float(a), float(b))
+
+    def block(res, m, a, b):                            # `F \ V`: one chain of launches and two reads of L per 8 columns
+        ldr, ldv, k = _check_block_operands(res, m, T, n)
+        _lib.call("mxlo_ldlp_mul_block", ctx_of(res).handle, code, res.data_ptr(), ldr, *head, m.data_ptr(), ldv, k, float(a), float(b))
+
+    columnwise(prod)
+    prod._matrix = block
+    op = LinearOperator(T, n, n, True, True, prod, prod, prod, S=Storage(T, M.device))
+    op._deps = (W,)
+    op._perm = pbuf[:n]
+    op._d = de[0, :n]
+    op._e = de[1, :n]
+    op._factor = (W, dinv, de, pbuf, work)              # owned storage (kept alive with the operator)
+    op._refine = 0
+    return op
+
+
+def ldl_inertia(op):
+    """(n_pos, n_neg, n_zero) of the matrix an opLDL operator was built from, by Sylvester's law of inertia from the block
+    diagonal D: one read-back of `op._d` and, for a pivoted operator, `op._e`. A 2 x 2 block that Bunch–Kaufman chose has a
+    negative determinant, one positive and one negative eigenvalue, and counts (1, 1, 0). An unpivoted operator has no
+    `_e`: its D is diagonal."""
+    d = getattr(op, "_d", None)
+    if d is None:
+        raise TypeError("ldl_inertia: not an opLDL operator (no pivots `_d`)")
+    e = getattr(op, "_e", None)
+    d = d.detach().cpu().tolist() if e is None else torch.stack((d, e)).cpu().tolist()
+    d, e = (d, [0.0] * len(d)) if e is None else d
+    pos = neg = zero = 0
+    k, n = 0, len(d)
+    while k < n:
+        if e[k] != 0.0 and k + 1 < n:
+            pos, neg, k = pos + 1, neg + 1, k + 2
+            continue
+        pos, neg, zero = pos + (d[k] > 0), neg + (d[k] < 0), zero + (d[k] == 0)
+        k += 1
+    return int(pos), int(neg), int(zero)
 
 
 def opInverse(M: torch.Tensor, symm: bool = False, herm: bool = False):

@@ -52,6 +52,16 @@ the apply in both modes on a vector and on k = 8 columns; GB/s by the two-read m
 2·(mf + nf)·r·sizeof(T) for opPinv's —, the last column the time over the pivoted row's, to be held against 1 + nf/mf.
 
     python tools/bench_linalg.py --pinv [MFxNF ...] > profiles/linalg_pinv.txt
+
+--ldlp: opLDL(K, pivot=True) on the indefinite K = (G + Gᵀ)/√(2n) at n = 2048, 8192, 16384 in both precisions: the factorisation
+(construction, allocations and the one synchronisation included) and the apply on a vector, on k = 8 columns and as a graph
+replay — and, in the same run, the yardsticks: opLU(K), what a caller had for such a matrix before; the unpivoted opLDL on a
+quasi-definite matrix of the same n, which prices the pivoting; torch.linalg.ldl_factor / ldl_solve on the device where this
+torch has them (n <= 2048 only: the vendor factorisation takes 52 s at n = 8192). GB/s by the byte model of two reads of the triangle (n² elements for opLU). `x opLU` is the time over the opLU
+row of the same kind. `--ldlp --once n` builds one Float64 opLDL(K, pivot=True) and one opLU(K) and nothing else: the run to put
+under a kernel trace, whose per-kernel totals are the panel's share of the factorisation.
+
+    python tools/bench_linalg.py --ldlp [n ...] > profiles/linalg_ldlp.txt
 """
 import ctypes as C
 import os
@@ -72,7 +82,9 @@ PEAK = 8000.0          # GB/s
 BLOCK = "--block" in sys.argv
 MUL_ONLY = "--mul-only" in sys.argv
 REFINE = "--refine" in sys.argv
-NS = [int(a) for a in sys.argv[1:] if not a.startswith("--") and "x" not in a] or ([2048, 8192, 16384] if BLOCK or REFINE else [1024, 4096, 16384])
+LDLP = "--ldlp" in sys.argv
+VENDOR_MAX = 2048      # --ldlp: the largest n at which torch.linalg.ldl_factor on the device is timed
+NS = [int(a) for a in sys.argv[1:] if not a.startswith("--") and "x" not in a] or ([2048, 8192, 16384] if BLOCK or REFINE or LDLP else [1024, 4096, 16384])
 
 
 def timeit(fn, reps):
@@ -370,6 +382,78 @@ def pinv_legs():
             torch.cuda.empty_cache()
 
 
+def indefinite(n, dtype):
+    """(G + G') / sqrt(2 n): the `indef` family of tests/ldl_pivot_cases.py, column-major"""
+    gen = torch.Generator(device=dev).manual_seed(7700 + n)
+    G = torch.randn(n, n, dtype=torch.float64, device=dev, generator=gen)
+    return ((G + G.t()) / (2 * n) ** 0.5).to(dtype).t().contiguous().t()
+
+
+def ldlp_legs():
+    """opLDL(K, pivot=True) beside opLU(K), the unpivoted opLDL and the vendor's LDL': see the module docstring"""
+    if "--once" in sys.argv:
+        K = indefinite(NS[0], torch.float64)
+        lo.opLDL(K, pivot=True)
+        lo.opLU(K)
+        torch.cuda.synchronize()
+        return
+    print(f"# {torch.cuda.get_device_name(0)}; opLDL(K, pivot=True) on K = (G + G') / sqrt(2 n); ms per call, median of 3 event-timed windows, "
+          f"spread = (max - min) / median")
+    print(f"# factorisation: construction, allocations and the one synchronisation included. apply: two reads of the triangle, n (n + 1) "
+          f"sizeof(T) (opLU: n^2 sizeof(T)), per group of 8 columns; peak {PEAK:.0f} GB/s. unpivoted opLDL: on a quasi-definite matrix")
+    print(f"{'case':46s} {'n':>6s} {'k':>2s} {'ms':>10s} {'spread':>6s} {'launch':>6s} {'GB/s':>8s} {'%peak':>6s} {'x opLU':>7s}", flush=True)
+    for dtype, tag in ((torch.float64, "f64"), (torch.float32, "f32")):
+        es = 8 if dtype is torch.float64 else 4
+        for n in NS:
+            K = indefinite(n, dtype)
+            Q = quasi_definite(spd(n, dtype))
+            tri2, full = n * (n + 1) * es, n * n * es
+            reps = 20 if n <= 2048 else (5 if n <= 8192 else 3)
+            base = {}
+
+            def row(name, fn, reps, nbytes, nl, key, k):
+                ms = timeit(fn, reps)
+                gbs = nbytes / ms / 1e6 if nbytes else 0.0
+                ratio = f"{ms / base[key]:7.3f}" if key in base else f"{'':7s}"
+                if name.startswith("opLU"):
+                    base[key] = ms
+                print(f"{name + ' ' + tag:46s} {n:6d} {k:2d} {ms:10.4f} {100 * timeit.spread:5.1f}% {nl:6d} {gbs:8.1f} {100 * gbs / PEAK:6.2f} {ratio}",
+                      flush=True)
+
+            row("opLU(K) factorisation", lambda: lo.opLU(K), 1, 0, 0, "f", 0)
+            row("opLDL(K, pivot=True) factorisation", lambda: lo.opLDL(K, pivot=True), 1, 0, 0, "f", 0)
+            row("unpivoted opLDL(Q) factorisation", lambda: lo.opLDL(Q), 1, 0, 0, "f", 0)
+            tsolve = None
+            try:                                        # the vendor LDL' (pivoted), as far as this torch has it on the device, and only
+                if n > VENDOR_MAX:                      # where it ends in reasonable time: it grows faster than n^3 (52 s at n = 8192)
+                    raise RuntimeError(f"skipped for n > {VENDOR_MAX}")
+                LD, piv = torch.linalg.ldl_factor(K)
+                row("torch.linalg.ldl_factor(K)", lambda: torch.linalg.ldl_factor(K), 1, 0, 0, "f", 0)
+                torch.linalg.ldl_solve(LD, piv, colmajor(n, 1, dtype, 3))
+                tsolve = lambda V: torch.linalg.ldl_solve(LD, piv, V)
+            except RuntimeError as err:
+                print(f"# torch.linalg.ldl_factor / ldl_solve on the device: {str(err).splitlines()[0]}", flush=True)
+            lu, piv_op, plain = lo.opLU(K), lo.opLDL(K, pivot=True), lo.opLDL(Q)
+            for k in (1, 8):
+                V, R = colmajor(n, k, dtype, 10 * n + k), colmajor(n, k, dtype, 1)
+                v, res = (V[:, 0], R[:, 0]) if k == 1 else (V, R)
+                for name, op, nbytes in (("opLU apply", lu, full), ("opLDL(pivot=True) apply", piv_op, tri2), ("unpivoted opLDL apply", plain, tri2)):
+                    mul = lambda: lo.mul(res, op, v, 1.0, 0.0)
+                    row(name, mul, reps, nbytes, launches(mul), ("a", k), k)
+                if tsolve:
+                    row("torch.linalg.ldl_solve", lambda: tsolve(V), reps, 0, 0, ("a", k), k)
+            v, res = colmajor(n, 1, dtype, 5)[:, 0], colmajor(n, 1, dtype, 6)[:, 0]
+            for name, op, nbytes in (("opLU apply (graph replay)", lu, full), ("opLDL(pivot=True) apply (graph replay)", piv_op, tri2)):
+                gr = lo.capture_mul(res, op, v, 1.0, 0.0)
+                row(name, gr.replay, reps, nbytes, 0, "g", 1)
+                del gr
+            del lu, piv_op, plain, K, Q, tsolve
+            torch.cuda.empty_cache()
+
+
+if LDLP:
+    ldlp_legs()
+    sys.exit(0)
 if "--pinv" in sys.argv:
     pinv_legs()
     sys.exit(0)

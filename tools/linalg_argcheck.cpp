@@ -1,6 +1,6 @@
 // Host-side check of the argument checks of the factorisation entry points of linalg.hip: the three factorisations of the
-// rectangular family (mxlo_geqrf, mxlo_geqp3, mxlo_cod_factor) and their six applies, mxlo_getrf / mxlo_potrf / mxlo_ldlt, and
-// one square apply per check path. Every call below is refused (null operands, bad shapes, a bad rank, overlaps, a scratch one
+// rectangular family (mxlo_geqrf, mxlo_geqp3, mxlo_cod_factor) and their six applies, mxlo_getrf / mxlo_potrf / mxlo_ldlt, one
+// square apply per check path, and mxlo_sytrf with its two applies. Every call below is refused (null operands, bad shapes, a bad rank, overlaps, a scratch one
 // double too short), or is a no-op, before anything touches a device, so the program needs no GPU. The pointers are addresses
 // inside one host buffer that is never dereferenced by the library. Calls that break two rules at once pin which refusal wins.
 // Build the host code with AddressSanitizer and UBSan and run it (from the repository root):
@@ -36,6 +36,8 @@ struct Args {
   double *M, *W, *tfac, *dinv, *W2, *tfac2, *dinv2, *scratch, *work, *res, *v;
   double *dinv_u, *d, *dg, *A2;                                       // square family: W, dinv (= dinv_l) and these
   int32_t *jpvt, *info_dev, *info, *rank_out;
+  double *e, *panel;                                                  // mxlo_sytrf: the sub-diagonal of D, the n x 65 workspace and
+  int32_t *perm;                                                      // its 2 n + ceil(n/64) + 1 words
   int64_t slen = 0;
   Args tr() const { Args a = *this; a.op = T; a.ldr = mf; a.ldv = nf; return a; }            // the valid transposed apply
   Args sq() const { Args a = *this; a.ldr = a.ldv = n; return a; }                           // the valid square apply
@@ -76,6 +78,9 @@ int32_t lu_mul(const Args &a) { return mxlo_lu_mul(a.ctx, a.dtype, a.res, a.W, a
 int32_t lu_mul_block(const Args &a) { return mxlo_lu_mul_block(a.ctx, a.dtype, a.res, a.ldr, a.W, a.ldw, a.n, a.dinv, a.dinv_u, a.jpvt, a.work, a.v, a.ldv, a.k, a.op, 1.0, 0.0); }
 int32_t ldl_mul_refine(const Args &a) { return mxlo_ldl_mul_refine(a.ctx, a.dtype, a.res, a.ldr, a.W, a.ldw, a.n, a.dinv, a.d, a.dg, a.work, a.v, a.ldv, a.k, a.steps, 1.0, 0.0); }
 int32_t lu_mul_refine(const Args &a) { return mxlo_lu_mul_refine(a.ctx, a.dtype, a.res, a.ldr, a.W, a.ldw, a.n, a.dinv, a.dinv_u, a.jpvt, a.A2, a.lda, a.work, a.v, a.ldv, a.k, a.steps, a.op, 1.0, 0.0); }
+int32_t sytrf(const Args &a) { return mxlo_sytrf(a.ctx, a.dtype, a.M, a.ldm, a.rowmajor, a.W, a.ldw, a.n, a.dinv, a.d, a.e, a.perm, a.panel, a.info_dev, a.info); }
+int32_t ldlp_mul(const Args &a) { return mxlo_ldlp_mul(a.ctx, a.dtype, a.res, a.W, a.ldw, a.n, a.dinv, a.d, a.e, a.perm, a.work, a.v, 1.0, 0.0); }
+int32_t ldlp_mul_block(const Args &a) { return mxlo_ldlp_mul_block(a.ctx, a.dtype, a.res, a.ldr, a.W, a.ldw, a.n, a.dinv, a.d, a.e, a.perm, a.work, a.v, a.ldv, a.k, 1.0, 0.0); }
 }  // namespace
 
 #define CASE(what, base, call, want, ...) expect(what, base, call, [&](Args &a) { __VA_ARGS__; }, want)
@@ -87,7 +92,7 @@ int main() {
   const int64_t geqp3_len = 2 * 64 * nf + 64 + 2 * nf + 2 * mf + 2 + 64 * 4096;
   const int64_t cod_len = 2 * (QS + 64) + (512 + 2 * 2) * 4096;              // rank 65: two block columns
   const int64_t work_len = 8 * (mf + nf + 2 * QS);
-  std::vector<double> pool(3 * n * n + mf * nf + nf * r + 8 * 4 * 4096 + nf + geqrf_len + work_len + 16 * mf + 3 * n + 4096);
+  std::vector<double> pool(3 * n * n + mf * nf + nf * r + 8 * 4 * 4096 + nf + geqrf_len + work_len + 16 * mf + 3 * n + 4096 + 66 * n + 3 * n);
   double *p = pool.data();
   Args b;
   b.ctx = &ctx;
@@ -108,6 +113,10 @@ int main() {
   b.work = p; p += work_len;
   b.res = p; p += 8 * mf;
   b.v = p; p += 8 * mf;
+  p += 3 * n + 4096 - 1;                                // the slack the pool always had; what mxlo_sytrf adds lies behind it
+  b.e = p; p += n;
+  b.panel = p; p += 65 * n;
+  b.perm = (int32_t *)p; p += n + 3;                    // 2 n + 4 + 1 words
   b.info = &info;
   b.rank_out = &rank;
   double *const M = b.M, *const W = b.W, *const W2 = b.W2, *const tfac2 = b.tfac2, *const dinv2 = b.dinv2, *const scratch = b.scratch;
@@ -459,6 +468,70 @@ int main() {
   CASE("lu_mul_refine: null snapshot", s, lu_mul_refine, EINVAL_, a.A2 = nullptr);
   CASE("lu_mul_refine: V inside the snapshot", s, lu_mul_refine, EINVAL_, a.v = b.A2 + n * n - 1);
   CASE("lu_mul_refine: k == 0, null operands", s, lu_mul_refine, OK, a.k = 0; a.A2 = nullptr; a.jpvt = nullptr);
+
+  // ---- mxlo_sytrf and its applies
+  const Args y = s;
+  CASE("sytrf: null ctx", y, sytrf, EINVAL_, a.ctx = nullptr);
+  CASE("sytrf: complex dtype", y, sytrf, EINVAL_, a.dtype = MXLO_C64);
+  CASE("sytrf: n < 0", y, sytrf, ESHAPE, a.n = -1);
+  CASE("sytrf: ldw < n", y, sytrf, ESHAPE, a.ldw = n - 1);
+  CASE("sytrf: null W", y, sytrf, EINVAL_, a.W = nullptr);
+  CASE("sytrf: null info", y, sytrf, EINVAL_, a.info = nullptr);
+  CASE("sytrf: n == 0 sets info 0", y, sytrf, OK, a.n = 0; a.W = nullptr; a.d = nullptr; a.e = nullptr; a.perm = nullptr);
+  CASE("sytrf: null block inverses", y, sytrf, EINVAL_, a.dinv = nullptr);
+  CASE("sytrf: null d", y, sytrf, EINVAL_, a.d = nullptr);
+  CASE("sytrf: null e", y, sytrf, EINVAL_, a.e = nullptr);
+  CASE("sytrf: null perm", y, sytrf, EINVAL_, a.perm = nullptr);
+  CASE("sytrf: null panel workspace", y, sytrf, EINVAL_, a.panel = nullptr);
+  CASE("sytrf: null info word", y, sytrf, EINVAL_, a.info_dev = nullptr);
+  CASE("sytrf: n too large", y, sytrf, ESHAPE, a.n = a.ldw = a.ldm = 1LL << 31);
+  CASE("sytrf: ldm < n", y, sytrf, ESHAPE, a.ldm = n - 1);
+  CASE("sytrf: no M, factored in place", y, sytrf, EINVAL_, a.M = nullptr; a.e = W);
+  CASE("sytrf: W is M", y, sytrf, EINVAL_, a.W = M);
+  CASE("sytrf: W overlaps M, row-major", y, sytrf, EINVAL_, a.rowmajor = 1; a.W = M + n * n - 1);
+  CASE("sytrf: d inside W", y, sytrf, EINVAL_, a.d = W + 5);
+  CASE("sytrf: e ends inside the block inverses", y, sytrf, EINVAL_, a.e = dinv - n + 1);
+  CASE("sytrf: e is d", y, sytrf, EINVAL_, a.e = y.d);
+  CASE("sytrf: perm's panel starts inside d", y, sytrf, EINVAL_, a.perm = (int32_t *)y.d - 2 * n - 1);
+  CASE("sytrf: perm inside W", y, sytrf, EINVAL_, a.perm = (int32_t *)(W + 9));
+  CASE("sytrf: panel workspace's last element inside W, no M", y, sytrf, EINVAL_, a.M = nullptr; a.panel = W - 65 * n + 1);
+  CASE("sytrf: panel workspace inside M", y, sytrf, EINVAL_, a.panel = M + 3);
+  CASE("sytrf: info word inside M", y, sytrf, EINVAL_, a.info_dev = (int32_t *)(M + 3));
+  ctx.capturing = true;
+  CASE("sytrf: during a capture", y, sytrf, ESTATE, (void)a);
+  CASE("sytrf: during a capture, float, no M", y, sytrf, ESTATE, a.dtype = F32; a.M = nullptr);
+  CASE("sytrf: overlap + capture", y, sytrf, EINVAL_, a.d = W);
+  ctx.capturing = false;
+  CASE("sytrf: bad dtype + bad shape", y, sytrf, EINVAL_, a.dtype = 9; a.n = -1);
+  CASE("sytrf: bad shape + null info", y, sytrf, ESHAPE, a.ldw = 1; a.info = nullptr);
+  CASE("sytrf: null storage + too large", y, sytrf, EINVAL_, a.e = nullptr; a.n = a.ldw = a.ldm = 1LL << 31);
+  CASE("sytrf: bad ldm + overlap leaves info 0", y, sytrf, ESHAPE, a.ldm = 1; a.e = y.d);
+  CASE("ldlp_mul: null ctx", y, ldlp_mul, EINVAL_, a.ctx = nullptr);
+  CASE("ldlp_mul: complex dtype", y, ldlp_mul, EINVAL_, a.dtype = MXLO_C64);
+  CASE("ldlp_mul: ld < n", y, ldlp_mul, ESHAPE, a.ldw = n - 1);
+  CASE("ldlp_mul: n == 0, null operands", y, ldlp_mul, OK, a.n = 0; a.d = nullptr; a.e = nullptr; a.perm = nullptr);
+  CASE("ldlp_mul: null res", y, ldlp_mul, EINVAL_, a.res = nullptr);
+  CASE("ldlp_mul: null d", y, ldlp_mul, EINVAL_, a.d = nullptr);
+  CASE("ldlp_mul: null e", y, ldlp_mul, EINVAL_, a.e = nullptr);
+  CASE("ldlp_mul: null perm", y, ldlp_mul, EINVAL_, a.perm = nullptr);
+  CASE("ldlp_mul: null work", y, ldlp_mul, EINVAL_, a.work = nullptr);
+  CASE("ldlp_mul: res overlaps v", y, ldlp_mul, EINVAL_, a.res = v + n - 1);
+  CASE("ldlp_mul: res inside e", y, ldlp_mul, EINVAL_, a.res = y.e + n - 1);
+  CASE("ldlp_mul: v inside d, float", y, ldlp_mul, EINVAL_, a.dtype = F32; a.v = (double *)((float *)y.d - n + 1));
+  CASE("ldlp_mul: res ends at the permutation's first word", y, ldlp_mul, EINVAL_, a.res = (double *)y.perm - n + 1);
+  CASE("ldlp_mul: res behind the permutation's n words", y, ldlp_mul, EINVAL_, a.res = (double *)y.perm + n / 2 - 1);
+  CASE("ldlp_mul: bad shape + null e", y, ldlp_mul, ESHAPE, a.ldw = 1; a.e = nullptr);
+  CASE("ldlp_mul_block: k == 0, null operands", y, ldlp_mul_block, OK, a.k = 0; a.d = nullptr; a.e = nullptr; a.perm = nullptr);
+  CASE("ldlp_mul_block: k < 0", y, ldlp_mul_block, ESHAPE, a.k = -1);
+  CASE("ldlp_mul_block: ldr < n", y, ldlp_mul_block, ESHAPE, a.ldr = n - 1);
+  CASE("ldlp_mul_block: ldv < n", y, ldlp_mul_block, ESHAPE, a.ldv = n - 1);
+  CASE("ldlp_mul_block: null e", y, ldlp_mul_block, EINVAL_, a.e = nullptr);
+  CASE("ldlp_mul_block: null perm", y, ldlp_mul_block, EINVAL_, a.perm = nullptr);
+  CASE("ldlp_mul_block: res is V in another leading dimension", y, ldlp_mul_block, EINVAL_, a.res = v; a.ldr = n + 1; a.k = 7);
+  CASE("ldlp_mul_block: last column of V inside e", y, ldlp_mul_block, EINVAL_, a.v = y.e - 7 * n);
+  CASE("ldlp_mul_block: last column of res inside L", y, ldlp_mul_block, EINVAL_, a.res = W - 7 * n);
+  CASE("ldlp_mul_block: V inside the work matrix's eighth column", y, ldlp_mul_block, EINVAL_, a.v = work + 8 * n - 1);
+  CASE("ldlp_mul_block: bad ldv + null perm", y, ldlp_mul_block, ESHAPE, a.ldv = 1; a.perm = nullptr);
 
   std::printf("%d calls, %d unexpected\n", lines, failures);
   return failures ? 1 : 0;
