@@ -146,7 +146,11 @@ int32_t mxlo_ctx_info(mxlo_ctx *ctx, int64_t info[4]);
  *   "alias_guard" (1; 0/1): res overlapping v is staged or leaves the one-launch kron, see Conventions; 0: TEST HOOK,
  *     overlapping operands reach the kernels unguarded
  *  opHouseholder
- *   "house_fused" (1; any value, stored as value != 0): the single-launch form (dot, grid exchange, update)
+ *   "house_fused" (1; any value, stored as value != 0): the forms whose workgroups wait for each other — the
+ *     single-launch form (dot, grid exchange, update) and, at sizes where the dot pass streams from HBM (its footprint
+ *     >= "nt_min_bytes", n > "house_inline_n"), the dot launch that keeps its last rounds of h and v in registers and
+ *     LDS, exchanges the partial sums the same way and updates that tail itself (the update launch gets a shorter n;
+ *     results are bit-identical to the three-launch path)
  *   "house_fused_per_cu" (2; 1..2): workgroups per CU that launch may use: 2 takes vectors up to 2^22 doubles, 1 up to 2^21
  *   "house_reverse" (1; any value, stored as value != 0): the update phase walks the vectors back to front
  *   "house_inline_n" (2^23; >= 0): two-pass form up to this n: the update pass adds up the dots pass's partial sums
@@ -204,7 +208,9 @@ int32_t mxlo_ctx_info(mxlo_ctx *ctx, int64_t info[4]);
  * single-launch apply wait for each other, so a launch must be resident as a whole; two of the largest Householder launches
  * (256 workgroups of 179-209 VGPRs: 2^20 < n <= 2^21 doubles; four of those up to 2^20 — since round 6 a launch for 2^21 < n <= 2^22 doubles takes the WHOLE chip itself, two workgroups per CU, "house_fused_per_cu"; and the persistent quasi-Newton apply with LDS parking, "qn_persist_lds", owns every CU's LDS: ONE of either at a time) or two quasi-Newton ones (up to 256
  * workgroups of 166-224 VGPRs since round 4; twelve of the 64-workgroup launches of short vectors) fit on the chip at once, beyond that two launches could each be partly resident and wait for each other —
- * until the bounded wait below ends them. (They are never used with an all-reduce hook installed.)
+ * until the bounded wait below ends them. The Householder dot launch that keeps its last rounds on chip (HBM sizes) is one
+ * workgroup per CU with the whole register file and 128 KiB of LDS: it owns the chip like the 2^22 launch, ONE at a time, with
+ * the same bounded wait and fault word. (None of these forms is used with an all-reduce hook installed.)
  * That wait is BOUNDED: "fused_timeout_ms" (default 2000, 1..600000) is how long a workgroup polls for a peer's partial before
  * it gives up, stores NaN and raises the ctx fault word (pinned host memory). The host reads that word, without
  * synchronising, before every single-launch apply and at the end of mxlo_ctx_sync: the call then returns MXLO_EHIP naming the

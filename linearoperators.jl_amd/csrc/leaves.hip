@@ -3,7 +3,7 @@
 // opRestriction / opExtension.
 #include "common.h"
 #include "stream_kernels.h"
-
+#include "house_keep.h"
 using namespace mxlo;
 
 #define CHECK_COMMON(name)                                                                       \
@@ -398,7 +398,7 @@ static int32_t householder_t(mxlo_ctx *ctx, T *res, const T *h, const T *v, int6
     });
   }
   double *dot = ctx->scalars;  // slot 0
-  MXLO_TRY(panel_dots<T>(ctx, cols, 1, v, n, dot));  // phase A (+ all-reduce hook)
+  MXLO_TRY(householder_dots_t<T>(ctx, res, h, v, &n, alpha, beta, flags, dot));  // phase A (+ all-reduce hook); HBM sizes: it updates the tail it kept on chip and shortens n (house_keep.h)
   return householder_apply_t<T>(ctx, res, h, v, n, alpha, beta, flags, dot);  // phase B
 }
 
