@@ -137,7 +137,9 @@ int32_t mxlo_ctx_info(mxlo_ctx *ctx, int64_t info[4]);
  * The keys, as  "key" (default; accepted values): what it selects
  *  streaming kernels and reductions
  *   "blocks_per_cu" (0; 0..64): 0 = one chunk per workgroup, k = a persistent grid of k workgroups per CU
- *   "nt_min_bytes" (256 MiB; >= 0): streamed footprint from which nontemporal accesses are used
+ *   "nt_min_bytes" (256 MiB; >= 0): streamed footprint from which nontemporal accesses are used; it stands for the
+ *     size of the last-level cache, and the opHouseholder form that keeps rounds on chip (below) leaves up to 14/16 of
+ *     it to chunks of h that it loads with the default policy, so that they stay cached from one apply to the next
  *   "red_blocks_per_cu" (4; >= 1): workgroups per CU of the reduction kernels
  *   "fuse_finalize" (1; 0/1): reductions of <= 4 columns are finalized by the last-arriving workgroup of the dots kernel
  *   "dots_max_nc" (20; 1..20): columns per dots launch

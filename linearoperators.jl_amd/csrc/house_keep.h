@@ -25,13 +25,31 @@ namespace mxlo {
 constexpr int kHouseKeepKR = 14;
 constexpr int kHouseKeepKL = 4;
 constexpr int kHouseKeepUnroll = 4;   // = launch_dots' UNROLL for one column
+static_assert(kHouseKeepUnroll == kStreamUnroll, "the dot launch and the update launch count the same chunks");
+
+// The slice of h that stays in the Infinity Cache between applies (house_keep_plan.h: house_resident_q / _chunk): its
+// target is this many sixteenths of Tune::nt_min_bytes, the key that stands for the cache's size. 0 switches it off.
+// profiles/house_resident.md, house_fused 1 against 0 in one process at n = 1e8 f64 (the parent: 4.3-4.5 %): 0 4.2-4.9 %,
+// 4 4.9-5.1 %, 8 6.2-6.5 %, 10 7.4 %, 12 8.5-8.8 %, 14 8.7-8.8 % (12 and 14 are the same 4 sixteenths = 200 MB there);
+// 14 is also the fastest at n = 5e7 f64 and 1e8 f32, where 12 lands on 8 sixteenths — every other diagonal — and gains nothing.
+constexpr int kHouseResidentNum = 14;
+static_assert(kHouseResidentNum >= 0 && kHouseResidentNum <= 16);
+// The two sides of a per-chunk policy choice load the same addresses and differ only in the nontemporal hint, which is
+// metadata: when the compiler merges the "identical" loads of the two sides it drops the hint and EVERY load of h takes
+// the default policy (seen in the ISA). A side-effecting marker that differs between the sides, in front of and behind
+// the loads, keeps them two straight lines; it emits a comment, no instruction and no wait.
+#define MXLO_POLICY_SIDE(tag) asm volatile("; h loads: " tag ::: "memory")
+struct HouseResident {
+  int q = 0;      // sixteenths of h's chunks loaded with the default policy; 0: every load nontemporal, as before
+  int grid = 0;   // workgroups of the dot launch: chunk c is round c / grid, workgroup c % grid
+};
 
 template <typename T, typename CA, typename CB, bool BETA0, int KR, int KL>
 __global__ void __launch_bounds__(kBlock)
 householder_dots_keep_kernel(T *__restrict__ res, const T *__restrict__ h, const T *__restrict__ v, int64_t head,
                              int64_t n, CA alpha, CB beta, HouseKeepPlan pl, unsigned long long *__restrict__ slots,
                              unsigned long long ticks, unsigned *__restrict__ fault, int drop,
-                             double *__restrict__ dot_out) {
+                             double *__restrict__ dot_out, int rq) {
   constexpr int VEC = Vec16<T>::N, U = kHouseKeepUnroll;
   using V = typename Vec16<T>::type;
   constexpr int64_t CHUNK = (int64_t)kBlock * U;
@@ -49,10 +67,23 @@ householder_dots_keep_kernel(T *__restrict__ res, const T *__restrict__ h, const
   double acc = 0.0;
   auto load4 = [&](int64_t round, V (&a)[U], V (&x)[U]) {
     const int64_t base = (round * G + b) * CHUNK + tid;
+    // a resident chunk of h takes the default policy: one wave-uniform choice per chunk, each side a straight line of loads
+    if (house_resident_diag((int)((round + b) & 15), rq)) {
+      MXLO_POLICY_SIDE("resident");
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      x[u] = __builtin_nontemporal_load(xv + base + (int64_t)u * kBlock);
-      a[u] = __builtin_nontemporal_load(hv + base + (int64_t)u * kBlock);
+      for (int u = 0; u < U; ++u) {
+        x[u] = __builtin_nontemporal_load(xv + base + (int64_t)u * kBlock);
+        a[u] = hv[base + (int64_t)u * kBlock];
+      }
+      MXLO_POLICY_SIDE("resident, issued");
+    } else {
+      MXLO_POLICY_SIDE("streamed");
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        x[u] = __builtin_nontemporal_load(xv + base + (int64_t)u * kBlock);
+        a[u] = __builtin_nontemporal_load(hv + base + (int64_t)u * kBlock);
+      }
+      MXLO_POLICY_SIDE("streamed, issued");
     }
   };
   auto fma4 = [&](const V (&a)[U], const V (&x)[U]) {
@@ -180,9 +211,10 @@ householder_dots_keep_kernel(T *__restrict__ res, const T *__restrict__ h, const
 
 // The dot of a Householder apply into `dot`. When the kept form engages, it has also updated res[*n_left, n) and
 // *n_left is the prefix the update launch still has to do; otherwise panel_dots runs as before and *n_left stays n.
+// *rs: the resident slice of h the kept form loaded with the default policy (q = 0: none), for the update launch.
 template <typename T>
 static int32_t householder_dots_t(mxlo_ctx *ctx, T *res, const T *h, const T *v, int64_t *n_left, double alpha,
-                                  double beta, int32_t flags, double *dot) {
+                                  double beta, int32_t flags, double *dot, HouseResident *rs) {
   constexpr int VEC = Vec16<T>::N, KR = kHouseKeepKR, KL = kHouseKeepKL;
   constexpr int64_t CHUNK = (int64_t)kBlock * kHouseKeepUnroll;
   constexpr size_t kLds = (size_t)2 * KL * CHUNK * 16;
@@ -202,6 +234,7 @@ static int32_t householder_dots_t(mxlo_ctx *ctx, T *res, const T *h, const T *v,
     keep = grid == ctx->num_cu && grid <= kFusedSlots && pl.ok;
   }
   if (!keep) return panel_dots<T>(ctx, cols, 1, v, n, dot);   // (+ all-reduce hook)
+  const int rq = house_resident_q((int64_t)sizeof(T) * n, ctx->tune.nt_min_bytes / 16 * kHouseResidentNum);
   bool launched = false;
   MXLO_TRY((dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
     constexpr auto kernel = householder_dots_keep_kernel<T, CA, CB, B0, KR, KL>;
@@ -215,14 +248,89 @@ static int32_t householder_dots_t(mxlo_ctx *ctx, T *res, const T *h, const T *v,
     }
     if (st != 1 || !coresident<kernel>(ctx, grid, kLds)) return MXLO_OK;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), kLds, ctx->stream, res, h, v, head, n, (CA)alpha, (CB)beta, pl,
-                       ctx->xslots, fused_timeout_ticks(ctx), ctx->fault_dev, ctx->tune.fused_debug_drop, dot);
+                       ctx->xslots, fused_timeout_ticks(ctx), ctx->fault_dev, ctx->tune.fused_debug_drop, dot, rq);
     MXLO_LAUNCH_CHECK();
     launched = true;
     return MXLO_OK;
   })));
   if (!launched) return panel_dots<T>(ctx, cols, 1, v, n, dot);
   *n_left = pl.prefix;
+  *rs = HouseResident{rq, grid};
   return MXLO_OK;
+}
+
+// The update launch over the prefix the kept form left, when that form loaded a resident slice of h (rs.q > 0): it is
+// map_kernel<T, VEC, kStreamUnroll, 2, !BETA0, REVERSE, NT, HouseholderOp> — same chunks, same order, same arithmetic
+// — with the h loads of the resident chunks on the default policy. The prefix is the scalar head and whole chunks.
+template <typename T, typename CA, typename CB, bool BETA0, bool REVERSE, bool NT>
+__global__ void __launch_bounds__(kBlock)
+householder_update_resident_kernel(T *__restrict__ res, const T *__restrict__ h, const T *__restrict__ v, int64_t head,
+                                   int64_t nchunks, int64_t dots_grid, int rq, HouseholderOp<T, CA, CB, BETA0> op) {
+  constexpr int VEC = Vec16<T>::N, U = kStreamUnroll;
+  using V = typename Vec16<T>::type;
+  constexpr int64_t CHUNK = (int64_t)kBlock * U;
+  op.init();
+  const int tid = threadIdx.x;
+  V *rv = reinterpret_cast<V *>(res + head);
+  const V *hv = reinterpret_cast<const V *>(h + head), *xv = reinterpret_cast<const V *>(v + head);
+  for (int64_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+    const int64_t c = REVERSE ? (nchunks - 1 - ch) : ch;
+    const int64_t base = c * CHUNK + tid;
+    V a[U], x[U], r[U];
+    if (house_resident_chunk(c, dots_grid, rq)) {   // wave-uniform; each side a straight line of loads
+      MXLO_POLICY_SIDE("resident");
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        a[u] = hv[base + (int64_t)u * kBlock];
+        x[u] = ldg<NT>(xv + base + (int64_t)u * kBlock);
+        if constexpr (!BETA0) r[u] = ldg<NT>(rv + base + (int64_t)u * kBlock);
+      }
+      MXLO_POLICY_SIDE("resident, issued");
+    } else {
+      MXLO_POLICY_SIDE("streamed");
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        a[u] = ldg<NT>(hv + base + (int64_t)u * kBlock);
+        x[u] = ldg<NT>(xv + base + (int64_t)u * kBlock);
+        if constexpr (!BETA0) r[u] = ldg<NT>(rv + base + (int64_t)u * kBlock);
+      }
+      MXLO_POLICY_SIDE("streamed, issued");
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      V o;
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) o[k] = op(a[u][k], x[u][k], BETA0 ? T(0) : r[u][k]);
+      stg<NT>(rv + base + (int64_t)u * kBlock, o);
+    }
+  }
+  if (blockIdx.x == gridDim.x - 1 && tid < head) res[tid] = op(h[tid], v[tid], BETA0 ? T(0) : res[tid]);   // scalar head
+}
+
+template <typename T>
+static int32_t householder_apply_resident_t(mxlo_ctx *ctx, T *res, const T *h, const T *v, int64_t n, double alpha,
+                                            double beta, int32_t flags, const double *dot, HouseResident rs) {
+  constexpr int VEC = Vec16<T>::N;
+  constexpr int64_t CHUNK = (int64_t)kBlock * kStreamUnroll;
+  const int64_t head = common_head<T>({res, h, v}), nchunks = (n - head) / VEC / CHUNK;
+  MXLO_REQUIRE(head >= 0 && rs.grid > 0 && head + nchunks * CHUNK * VEC == n, MXLO_ESTATE,
+               "householder: the prefix of the kept form is not the scalar head and whole chunks");
+  const bool rev = ctx->tune.house_reverse != 0;
+  int64_t g = nchunks;                                   // = launch_map's grid and nontemporal rule
+  if (ctx->tune.blocks_per_cu > 0 && g > (int64_t)ctx->num_cu * ctx->tune.blocks_per_cu) g = (int64_t)ctx->num_cu * ctx->tune.blocks_per_cu;
+  const int grid = (int)(g > 0x7fffffffLL ? 0x7fffffffLL : (g < 1 ? 1 : g));
+  return dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
+    HouseholderOp<T, CA, CB, B0> op{(CA)alpha, (CB)beta, dot, T(0)};
+    const bool nt = (int64_t)sizeof(T) * n * (B0 ? 3 : 4) >= ctx->tune.nt_min_bytes;
+    auto go = [&]<bool REV, bool NT>() {
+      hipLaunchKernelGGL((householder_update_resident_kernel<T, CA, CB, B0, REV, NT>), dim3(grid), dim3(kBlock), 0,
+                         ctx->stream, res, h, v, head, nchunks, (int64_t)rs.grid, rs.q, op);
+    };
+    if (rev) nt ? go.template operator()<true, true>() : go.template operator()<true, false>();
+    else nt ? go.template operator()<false, true>() : go.template operator()<false, false>();
+    MXLO_LAUNCH_CHECK();
+    return MXLO_OK;
+  });
 }
 
 }  // namespace mxlo

@@ -39,4 +39,26 @@ inline HouseKeepPlan house_keep_plan(int64_t n, int64_t head, int vec, int64_t g
   return p;
 }
 
+// ---- a slice of h that stays in the Infinity Cache from one apply to the next -----------------------------------------
+// h is the operator's own vector: every apply reads the same bytes twice (dot launch, update launch). Chunks of h marked
+// "resident" are loaded with the default cache policy in both launches, every other access stays nontemporal, so once the
+// slice is warm neither read of it goes to HBM. Chunks are the CHUNK-vector chunks both launches already count from
+// `head`; chunk c is workgroup c % grid's chunk of round c / grid of the dot launch.
+
+// Sixteenths of the chunks of h to keep resident for a target of `cache_bytes`: 0 for no target, 16 when all of h fits.
+constexpr int house_resident_q(int64_t h_bytes, int64_t cache_bytes) {
+  if (cache_bytes <= 0 || h_bytes < 0) return 0;
+  if (h_bytes <= cache_bytes) return 16;
+  return (int)(cache_bytes / ((h_bytes + 15) / 16));   // q/16 of h is at most the target (+ rounding of h_bytes/16)
+}
+
+// Diagonal in (round, workgroup), t = (round + workgroup) mod 16, and q of the 16 values of t spread evenly (the steps of
+// floor(t q / 16)): over any 16 consecutive rounds every workgroup of the statically partitioned dot launch has exactly q
+// resident chunks, and any `grid` consecutive chunks — one round — hold floor or ceil(grid q / 16) of them, so hits and
+// misses are in flight together in both launches.
+constexpr bool house_resident_diag(int t, int q) { return (t * q) % 16 >= 16 - q; }   // t in [0, 16), q in [0, 16]
+constexpr bool house_resident_chunk(int64_t c, int64_t grid, int q) {
+  return house_resident_diag((int)(((c / grid) + (c % grid)) % 16), q);
+}
+
 }  // namespace mxlo

@@ -398,8 +398,8 @@ static int32_t householder_t(mxlo_ctx *ctx, T *res, const T *h, const T *v, int6
     });
   }
   double *dot = ctx->scalars;  // slot 0
-  MXLO_TRY(householder_dots_t<T>(ctx, res, h, v, &n, alpha, beta, flags, dot));  // phase A (+ all-reduce hook); HBM sizes: it updates the tail it kept on chip and shortens n (house_keep.h)
-  return householder_apply_t<T>(ctx, res, h, v, n, alpha, beta, flags, dot);  // phase B
+  HouseResident rs; MXLO_TRY(householder_dots_t<T>(ctx, res, h, v, &n, alpha, beta, flags, dot, &rs));  // phase A (+ all-reduce hook); HBM sizes: it updates the tail it kept on chip and shortens n (house_keep.h)
+  return rs.q > 0 ? householder_apply_resident_t<T>(ctx, res, h, v, n, alpha, beta, flags, dot, rs) : householder_apply_t<T>(ctx, res, h, v, n, alpha, beta, flags, dot);  // phase B; resident slice of h: house_keep.h
 }
 
 MXLO_API int32_t mxlo_dot(mxlo_ctx *ctx, int32_t dtype, const void *a, const void *b, int64_t n,
