@@ -64,21 +64,13 @@ MXLO_API int32_t mxlo_ctx_create(int32_t device_id, void *stream, mxlo_ctx **out
   }
   MXLO_HIP(hipMemsetAsync(ctx->scalars, 0, sizeof(double) * kScalarSlots, ctx->stream));
   MXLO_HIP(hipMemsetAsync(ctx->ticket, 0, 64, ctx->stream));
-  {  // every exchange slot empty, epoch 0
-    std::vector<unsigned long long> init(2 * kFusedSlots + 8, kSlotEmpty);
-    for (int i = 0; i < 8; ++i) init[2 * kFusedSlots + i] = 0;
-    MXLO_HIP(hipMemcpy(ctx->xslots, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
-  }
-  {  // the same for the single-launch quasi-Newton apply: 2 sets of 40 columns x 256 workgroups
-    constexpr size_t kQ = 2 * kQnfSlots + 8;
-    if (hipMalloc((void **)&ctx->qslots, sizeof(unsigned long long) * kQ) == hipSuccess) {
-      std::vector<unsigned long long> init(kQ, kSlotEmpty);
-      for (int i = 0; i < 8; ++i) init[kQ - 8 + i] = 0;
-      MXLO_HIP(hipMemcpy(ctx->qslots, init.data(), kQ * sizeof(unsigned long long), hipMemcpyHostToDevice));
-    } else {
-      ctx->qslots = nullptr;     // the four-launch apply is used instead
-      (void)hipGetLastError();
-    }
+  MXLO_HIP(exchange_slots_init(ctx->xslots, kFusedSlots));   // every exchange slot empty, epoch 0
+  // the same for the single-launch quasi-Newton apply: 2 sets of 40 columns x 256 workgroups
+  if (hipMalloc((void **)&ctx->qslots, sizeof(unsigned long long) * (2 * kQnfSlots + 8)) == hipSuccess) {
+    MXLO_HIP(exchange_slots_init(ctx->qslots, kQnfSlots));
+  } else {
+    ctx->qslots = nullptr;     // the four-launch apply is used instead
+    (void)hipGetLastError();
   }
   {  // fault word of the single-launch kernels: pinned + device-mapped, so that the host reads it without a sync
     void *hp = nullptr, *dp = nullptr;
@@ -100,17 +92,8 @@ MXLO_API int32_t mxlo_ctx_create(int32_t device_id, void *stream, mxlo_ctx **out
 
 namespace mxlo {
 static int32_t rearm_fused_slots(mxlo_ctx *ctx) {
-  if (ctx->xslots) {
-    std::vector<unsigned long long> init(2 * kFusedSlots + 8, kSlotEmpty);
-    for (int i = 0; i < 8; ++i) init[2 * kFusedSlots + i] = 0;
-    MXLO_HIP(hipMemcpy(ctx->xslots, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
-  }
-  if (ctx->qslots) {
-    constexpr size_t kQ = 2 * kQnfSlots + 8;
-    std::vector<unsigned long long> init(kQ, kSlotEmpty);
-    for (int i = 0; i < 8; ++i) init[kQ - 8 + i] = 0;
-    MXLO_HIP(hipMemcpy(ctx->qslots, init.data(), kQ * sizeof(unsigned long long), hipMemcpyHostToDevice));
-  }
+  if (ctx->xslots) MXLO_HIP(exchange_slots_init(ctx->xslots, kFusedSlots));
+  if (ctx->qslots) MXLO_HIP(exchange_slots_init(ctx->qslots, kQnfSlots));
   return MXLO_OK;
 }
 

@@ -26,7 +26,6 @@ constexpr int kMaxRedCols = 128;     // columns a single reduction call may prod
 constexpr int kQnfMaxCols = 40, kQnfMaxGrid = 256;   // single-launch quasi-Newton apply: panel columns x workgroups of its exchange
 constexpr int kQnfSlots = kQnfMaxCols * kQnfMaxGrid;
 constexpr int kFusedSlots = 512;     // workgroups of a single-launch (grid-exchange) kernel: all co-resident (round 6: up to two per CU)
-constexpr unsigned long long kSlotEmpty = 0x7FF8DEADBEEF0001ull;   // a NaN payload no arithmetic produces (partials are canonicalised)
 constexpr int kMaxRedBlocks = 4096;  // partial slots per column in the workspace
 constexpr int kScalarSlots = 8192;   // doubles in the device scalar buffer
 
@@ -160,6 +159,8 @@ struct mxlo_ctx {
   mxlo::Tune tune;
 };
 
+#include "grid_exchange.h"   // (behind the counting macros above: its host call is a counted hipMemcpy)
+
 namespace mxlo {
 
 // Every entry point that allocates or launches runs on the device its ctx was created for, whatever the calling
@@ -193,40 +194,11 @@ inline bool bytes_overlap(const void *a, int64_t na, const void *b, int64_t nb) 
 int32_t stage_alias(mxlo_ctx *ctx, const void *res, int64_t res_bytes, const void **v, int64_t v_bytes, bool same_ok,
                     const char *what);   // api_ctx.hip
 
-// ---- single-launch (grid-exchange) kernels: bounded wait + fault flag -----------------------------------------------
-// The workgroups of householder_fused_kernel / qn_apply_fused_kernel wait for each other's partials, so the whole grid
-// must be resident at once. The launch sites check that against the occupancy of the kernel (coresident()); what no
-// host-side check can see — other processes occupying the CUs, CU masking, a launch killed half-way that left the
-// slots inconsistent — is caught by the wait itself: a lane that has polled one slot for longer than
-// `fused_timeout_ms` raises the ctx fault word (pinned host memory, system-scope store) and continues with a NaN, so
-// the kernel ENDS with NaN results instead of hanging the GPU. The host looks at the word (a plain read of pinned
-// memory, no synchronisation) before every single-launch apply and inside mxlo_ctx_sync: fused_fault_check() then
-// re-arms the slots, switches the single-launch forms of the ctx off and returns MXLO_EHIP naming what happened.
-constexpr unsigned kFaultHouseholder = 1u, kFaultQn = 2u, kFaultHermitian = 4u, kFaultKron = 8u;
-constexpr unsigned long long kCanonicalNaN = 0x7FF8000000000000ull;
+// ---- single-launch (grid-exchange) kernels: the exchange, its bounded wait and the fault codes are grid_exchange.h ------
 int32_t fused_fault_check(mxlo_ctx *ctx);           // api_ctx.hip
 inline unsigned long long fused_timeout_ticks(const mxlo_ctx *ctx) {   // wall_clock64() ticks: the device's constant-rate clock
   return (unsigned long long)ctx->tune.fused_timeout_ms * (unsigned long long)ctx->wall_clock_khz;
 }
-#if defined(__HIPCC__)
-__device__ __forceinline__ unsigned long long poll_slot(const unsigned long long *slot, unsigned long long ticks,
-                                                        unsigned *fault, unsigned code) {
-  unsigned long long bits, t0 = 0;
-  unsigned it = 0;
-  while ((bits = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == kSlotEmpty) {
-    __builtin_amdgcn_s_sleep(1);
-    if ((++it & 255u) == 0) {                       // the clock is read once per 256 polls (each poll is a memory round trip)
-      const unsigned long long now = (unsigned long long)wall_clock64();
-      if (t0 == 0) t0 = now;
-      else if (now - t0 > ticks) {
-        __hip_atomic_store(fault, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        return kCanonicalNaN;
-      }
-    }
-  }
-  return bits;
-}
-#endif
 // true when `grid` workgroups of `kernel` (BLOCK threads, `lds_worst` bytes of dynamic LDS) fit on the device at once.
 // Evaluated once per kernel instantiation and device (the occupancy query costs microseconds) — so `lds_worst` must be
 // the LARGEST dynamic LDS size the kernel is ever launched with, not the size of the launch at hand: the cached answer
@@ -345,6 +317,14 @@ __device__ __forceinline__ double wave_sum(double v) {
   v += dpp_shift_or_zero<0x101, 0xf>(v);   // row_shl:1
 #endif
   return v;
+}
+// Sum over a workgroup of kBlock lanes, in EVERY lane: wave_sum, then the four wave sums as (l0 + l1) + (l2 + l3)
+// through `lds`. Two uses of one `lds` need a barrier between them.
+__device__ __forceinline__ double block_sum4(double v, double (&lds)[kBlock / kWave]) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (lds[0] + lds[1]) + (lds[2] + lds[3]);
 }
 
 // ---- halving butterfly steps without LDS ---------------------------------------------------------------------------

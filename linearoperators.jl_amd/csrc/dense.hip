@@ -1136,9 +1136,7 @@ __host__ __device__ __forceinline__ int64_t herm_col_base(int64_t Gc, int64_t ng
 // agent-scope stores (an empty slot is a NaN payload no arithmetic produces; NaN partials are canonicalised), no fence.
 __device__ __forceinline__ void herm_put(double *p, double v, bool slot) {
   if (slot) {
-    unsigned long long bits = (unsigned long long)__double_as_longlong(v);
-    if (v != v) bits = kCanonicalNaN;
-    __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), slot_bits(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   } else {
     *p = v;
   }

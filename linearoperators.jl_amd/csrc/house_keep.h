@@ -4,7 +4,7 @@
 // that re-reads h and v (24 B/elt). The dot pass runs ONE workgroup per CU with one wave per SIMD: each lane may use
 // the whole 512-register budget and the CU's 160 KiB of LDS are idle. Here every workgroup keeps the h and v vectors
 // of its last KL + KR grid-stride rounds (KL in LDS, KR in registers), the workgroups exchange their partial sums as
-// the single-launch form does (householder_fused_kernel: fence-free slots, bounded wait), and each one updates what it
+// the single-launch form does (GridExchange, grid_exchange.h, on the same slots), and each one updates what it
 // kept. Those rounds are one contiguous tail of the vector (house_keep_plan.h), so the update launch simply gets a
 // shorter n: 40 - 16 kept/n bytes per element, and no finalize launch.
 //
@@ -56,11 +56,8 @@ householder_dots_keep_kernel(T *__restrict__ res, const T *__restrict__ h, const
   extern __shared__ __attribute__((aligned(16))) unsigned char keep_lds[];   // [2][KL][U][kBlock] vectors: h, then v
   V *lh = reinterpret_cast<V *>(keep_lds), *lx = lh + (int64_t)KL * CHUNK;
   const int tid = threadIdx.x, G = (int)gridDim.x, b = (int)blockIdx.x;
-  unsigned long long *epoch = slots + 2 * kFusedSlots;
-  const unsigned e = (unsigned)__hip_atomic_load(epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u;
-  unsigned long long *mine = slots + e * kFusedSlots, *other = slots + (1u - e) * kFusedSlots;
-  for (int i = b + tid * G; i < kFusedSlots; i += G * kBlock)          // re-arm the other set for the next launch
-    __hip_atomic_store(other + i, kSlotEmpty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  GridExchange X;
+  X.begin<kBlock>(slots, kFusedSlots);
 
   const V *hv = reinterpret_cast<const V *>(h + head), *xv = reinterpret_cast<const V *>(v + head);
   V *rv = reinterpret_cast<V *>(res + head);
@@ -136,28 +133,15 @@ householder_dots_keep_kernel(T *__restrict__ res, const T *__restrict__ h, const
   }
 
   __shared__ double lds[kBlock / kWave];
-  const int wave = tid >> 6, lane = tid & 63;
-  acc = wave_sum(acc);
-  if (lane == 0) lds[wave] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    const double s = (lds[0] + lds[1]) + (lds[2] + lds[3]);
-    unsigned long long bits = (unsigned long long)__double_as_longlong(s);
-    if (s != s) bits = kCanonicalNaN;                                  // canonical NaN: never the empty marker
-    if (b != drop) __hip_atomic_store(mine + b, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  // every workgroup waits for all G partials (bounded: poll_slot) and adds them up in finalize_kernel's order
+  const double s = block_sum4(acc, lds);
+  if (tid == 0) X.publish(b, s, b == drop);
+  // every workgroup waits for all G partials and adds them up in finalize_kernel's order (0 + slot t + slot t + 256 ..)
   double p = 0.0;
-  for (int i = tid; i < G; i += kBlock) p += __longlong_as_double((long long)poll_slot(mine + i, ticks, fault, kFaultHouseholder));
-  p = wave_sum(p);
+  for (int i = tid; i < G; i += kBlock) p += X.wait(i, ticks, fault, kFaultHouseholder);
   __syncthreads();                                                     // lds reuse
-  if (lane == 0) lds[wave] = p;
-  __syncthreads();
-  const double dot = (lds[0] + lds[1]) + (lds[2] + lds[3]);
-  if (b == 0 && tid == 0) {
-    *dot_out = dot;                                                    // for the update launch over the prefix
-    __hip_atomic_store(epoch, (unsigned long long)(1u - e), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  const double dot = block_sum4(p, lds);
+  if (b == 0 && tid == 0) *dot_out = dot;                              // for the update launch over the prefix
+  X.finish();
 
   HouseholderOp<T, CA, CB, BETA0> op{alpha, beta, nullptr, T(0)};
   op.c = (T)2 * (T)dot;                                                // = HouseholderOp::init()

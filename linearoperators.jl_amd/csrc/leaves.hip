@@ -235,12 +235,7 @@ static int32_t householder_apply_t(mxlo_ctx *ctx, T *res, const T *h, const T *v
 // Two dependent launches (dot, update) cost more than the data movement below ~1 MiB. Here every workgroup keeps its
 // slice of h and v in registers (read ONCE: 24 B/elt instead of 40), publishes its partial h'v into an exchange slot,
 // waits until all G <= 256 co-resident workgroups have published, sums the G partials in the same fixed order (every
-// workgroup obtains the bit-identical dot) and writes its slice of res.
-// The exchange uses no fence: each partial is ONE self-contained 64-bit agent-scope atomic store, an empty slot is a
-// NaN payload that arithmetic cannot produce, and readers poll with agent-scope loads (an agent-scope release fence
-// would write back the whole L2 of every XCD). Two slot sets alternate by an epoch bit kept in device memory (graph
-// replay safe): a launch uses set e, re-arms set 1-e for its successor, and workgroup 0 flips e after it has seen every
-// partial — by then every workgroup has read e.
+// workgroup obtains the bit-identical dot) and writes its slice of res. The exchange is GridExchange (grid_exchange.h).
 namespace {
 template <typename T, typename CA, typename CB, bool BETA0, int VPT, bool ALIGNED>
 __global__ void __launch_bounds__(kBlock)
@@ -250,11 +245,8 @@ householder_fused_kernel(T *__restrict__ res, const T *__restrict__ h, const T *
   constexpr int VEC = Vec16<T>::N;
   using V = typename Vec16<T>::type;
   const int tid = threadIdx.x, G = (int)gridDim.x, b = (int)blockIdx.x;
-  unsigned long long *epoch = slots + 2 * kFusedSlots;
-  const unsigned e = (unsigned)__hip_atomic_load(epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u;
-  unsigned long long *mine = slots + e * kFusedSlots, *other = slots + (1u - e) * kFusedSlots;
-  for (int i = b + tid * G; i < kFusedSlots; i += G * kBlock)          // re-arm the other set for the next launch
-    __hip_atomic_store(other + i, kSlotEmpty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  GridExchange X;
+  X.begin<kBlock>(slots, kFusedSlots);
 
   T hh[VPT][VEC], vv[VPT][VEC];
   double acc = 0.0;
@@ -279,31 +271,16 @@ householder_fused_kernel(T *__restrict__ res, const T *__restrict__ h, const T *
 #pragma unroll
     for (int k = 0; k < VEC; ++k) acc = fma((double)hh[q][k], (double)vv[q][k], acc);
 
-  __shared__ double lds[kBlock / 64];
-  const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if (lane == 0) lds[wave] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    const double s = (lds[0] + lds[1]) + (lds[2] + lds[3]);
-    unsigned long long bits = (unsigned long long)__double_as_longlong(s);
-    if (s != s) bits = kCanonicalNaN;                                // canonical NaN: never the empty marker
-    if (b != drop) __hip_atomic_store(mine + b, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  // wait for all G partials; lane t owns slot t (G <= 256 = one slot per lane). The wait is bounded (poll_slot): a
-  // peer that never becomes resident turns into a NaN result and a raised ctx fault word, not into a hung GPU.
-  double p = 0.0;                      // (G <= 256: one slot per lane, as rounds 3-5 summed them; G <= 512, round 6: lane t adds slots t, t + 256)
-  if (tid < G) p = __longlong_as_double((long long)poll_slot(mine + tid, ticks, fault, kFaultHouseholder));
-  if (tid + kBlock < G) p += __longlong_as_double((long long)poll_slot(mine + tid + kBlock, ticks, fault, kFaultHouseholder));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) p += __shfl_down(p, off, 64);
+  __shared__ double lds[kBlock / kWave];
+  const double s = block_sum4(acc, lds);   // (wave_sum: the tree of the __shfl_down loop this kernel used to carry)
+  if (tid == 0) X.publish(b, s, b == drop);
+  // wait for all G partials: lane t adds slots t and t + 256 (G <= 512; up to 256 a lane's one slot as it is, not 0 + it)
+  double p = 0.0;
+  if (tid < G) p = X.wait(tid, ticks, fault, kFaultHouseholder);
+  if (tid + kBlock < G) p += X.wait(tid + kBlock, ticks, fault, kFaultHouseholder);
   __syncthreads();                                                     // lds reuse
-  if (lane == 0) lds[wave] = p;
-  __syncthreads();
-  const double dot = (lds[0] + lds[1]) + (lds[2] + lds[3]);            // same order in every workgroup
-  if (b == 0 && tid == 0)
-    __hip_atomic_store(epoch, (unsigned long long)(1u - e), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const double dot = block_sum4(p, lds);                               // same order in every workgroup
+  X.finish();
 
   HouseholderOp<T, CA, CB, BETA0> op{alpha, beta, nullptr, T(0)};
   op.c = (T)2 * (T)dot;                                                // = HouseholderOp::init()

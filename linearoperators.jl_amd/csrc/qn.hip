@@ -643,18 +643,14 @@ cfwd_coef_kernel(const double *__restrict__ dots, const double *__restrict__ Cm,
 // dots -> finalize -> coefficients -> combine are 4 dependent launches, ~3.5 us each on MI355X whatever their size; for
 // n <= 2^17 the data movement is a fraction of that. Here (DESIGN §9 of round 2, built in round 3) every workgroup
 //   1. keeps its slice of x in registers and reduces it against its slice of the <= 40 panel columns,
-//   2. publishes the partial dots as self-validating 64-bit agent-scope stores into exchange slots (an empty slot is a
-//      NaN payload arithmetic cannot produce; NaN partials are canonicalised) — NO fence: an agent-scope release would
-//      write back the L2 of all 8 XCDs (profiles/r01_sweep_fuse.txt), the protocol of the single-launch Householder,
+//   2. publishes the partial dots into exchange slots (GridExchange, grid_exchange.h: the protocol and why it is safe),
 //   3. polls until all G <= 64 co-resident workgroups have published, sums every column's partials in a fixed order
 //      (lane i <- workgroup i, one fixed DPP tree: bit-identical in every workgroup),
 //   4. runs the operator's coefficient recurrence on one wave — redundantly per workgroup — from Gram data it staged
 //      in LDS while the dots were in flight, and
 //   5. applies the columns to its slice in the reference's elementwise order (the formulas of combine_kernel) and
 //      writes res.
-// Two slot sets alternate by an epoch word in device memory (graph-replay safe): a launch uses set e, re-arms set 1 - e
-// for its successor, workgroup 0 flips e once it has seen every partial. One fused launch in flight per ctx (all work of
-// a ctx is stream-ordered: mxlo_ctx_set_stream). Not used with an all-reduce hook (a host callback sits between 3 and 4).
+// Slot (column c, workgroup w) is c * kQnfMaxGrid + w. Not used with an all-reduce hook (a host callback sits between 3 and 4).
 // kQnfMaxCols = 40 (2*mem at mem <= 20: the launch-bound defaults of the callers), kQnfMaxGrid = 256 workgroups (round 4;
 // 64 before: n <= 131072 doubles), kQnfSlots: common.h. The gathered partials live in DYNAMIC LDS (ncol x grid doubles,
 // at most kQnfMaxPart = 6144: 48 KiB next to the 8 KiB of static LDS).
@@ -673,6 +669,76 @@ struct QnfArgs {
   const double *as_;                         // L-SR1
   int ct_f32;
 };
+// the scalars an apply has already put into its CombineArgs; the caller adds its kind's pointers
+template <typename T>
+inline QnfArgs qnf_args(int kind, const CombineArgs<T> &A) {
+  QnfArgs F{};
+  F.kind = kind;
+  F.ncol = A.ncol;
+  F.nfirst = A.nfirst;
+  F.use_gamma = A.use_gamma;
+  F.gamma = A.gamma;
+  F.alpha = A.alpha;
+  F.beta = A.beta;
+  F.shift = A.shift;
+  return F;
+}
+
+// ---- the phases qn_apply_fused_kernel and qn_apply_persist_kernel share (BLOCK: threads per workgroup) ----------------
+// Stage the Gram data the coefficient recurrence reads (the loads overlap the dots phase).
+// sg1: inverse: s_i'y_j by ord position (na x na); forward: Cm (r x 2r). sg2: inverse: y_i'y_j by ord position; L-SR1: as by ord position
+template <int KIND, int BLOCK>
+__device__ __forceinline__ void qnf_stage_gram(const QnfArgs &F, const OrdArgs &O, double *sg1, double *sg2) {
+  const int tid = threadIdx.x, na = O.na;
+  if constexpr (KIND == MXLO_QN_LBFGS_INV) {
+    const int mem = O.mem;
+    for (int p = tid; p < na * na; p += BLOCK) {
+      const int i = O.ord[p / na], j = O.ord[p % na];                  // slots
+      sg1[p] = O.age[j] >= O.age[i] ? F.SY[i + (int64_t)j * mem] : F.YS[j + (int64_t)i * mem];   // s_i'y_j
+      sg2[p] = O.age[j] >= O.age[i] ? F.YY[i + (int64_t)j * mem] : F.YY[j + (int64_t)i * mem];   // y_i'y_j
+    }
+  } else if constexpr (KIND == MXLO_QN_LBFGS_FWD) {
+    for (int p = tid; p < na * 2 * na; p += BLOCK) sg1[p] = F.Cm[p];
+  } else {
+    if (tid < na) sg2[tid] = F.as_[O.ord[tid]];
+  }
+}
+// Coefficients from the summed dots: wave 0, redundantly per workgroup; the recurrences of the *_coef_kernel bodies.
+template <int KIND>
+__device__ __forceinline__ void qnf_coef(const QnfArgs &F, const OrdArgs &O, const double *sdots, double *scoef,
+                                         const double *sg1, const double *sg2) {
+  const int lane = threadIdx.x & 63, na = O.na;
+  if (threadIdx.x >= 64) return;
+  if constexpr (KIND == MXLO_QN_LBFGS_INV) {
+    inv_coef_generic(lane, sdots, scoef, blockIdx.x == 0 ? F.alpha_out : nullptr, O,
+                     [&](int i, int j) { return sg1[i * na + j]; }, [&](int i, int j) { return sg2[i * na + j]; });
+  } else if constexpr (KIND == MXLO_QN_LBFGS_FWD) {
+    cfwd_coef_body(lane, sdots, sg1, scoef, na);
+  } else {
+    if (lane < na) {
+      const double d = rnd(sdots[lane], O.is_f32), as = rnd(sg2[lane], O.is_f32);
+      scoef[lane] = F.ct_f32 ? (double)(((float)F.alpha * (float)d) / (float)as) : (F.alpha * d) / as;
+    }
+  }
+}
+// Combine column c in terms of the dots columns: the inverse operator's dots run over [s.., y..] newest -> oldest, its
+// combine over y newest -> oldest, then s oldest -> newest; the other two use one order for both.
+template <int KIND, typename T>
+__device__ __forceinline__ const T *qnf_ccol(const QnfCols<T> &cols, const QnfArgs &F, int c) {
+  if constexpr (KIND == MXLO_QN_LBFGS_INV) return c < F.nfirst ? cols.p[F.nfirst + c] : cols.p[2 * F.nfirst - 1 - c];
+  else return cols.p[c];
+}
+// Guarded load at element i: 16 bytes, or element loads with zero fill behind n (the persistent kernel keeps this text inline).
+template <typename T>
+__device__ __forceinline__ typename Vec16<T>::type qnf_ldv(const T *p, int64_t i, int64_t n) {
+  constexpr int VEC = Vec16<T>::N;
+  using V = typename Vec16<T>::type;
+  if (i + VEC <= n) return *reinterpret_cast<const V *>(p + i);
+  V v;
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) v[k] = i + k < n ? p[i + k] : T(0);
+  return v;
+}
 
 // U vectors per lane and NB columns per batch: (4, 8) in general; (2, 12) when 8 < ncol <= 12 and the vector is short enough
 // for 64 workgroups of half the slice — then ALL columns are one batch: one round trip in the dots phase and one in the
@@ -686,31 +752,16 @@ qn_apply_fused_kernel(T *__restrict__ res, QnfCols<T> cols, const T *__restrict_
   constexpr int VEC = Vec16<T>::N;
   using V = typename Vec16<T>::type;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, G = (int)gridDim.x, b = (int)blockIdx.x;
-  const int ncol = F.ncol, na = O.na;
+  const int ncol = F.ncol;
   __shared__ double red[kBlock / 64][kQnfMaxCols];
   extern __shared__ double spart[];                         // [ncol][G] gathered partials
   __shared__ double sdots[kQnfMaxCols];
   __shared__ double scoef[kQnfMaxCols];
   __shared__ double sg1[kQnfMaxCols * kQnfMaxCols / 2];     // inverse: s_i'y_j by ord position (na x na); forward: Cm (r x 2r)
   __shared__ double sg2[kQnfMaxCols * kQnfMaxCols / 4];     // inverse: y_i'y_j by ord position; L-SR1: as by ord position
-  unsigned long long *epoch = slots + 2 * kQnfSlots;
-  const unsigned e = (unsigned)__hip_atomic_load(epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u;
-  unsigned long long *mine = slots + e * kQnfSlots, *other = slots + (1u - e) * kQnfSlots;
-  for (int i = b * kBlock + tid; i < kQnfSlots; i += G * kBlock)       // re-arm the other set for the next launch
-    __hip_atomic_store(other + i, kSlotEmpty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  // ---- stage the Gram data the coefficient recurrence reads (loads overlap the dots below)
-  if constexpr (KIND == MXLO_QN_LBFGS_INV) {
-    const int mem = O.mem;
-    for (int p = tid; p < na * na; p += kBlock) {
-      const int i = O.ord[p / na], j = O.ord[p % na];                  // slots
-      sg1[p] = O.age[j] >= O.age[i] ? F.SY[i + (int64_t)j * mem] : F.YS[j + (int64_t)i * mem];   // s_i'y_j
-      sg2[p] = O.age[j] >= O.age[i] ? F.YY[i + (int64_t)j * mem] : F.YY[j + (int64_t)i * mem];   // y_i'y_j
-    }
-  } else if constexpr (KIND == MXLO_QN_LBFGS_FWD) {
-    for (int p = tid; p < na * 2 * na; p += kBlock) sg1[p] = F.Cm[p];
-  } else {
-    if (tid < na) sg2[tid] = F.as_[O.ord[tid]];
-  }
+  GridExchange X;
+  X.begin<kBlock>(slots, kQnfSlots);
+  qnf_stage_gram<KIND, kBlock>(F, O, sg1, sg2);
   // ---- 1. this workgroup's slice: U vectors per lane, x kept in registers
   const int64_t base = ((int64_t)b * kBlock * U + tid) * VEC;
   T xe[U][VEC];
@@ -731,13 +782,6 @@ qn_apply_fused_kernel(T *__restrict__ res, QnfCols<T> cols, const T *__restrict_
   // branch makes the compiler wait at every merge point: one memory round trip per LOAD). The last workgroup takes the
   // guarded form.
   const bool full = ((int64_t)(b + 1) * kBlock * U) * VEC <= n;
-  auto ldv = [&](const T *p, int64_t i) -> V {   // guarded: 16-byte load, or element loads with zero fill
-    if (i + VEC <= n) return *reinterpret_cast<const V *>(p + i);
-    V v;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) v[k] = i + k < n ? p[i + k] : T(0);
-    return v;
-  };
   // REUSE: the narrow shapes keep the LAST dots batch in registers through the exchange, and the combine phase applies
   // it from there instead of reading those columns again (forward L-BFGS and L-SR1: same column order in both phases;
   // with a single batch — the case these shapes exist for — the combine then issues no column load at all)
@@ -759,7 +803,7 @@ qn_apply_fused_kernel(T *__restrict__ res, QnfCols<T> cols, const T *__restrict_
         for (int u = 0; u < U; ++u) {
           const int64_t i = base + (int64_t)u * kBlock * VEC;
           if constexpr (FULL) cv[t][u] = *reinterpret_cast<const V *>(p + i);
-          else cv[t][u] = ldv(p, i);
+          else cv[t][u] = qnf_ldv(p, i, n);
         }
       }
 #pragma unroll
@@ -778,21 +822,14 @@ qn_apply_fused_kernel(T *__restrict__ res, QnfCols<T> cols, const T *__restrict_
   else dots_batches.template operator()<false>();
   __syncthreads();
   // ---- 2. publish
-  if (tid < ncol) {
-    const double sv = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-    unsigned long long bits = (unsigned long long)__double_as_longlong(sv);
-    if (sv != sv) bits = kCanonicalNaN;                               // canonical NaN: never the empty marker
-    if (b != drop) __hip_atomic_store(mine + tid * kQnfMaxGrid + b, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (tid < ncol) X.publish(tid * kQnfMaxGrid + b, (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]), b == drop);
   // ---- 3. gather: every (column, workgroup) slot is polled by exactly one lane; all polls of a lane are in flight together
   for (int p = tid; p < ncol * G; p += kBlock) {
     const int c = p / G, w = p - c * G;
-    // bounded wait (poll_slot, common.h): a peer that never becomes resident ends as NaN + the ctx fault word
-    spart[c * G + w] = __longlong_as_double((long long)poll_slot(mine + c * kQnfMaxGrid + w, ticks, fault, kFaultQn));
+    spart[c * G + w] = X.wait(c * kQnfMaxGrid + w, ticks, fault, kFaultQn);
   }
   __syncthreads();
-  if (b == 0 && tid == 0)                                             // every workgroup has read e: flip for the next launch
-    __hip_atomic_store(epoch, (unsigned long long)(1u - e), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  X.finish();
   for (int c = wave; c < ncol; c += kBlock / 64) {                    // fixed order: lane i <- workgroup i, one DPP tree
     double pv = lane < G ? spart[c * G + lane] : 0.0;                 // up to 64 workgroups: one partial per lane (the
     for (int w = lane + 64; w < G; w += 64) pv += spart[c * G + w];   // bits of round 3); beyond: lane l adds l, l+64, ...
@@ -800,31 +837,14 @@ qn_apply_fused_kernel(T *__restrict__ res, QnfCols<T> cols, const T *__restrict_
     if (lane == 0) sdots[dots_index(c)] = v;
   }
   __syncthreads();
-  // ---- 4. coefficients (one wave, redundantly per workgroup; same recurrences as the *_coef_kernel bodies)
-  if (wave == 0) {
-    if constexpr (KIND == MXLO_QN_LBFGS_INV) {
-      inv_coef_generic(lane, sdots, scoef, b == 0 ? F.alpha_out : nullptr, O,
-                       [&](int i, int j) { return sg1[i * na + j]; }, [&](int i, int j) { return sg2[i * na + j]; });
-    } else if constexpr (KIND == MXLO_QN_LBFGS_FWD) {
-      cfwd_coef_body(lane, sdots, sg1, scoef, na);
-    } else {
-      if (lane < na) {
-        const double d = rnd(sdots[lane], O.is_f32), as = rnd(sg2[lane], O.is_f32);
-        scoef[lane] = F.ct_f32 ? (double)(((float)F.alpha * (float)d) / (float)as) : (F.alpha * d) / as;
-      }
-    }
-  }
+  // ---- 4. coefficients
+  qnf_coef<KIND>(F, O, sdots, scoef, sg1, sg2);
   __syncthreads();
   // ---- 5. combine on this workgroup's slice: the elementwise formulas (and rounding points) of combine_kernel
   const T g = (T)F.gamma;
   const CA al = (CA)F.alpha;
   const CB be = (CB)F.beta;
-  // combine column c in terms of the dots columns: the inverse operator's dots run over [s.., y..] newest -> oldest, its
-  // combine over y newest -> oldest, then s oldest -> newest; the other two use one order for both
-  auto ccol = [&](int c) -> const T * {
-    if constexpr (KIND == MXLO_QN_LBFGS_INV) return c < F.nfirst ? cols.p[F.nfirst + c] : cols.p[2 * F.nfirst - 1 - c];
-    else return cols.p[c];
-  };
+  auto ccol = [&](int c) { return qnf_ccol<KIND>(cols, F, c); };
   // prologue / one column / epilogue of the combine on E elements (formulas and rounding points of combine_kernel)
   auto prologue = [&]<int E>(const T (&xq)[E], const T (&rq)[E], T (&q)[E]) {
 #pragma unroll
@@ -1021,29 +1041,15 @@ qn_apply_persist_kernel(T *__restrict__ res, QnfCols<T> cols, const T *__restric
     return reinterpret_cast<V *>(persist_dyn) + ((int64_t)slot * cpw + j) * kPersistBlock + threadIdx.x;
   };
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, G = (int)gridDim.x, b = (int)blockIdx.x;
-  const int ncol = F.ncol, na = O.na;
+  const int ncol = F.ncol;
   __shared__ double red[NW][kQnfMaxCols];
   __shared__ double sdots[kQnfMaxCols];
   __shared__ double scoef[kQnfMaxCols];
   __shared__ double sg1[kQnfMaxCols * kQnfMaxCols / 2];     // inverse: s_i'y_j by ord position; forward: Cm (r x 2r)
   __shared__ double sg2[kQnfMaxCols * kQnfMaxCols / 4];     // inverse: y_i'y_j by ord position; L-SR1: as by ord position
-  unsigned long long *epoch = slots + 2 * kQnfSlots;
-  const unsigned e = (unsigned)__hip_atomic_load(epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u;
-  unsigned long long *mine = slots + e * kQnfSlots, *other = slots + (1u - e) * kQnfSlots;
-  for (int i = b * kPersistBlock + tid; i < kQnfSlots; i += G * kPersistBlock)      // re-arm the other set for the next launch
-    __hip_atomic_store(other + i, kSlotEmpty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if constexpr (KIND == MXLO_QN_LBFGS_INV) {
-    const int mem = O.mem;
-    for (int p = tid; p < na * na; p += kPersistBlock) {
-      const int i = O.ord[p / na], j = O.ord[p % na];
-      sg1[p] = O.age[j] >= O.age[i] ? F.SY[i + (int64_t)j * mem] : F.YS[j + (int64_t)i * mem];
-      sg2[p] = O.age[j] >= O.age[i] ? F.YY[i + (int64_t)j * mem] : F.YY[j + (int64_t)i * mem];
-    }
-  } else if constexpr (KIND == MXLO_QN_LBFGS_FWD) {
-    for (int p = tid; p < na * 2 * na; p += kPersistBlock) sg1[p] = F.Cm[p];
-  } else {
-    if (tid < na) sg2[tid] = F.as_[O.ord[tid]];
-  }
+  GridExchange X;
+  X.begin<kPersistBlock>(slots, kQnfSlots);
+  qnf_stage_gram<KIND, kPersistBlock>(F, O, sg1, sg2);
   // this workgroup's chunks: [ch0, ch1) of kPersistBlock vectors each; only the very last chunk of the vector can hold
   // lanes beyond n (or a partial last vector): it takes the guarded loads
   const int64_t nvec = (n + VEC - 1) / VEC;
@@ -1051,7 +1057,9 @@ qn_apply_persist_kernel(T *__restrict__ res, QnfCols<T> cols, const T *__restric
   const int64_t ch0 = (int64_t)b * cpw < nchunks ? (int64_t)b * cpw : nchunks;
   const int64_t ch1 = ch0 + cpw < nchunks ? ch0 + cpw : nchunks;
   auto chunk_full = [&](int64_t ch) { return (ch + 1) * kPersistBlock * VEC <= n; };
-  auto ldv = [&](const T *p, int64_t i) -> V {   // guarded: 16-byte load, or element loads with zero fill (i: element index)
+  // guarded: 16-byte load, or element loads with zero fill (i: element index). The text of qnf_ldv, kept inline: through
+  // the shared function the applies at n = 2^19 measured 0.1-0.3 us slower in two sessions (profiles/grid_exchange_refactor.txt)
+  auto ldv = [&](const T *p, int64_t i) -> V {
     if (i + VEC <= n) return *reinterpret_cast<const V *>(p + i);
     V v;
 #pragma unroll
@@ -1101,11 +1109,7 @@ qn_apply_persist_kernel(T *__restrict__ res, QnfCols<T> cols, const T *__restric
     }
   }
   __syncthreads();
-  // combine column c in terms of the dots columns
-  auto ccol = [&](int c) -> const T * {
-    if constexpr (KIND == MXLO_QN_LBFGS_INV) return c < F.nfirst ? cols.p[F.nfirst + c] : cols.p[2 * F.nfirst - 1 - c];
-    else return cols.p[c];
-  };
+  auto ccol = [&](int c) { return qnf_ccol<KIND>(cols, F, c); };
   // PREFETCH across the exchange (tune key qn_persist_prefetch, OFF by default): x and the first batch of columns of the
   // chunk the combine phase takes first are requested NOW — they need no coefficient — and travel while the partials are
   // exchanged and the recurrence runs. Measured: no gain — 1.5 us slower at n = 2^19 .. 2^20 (loads return in order, so the
@@ -1120,48 +1124,29 @@ qn_apply_persist_kernel(T *__restrict__ res, QnfCols<T> cols, const T *__restric
     for (int t = 0; t < NB; ++t) pcv[t] = *reinterpret_cast<const V *>(ccol(t < ncol ? t : ncol - 1) + ip);
   }
   // ---- 2. publish, gather (fixed order: lane l adds workgroups l, l + 64, ..., then one DPP tree)
-  if (tid < ncol) {
-    const double sv = ((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid])) +
-                      ((red[4][tid] + red[5][tid]) + (red[6][tid] + red[7][tid]));
-    unsigned long long bits = (unsigned long long)__double_as_longlong(sv);
-    if (sv != sv) bits = kCanonicalNaN;
-    if (b != drop) __hip_atomic_store(mine + tid * kQnfMaxGrid + b, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (tid < ncol)
+    X.publish(tid * kQnfMaxGrid + b, ((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid])) +
+                                     ((red[4][tid] + red[5][tid]) + (red[6][tid] + red[7][tid])), b == drop);
   for (int c = wave; c < ncol; c += NW) {
     constexpr int kPer = kQnfMaxGrid / 64;
-    const unsigned long long *row = mine + c * kQnfMaxGrid;
+    const int row = c * kQnfMaxGrid + lane;
     unsigned long long bits[kPer];
 #pragma unroll
     for (int j = 0; j < kPer; ++j)      // first look: all of a lane's slots in flight together
-      bits[j] = lane + 64 * j < G ? __hip_atomic_load(row + lane + 64 * j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+      bits[j] = lane + 64 * j < G ? X.peek(row + 64 * j) : 0ull;
     double pv = 0.0;
 #pragma unroll
     for (int j = 0; j < kPer; ++j) {
-      if (lane + 64 * j < G) {
-        if (bits[j] == kSlotEmpty) bits[j] = poll_slot(row + lane + 64 * j, ticks, fault, kFaultQn);   // bounded wait
-        pv += __longlong_as_double((long long)bits[j]);
-      }
+      if (lane + 64 * j < G)
+        pv += bits[j] == kSlotEmpty ? X.wait(row + 64 * j, ticks, fault, kFaultQn) : __longlong_as_double((long long)bits[j]);
     }
     const double v = wave_allsum(pv);
     if (lane == 0) sdots[c] = v;
   }
   __syncthreads();
-  if (b == 0 && tid == 0)                                             // every workgroup has read e: flip for the next launch
-    __hip_atomic_store(epoch, (unsigned long long)(1u - e), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  // ---- 3. coefficients (one wave, redundantly per workgroup; the bodies of the *_coef_kernel launches)
-  if (wave == 0) {
-    if constexpr (KIND == MXLO_QN_LBFGS_INV) {
-      inv_coef_generic(lane, sdots, scoef, b == 0 ? F.alpha_out : nullptr, O,
-                       [&](int i, int j) { return sg1[i * na + j]; }, [&](int i, int j) { return sg2[i * na + j]; });
-    } else if constexpr (KIND == MXLO_QN_LBFGS_FWD) {
-      cfwd_coef_body(lane, sdots, sg1, scoef, na);
-    } else {
-      if (lane < na) {
-        const double d = rnd(sdots[lane], O.is_f32), as = rnd(sg2[lane], O.is_f32);
-        scoef[lane] = F.ct_f32 ? (double)(((float)F.alpha * (float)d) / (float)as) : (F.alpha * d) / as;
-      }
-    }
-  }
+  X.finish();
+  // ---- 3. coefficients
+  qnf_coef<KIND>(F, O, sdots, scoef, sg1, sg2);
   __syncthreads();
   // ---- 4. combine, last chunk first (columns in COMBINE order)
   const T g = (T)F.gamma;
@@ -1374,15 +1359,7 @@ int32_t inv_mul_twopass(mxlo_qn *h, T *res, const T *x, double alpha, double bet
       cols[na + i] = col<T>(h->Y, h->ld, O.ord[i]);
     }
     {  // launch-bound sizes: the whole apply in one launch
-      QnfArgs F{};
-      F.kind = MXLO_QN_LBFGS_INV;
-      F.ncol = 2 * na;
-      F.nfirst = na;
-      F.use_gamma = h->scaling;
-      F.gamma = h->scaling_factor;
-      F.alpha = alpha;
-      F.beta = beta;
-      F.shift = shift;
+      QnfArgs F = qnf_args(MXLO_QN_LBFGS_INV, A);
       F.SY = h->dsc + h->lay.SY;
       F.YS = h->dsc + h->lay.YS;
       F.YY = h->dsc + h->lay.YY;
@@ -1473,15 +1450,7 @@ int32_t fwd_mul(mxlo_qn *h, T *res, const T *x, double alpha, double beta, int32
       A.cols[na + i] = col<T>(h->B, h->ld, O.ord[i]);
     }
     {
-      QnfArgs F{};
-      F.kind = MXLO_QN_LBFGS_FWD;
-      F.ncol = 2 * na;
-      F.nfirst = 0;
-      F.use_gamma = h->scaling;
-      F.gamma = h->scaling_factor;
-      F.alpha = alpha;
-      F.beta = beta;
-      F.shift = shift;
+      QnfArgs F = qnf_args(MXLO_QN_LBFGS_FWD, A);
       F.Cm = h->dsc + h->lay.Cm;
       int32_t fst = MXLO_OK;
       if (try_persist_apply<T>(h, res, A.cols, x, F, O, flags, &fst)) return fst;
@@ -1528,15 +1497,7 @@ int32_t lsr1_mul(mxlo_qn *h, T *res, const T *x, double alpha, double beta, int3
     for (int i = 0; i < na; ++i) A.cols[i] = col<T>(h->A, h->ld, O.ord[i]);
     const int ct_f32 = alpha_is_f64(sizeof(T), flags) ? 0 : 1;
     {
-      QnfArgs F{};
-      F.kind = MXLO_QN_LSR1;
-      F.ncol = na;
-      F.nfirst = 0;
-      F.use_gamma = 1;
-      F.gamma = h->scaling_factor;
-      F.alpha = alpha;
-      F.beta = beta;
-      F.shift = shift;
+      QnfArgs F = qnf_args(MXLO_QN_LSR1, A);
       F.as_ = h->dsc + h->lay.as_;
       F.ct_f32 = ct_f32;
       int32_t fst = MXLO_OK;

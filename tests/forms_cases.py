@@ -106,12 +106,12 @@ FORMS = {
         row([0, 1, 64], "stream", STREAM, True, "only the grid of the grid-stride map_kernel changes: every element is still produced once by the same op",
             "linearoperators.jl_amd/csrc/stream_kernels.h:170"),
         row([0, 1, 64], "restrict", STREAM, True, "gather / scatter copy elements: the grid decides who copies, not what",
-            "linearoperators.jl_amd/csrc/leaves.hip:707"),
+            "linearoperators.jl_amd/csrc/leaves.hip:684"),
     ],
     "nt_min_bytes": [
         row([0, I64_MAX], "stream", STREAM, True, _NT_WHY, "linearoperators.jl_amd/csrc/stream_kernels.h:166"),
         row([0], "restrict", STREAM, True, "the gather / scatter kernels have no NT instantiation and never read the key",
-            "linearoperators.jl_amd/csrc/leaves.hip:709"),
+            "linearoperators.jl_amd/csrc/leaves.hip:686"),
         row([0], "dots", DOTS),      # reductions.hip:240: with nt on, one- and two-column dots take ONE workgroup per CU — a grid change
         row([0], "house2", HOUSE, fixed=dict(house_fused=0, house_inline_n=0)),
         row([0], "qn4", QN4, fixed=_QN4),
@@ -126,7 +126,7 @@ FORMS = {
     ],
     "extend_tiles_per_block": [
         row([0, 1, 1024], "extend", EXTEND, True, "tiles per workgroup: each output tile is still written once from the same plan search",
-            "linearoperators.jl_amd/csrc/leaves.hip:788"),
+            "linearoperators.jl_amd/csrc/leaves.hip:765"),
     ],
     "red_blocks_per_cu": [
         row([1, 4, HI_PER_CU], "dots", DOTS),
@@ -156,7 +156,7 @@ FORMS = {
     ],
     "house_reverse": [
         row([0, 1], "house2", HOUSE, True, "REVERSE is the order in which the elementwise update walks the vectors",
-            "linearoperators.jl_amd/csrc/leaves.hip:396", fixed=dict(house_fused=0)),
+            "linearoperators.jl_amd/csrc/leaves.hip:373", fixed=dict(house_fused=0)),
         row([0, 1], "house2", HOUSE, True, "REVERSE is the order in which the elementwise update walks the vectors",
             "linearoperators.jl_amd/csrc/leaves.hip:226", fixed=dict(house_fused=0, house_inline_n=0)),
     ],
@@ -171,7 +171,7 @@ FORMS = {
     ],
     "combine_reverse": [
         row([0, 1], "qn4", QN4, True, "the order in which the combine pass walks the (independent) output vectors",
-            "linearoperators.jl_amd/csrc/qn.hip:1409", fixed=_QN4),
+            "linearoperators.jl_amd/csrc/qn.hip:1386", fixed=_QN4),
     ],
     # (the probe's n = 4099 is odd: the four-launch form takes a fifth, scalar combine launch for the last element, qn.hip:384-388)
     "qn_fused_small": [
@@ -205,18 +205,18 @@ FORMS = {
     ],
     "qn_persist_reverse": [
         row([0, 1], "qnp", QNP, True, "the order in which a workgroup's combine phase walks its own (independent) chunks",
-            "linearoperators.jl_amd/csrc/qn.hip:1340", fixed=_PERSIST, engaged={0: 1, 1: 1}, probe=("inv", "f64", 5, 65_537)),
+            "linearoperators.jl_amd/csrc/qn.hip:1325", fixed=_PERSIST, engaged={0: 1, 1: 1}, probe=("inv", "f64", 5, 65_537)),
     ],
     "qn_persist_prefetch": [
         row([0, 1], "qnp", QNP, True, "loads issued earlier; values and the order of every operation stay",
-            "linearoperators.jl_amd/csrc/qn.hip:1340", fixed=_PERSIST, engaged={0: 1, 1: 1}, probe=("inv", "f64", 5, 65_537)),
+            "linearoperators.jl_amd/csrc/qn.hip:1325", fixed=_PERSIST, engaged={0: 1, 1: 1}, probe=("inv", "f64", 5, 65_537)),
     ],
     "qn_persist_lds": [
         row([0, 1], "qnp", QNP, True, "the combine phase reads x and the first columns from LDS copies instead of memory: same values",
-            "linearoperators.jl_amd/csrc/qn.hip:1323", fixed=_PERSIST, engaged={0: 1, 1: 1}, probe=("inv", "f64", 5, 65_537)),
+            "linearoperators.jl_amd/csrc/qn.hip:1308", fixed=_PERSIST, engaged={0: 1, 1: 1}, probe=("inv", "f64", 5, 65_537)),
     ],
     "qn_persist_lds_pad": [
-        row([0, 81_920, 114_688], "qnp", QNP, True, "dynamic LDS the kernel never touches", "linearoperators.jl_amd/csrc/qn.hip:1322",
+        row([0, 81_920, 114_688], "qnp", QNP, True, "dynamic LDS the kernel never touches", "linearoperators.jl_amd/csrc/qn.hip:1307",
             fixed=_PERSIST, engaged={0: 1, 81_920: 1, 114_688: 1}, probe=("inv", "f64", 5, 65_537)),
     ],
     "lbfgs_inv_mode": [
@@ -230,7 +230,7 @@ FORMS = {
     ],
     "push_posted": [
         row([0, 1], "push", PUSH, True, "the same kernels; only the way the decision scalars reach the host changes",
-            "linearoperators.jl_amd/csrc/qn.hip:1607"),
+            "linearoperators.jl_amd/csrc/qn.hip:1568"),
     ],
     # 0 off, 1 auto; a band height is taken where it is 8 V, 16 V or 32 V rows (16 / 32 / 64 for Float64, 32 / 64 / 128 for Float32,
     # dense.hip:391) and leaves the column-chunk schedule in place otherwise (7; 128 for Float64; 16 for Float32)
@@ -247,36 +247,36 @@ FORMS = {
     ],
     "herm_nt": [
         row([-1, 0, 1], "herm", HERM, True, "NT is a template parameter of the pass kernels: the cache policy of the strip loads",
-            "linearoperators.jl_amd/csrc/dense.hip:1579"),
+            "linearoperators.jl_amd/csrc/dense.hip:1577"),
         # (the single launch takes the real vector applies at n = 256 / 512 and has no NT instantiation: the two launches do)
         row([-1, 0, 1], "herm", HERM, True, "NT is a template parameter of the pass kernels: the cache policy of the strip loads",
-            "linearoperators.jl_amd/csrc/dense.hip:1579", fixed=dict(herm_single=0)),
+            "linearoperators.jl_amd/csrc/dense.hip:1577", fixed=dict(herm_single=0)),
     ],
     # an n = 512 Float64 triangle is 8 * 512 * 256 = 1 MiB: below dp_min (nontemporal), in [dp_min, nt_min) (default policy), from nt_min on
     "herm_dp_min_bytes": [
         row([0, MIB, MIB + 1, 96 * MIB, I64_MAX], "herm", HERM, True, "selects the cache policy of the strip loads only",
-            "linearoperators.jl_amd/csrc/dense.hip:1581", fixed=dict(herm_nt=-1, herm_nt_min_bytes=2 * MIB)),
+            "linearoperators.jl_amd/csrc/dense.hip:1579", fixed=dict(herm_nt=-1, herm_nt_min_bytes=2 * MIB)),
         row([0, MIB, MIB + 1, 96 * MIB, I64_MAX], "herm", HERM, True, "selects the cache policy of the strip loads only",
-            "linearoperators.jl_amd/csrc/dense.hip:1581", fixed=dict(herm_nt=-1, herm_nt_min_bytes=2 * MIB, herm_single=0)),
+            "linearoperators.jl_amd/csrc/dense.hip:1579", fixed=dict(herm_nt=-1, herm_nt_min_bytes=2 * MIB, herm_single=0)),
     ],
     "herm_nt_min_bytes": [
         row([0, MIB, MIB + 1, 384 * MIB, I64_MAX], "herm", HERM, True, "selects the cache policy of the strip loads only",
             "linearoperators.jl_amd/csrc/complex.hip:964", fixed=dict(herm_nt=-1, herm_dp_min_bytes=0)),
         row([0, MIB, MIB + 1, 384 * MIB, I64_MAX], "herm", HERM, True, "selects the cache policy of the strip loads only",
-            "linearoperators.jl_amd/csrc/dense.hip:1581", fixed=dict(herm_nt=-1, herm_dp_min_bytes=0, herm_single=0)),
+            "linearoperators.jl_amd/csrc/dense.hip:1579", fixed=dict(herm_nt=-1, herm_dp_min_bytes=0, herm_single=0)),
     ],
     "herm_lds_pad": [
-        row([0, 49_152], "herm", HERM, True, "dynamic LDS the pass kernels never touch", "linearoperators.jl_amd/csrc/dense.hip:1689",
+        row([0, 49_152], "herm", HERM, True, "dynamic LDS the pass kernels never touch", "linearoperators.jl_amd/csrc/dense.hip:1687",
             fixed=dict(herm_single=0)),
     ],
     "herm_poll_sleep": [
-        row([1, 4, 1024], "herm", HERM, True, "how often the finishers of the single launch look for their slots", "linearoperators.jl_amd/csrc/dense.hip:1653"),
+        row([1, 4, 1024], "herm", HERM, True, "how often the finishers of the single launch look for their slots", "linearoperators.jl_amd/csrc/dense.hip:1651"),
     ],
     "herm_order": [
         row([0, 1], "herm", HERM, True, "the order of the interior strips: every partial lands in the same slot and is added in the same order",
-            "linearoperators.jl_amd/csrc/dense.hip:1690"),
+            "linearoperators.jl_amd/csrc/dense.hip:1688"),
         row([0, 1], "herm", HERM, True, "the order of the interior strips: every partial lands in the same slot and is added in the same order",
-            "linearoperators.jl_amd/csrc/dense.hip:1690", fixed=dict(herm_single=0)),
+            "linearoperators.jl_amd/csrc/dense.hip:1688", fixed=dict(herm_single=0)),
     ],
     "herm_strip": [
         row([0, 1, 2, 8], "herm", HERM),
@@ -286,7 +286,7 @@ FORMS = {
     ],
     "herm_single": [
         row([0, 1], "herm", HERM, True, "strips and finishers share the partial layout and the order of the additions with the two launches",
-            "linearoperators.jl_amd/csrc/dense.hip:1618", engaged={0: 2, 1: 1}, probe=("f64", 512)),
+            "linearoperators.jl_amd/csrc/dense.hip:1616", engaged={0: 2, 1: 1}, probe=("f64", 512)),
     ],
     "herm_single_max_n": [
         row([0, 511, 512, I64_MAX], "herm", HERM, engaged={0: 1, 511: 2, 512: 1, I64_MAX: 1}, probe=("f64", 512)),

@@ -1093,6 +1093,65 @@ def test_persistent_apply_timeout_is_an_error_not_a_hang(lo, dev):
                 assert torch.equal(res, good)
 
 
+@pytest.mark.parametrize("n", [4099, 65_538])
+def test_slice_and_persistent_forms_alternate_on_one_ctx(lo, dev, n):
+    """The two single-launch quasi-Newton forms share the ctx's exchange slots and its one epoch word (csrc/grid_exchange.h):
+    each launch re-arms the set the NEXT launch uses, whichever form that is. Eight applies of one inverse L-BFGS operator
+    (mem = 5, five pairs, Float64) on one ctx, slice form and persistent form in turn: every result has the bits of the
+    same form applied to the same operands on a ctx of its own with nothing in between, and every apply was one launch
+    (so both forms did engage). The counterpart of test_alternating_with_the_single_launch_form_shares_the_slots."""
+    import ctypes as C
+    import gc
+    from linearoperators_jl_amd import device
+    forms = {"slice": dict(qn_persist=0, qn_fused_small=1),
+             "persist": dict(qn_persist=1, qn_persist_min_n=1, qn_persist_min_bytes=0, qn_fused_small=0)}
+    rng = np.random.default_rng(n)
+    prs = pairs(rng, n, 5)
+    x = T(rng.uniform(-1, 1, n), dev)
+
+    def launches():
+        a = (C.c_int64 * 12)()
+        lo._lib.call("mxlo_debug_counters", a)
+        return a[10]
+
+    def make():
+        op = lo.InverseLBFGSOperator(torch.float64, n, mem=5, device=dev)
+        for s, y in prs:
+            lo.push(op, T(s, dev), T(y, dev))
+        return op
+
+    def apply(op, form):
+        res = torch.empty(n, dtype=torch.float64, device=dev)
+        with op._ctx.tuned(**forms[form]):
+            l0 = launches()
+            lo.mul(res, op, x, 1.0, 0.0)
+            assert launches() - l0 == 1, form
+        return res
+
+    shared = device.get_ctx(dev)
+    alone, own = {}, []
+    for form in forms:                                   # the reference: operator and apply on a ctx of their own
+        own.append(device.Context(dev.index))            # (kept to the end of the test: a ctx must outlive its operators)
+        device._ctxs[dev.index] = own[-1]
+        try:
+            op = make()
+            assert op._ctx is own[-1]
+            alone[form] = apply(op, form)
+            torch.cuda.synchronize()
+        finally:
+            device._ctxs[dev.index] = shared
+        del op
+        gc.collect()                                     # an operator sits in a reference cycle: destroyed here, before its ctx
+    assert bool(torch.isfinite(alone["slice"]).all()) and not torch.equal(alone["slice"], torch.zeros_like(x))
+    op = make()
+    assert op._ctx is shared
+    for k in range(8):
+        form = ("slice", "persist")[k % 2]
+        assert torch.equal(apply(op, form), alone[form]), (k, form)
+    # (the two forms sum the dots in different fixed orders: they agree to rounding, as the persistent tests assert)
+    assert rel(alone["persist"].cpu().numpy(), alone["slice"].cpu().numpy()) <= 1e-12
+
+
 @pytest.mark.parametrize("kind", ["inv", "fwd", "lsr1"])
 def test_push_of_a_pair_that_lives_in_the_operators_own_storage(lo, dev, kind):
     """the streaming push! schedules read the caller's s and y while kernels store into the slot being
