@@ -905,7 +905,7 @@ __global__ void __launch_bounds__(kBlock) sweep_block_kernel(SweepArgs a) {
 }
 
 template <typename T, bool LDL>
-int32_t launch_sweep(mxlo_ctx *ctx, const SweepArgs &a) {
+int32_t launch_sweep_as(mxlo_ctx *ctx, const SweepArgs &a) {
   int64_t grid = a.nchunks;
   if (a.epi) {
     const int64_t d_lo = a.r0 + (int64_t)a.gd * NB, dl = a.r1 - d_lo < NB ? a.r1 - d_lo : NB;
@@ -924,43 +924,79 @@ int32_t launch_sweep(mxlo_ctx *ctx, const SweepArgs &a) {
   return MXLO_OK;
 }
 
-// One sweep: solves op(T) x = rhs. `ascending` = (lower, N) or (upper, T); the panel of a transposed solve is a block ROW.
-// first: the right-hand side comes from v (else z holds it and its first block is already solved). turn: after the last
-// block, multiply it by its transposed inverse once more (the first block of the Cholesky back sweep). epi: fuse the
-// alpha/beta epilogue into the last launch. dsc (opLDL): the pivots; they multiply the turn-around block between its two
-// products and, in a sweep that continues (!first), every other block as the first launch reads it. tdinv (opLU): the
-// turn-around multiplies by the last block of THESE inverses, transposed like the sweep itself, instead. gather / scatter
-// (opLU): the permutation the first launch reads v through / the epilogue writes res through. unit_lower (opLU): a lower
-// triangle is L, with an implicit unit diagonal, and the turn-around block is the OTHER triangle of the same storage.
-// grp.kb > 0: the block form — v and res are n x kb (ldv, ldr), z is n x kb with column stride n; the same launches.
-// A refined apply (xacc, block form only): first with v == NULL takes the right-hand side z already holds (the residual),
-// and the launch with epi ends as xmode says (SweepArgs) instead of writing res.
+// the kernels of opLDL are those of a launch that carries the pivots
+template <typename T>
+int32_t launch_sweep(mxlo_ctx *ctx, const SweepArgs &a) {
+  return a.dsc ? launch_sweep_as<T, true>(ctx, a) : launch_sweep_as<T, false>(ctx, a);
+}
+
+// A sweep is described by three structs, written at the call as designated initialisers that name what is not the default.
+
+// the columns of a block apply that one chain of launches takes; kb == 0: a vector apply, on the vector kernels
 struct Group {
-  int kb = 0;
+  int kb = 0;                          // kb > 0: v and res are n x kb (ldv, ldr), z is n x kb with column stride n; the same launches
   int64_t ldr = 0, ldv = 0;
 };
 
-template <typename T, bool LDL = false>
-int32_t sweep(mxlo_ctx *ctx, const T *Tm, int64_t ld, int64_t n, bool upper, bool trans, const double *dinv, double *z,
-              const T *v, bool first, bool turn, bool epi, T *res, double alpha, double beta, const double *dsc = nullptr,
-              const double *tdinv = nullptr, const int *gather = nullptr, const int *scatter = nullptr, bool unit_lower = false,
-              Group grp = {}, double *xacc = nullptr, int xmode = 0) {
-  const int64_t nb = (n + NB - 1) / NB;
-  const bool asc = upper == trans;
+// what the sweeps and the reflector chains of one apply, or of one group of its columns, share
+template <typename T>
+struct Apply {
+  mxlo_ctx *ctx;
+  T *res;                              // written by the launch with the epilogue only: res = alpha x + beta res
+  double alpha, beta;
+  double *z;                           // the work matrix: the right-hand side turning into the solution
+  Group grp = {};
+  double *xacc = nullptr;              // a refined apply (block form only): the iterate; the launch with the epilogue then ends as
+  int xmode = 0;                       // xmode says (SweepArgs) instead of writing res
+};
+
+// the triangle of a sweep and the inverses of its diagonal blocks
+template <typename T>
+struct Tri {
+  const T *Tm;
+  int64_t ld, n;
+  bool upper = false;
+  // opLU, pivoted opLDL: a lower triangle is L, with an implicit unit diagonal, and the turn-around block (Sweep::tdinv) is the
+  // OTHER triangle of the same storage
+  bool unit_lower = false;
+  const double *dinv;                  // the stored inverses of the NB x NB diagonal blocks, one per block column
+};
+
+// One sweep: solves op(T) x = rhs. `ascending` = (lower, N) or (upper, T); the panel of a transposed solve is a block ROW.
+template <typename T>
+struct Sweep {
+  bool trans = false;
+  const T *v = nullptr;                // the right-hand side of a first sweep; NULL (a refined apply): z already holds it, the residual
+  bool first = true;                   // the right-hand side comes from v; else z holds it and its first block is already solved
+  bool turn = false;                   // after the last block, multiply it by its transposed inverse once more (the first block of
+                                       // the Cholesky back sweep)
+  bool epi = false;                    // fuse the alpha/beta epilogue into the last launch
+  const double *dsc = nullptr;         // opLDL: the pivots; they multiply the turn-around block between its two products and, in a
+                                       // sweep that continues (!first), every other block as the first launch reads it
+  const double *tdinv = nullptr;       // opLU: the turn-around multiplies by the last block of THESE inverses, transposed like the
+                                       // sweep itself, instead
+  const int *gather = nullptr;         // the permutation the first launch reads v through ...
+  const int *scatter = nullptr;        // ... and the one the epilogue writes res through
+};
+
+template <typename T>
+int32_t sweep(const Apply<T> &ap, const Tri<T> &t, const Sweep<T> &s) {
+  const int64_t n = t.n, nb = (n + NB - 1) / NB;
+  const bool asc = t.upper == s.trans;
   SweepArgs a{};
-  a.Tm = Tm; a.ld = ld; a.n = n; a.z = z; a.rowpanel = trans; a.dinv_t = trans; a.res = res; a.alpha = alpha; a.beta = beta;
-  a.dsc = dsc; a.gather = gather; a.scatter = scatter; a.dinv2_t = tdinv ? trans : 1;
-  a.kb = grp.kb; a.ldr = grp.ldr; a.ldv = grp.ldv; a.xacc = xacc; a.xmode = xmode;
-  const bool upper2 = tdinv ? !upper : upper;
-  a.tri_upper = upper; a.tri_unit = unit_lower && !upper; a.tri2_upper = upper2; a.tri2_unit = unit_lower && !upper2;
+  a.Tm = t.Tm; a.ld = t.ld; a.n = n; a.z = ap.z; a.rowpanel = s.trans; a.dinv_t = s.trans; a.res = ap.res; a.alpha = ap.alpha;
+  a.beta = ap.beta; a.dsc = s.dsc; a.gather = s.gather; a.scatter = s.scatter; a.dinv2_t = s.tdinv ? s.trans : 1;
+  a.kb = ap.grp.kb; a.ldr = ap.grp.ldr; a.ldv = ap.grp.ldv; a.xacc = ap.xacc; a.xmode = ap.xmode;
+  const bool upper2 = s.tdinv ? !t.upper : t.upper;
+  a.tri_upper = t.upper; a.tri_unit = t.unit_lower && !t.upper; a.tri2_upper = upper2; a.tri2_unit = t.unit_lower && !upper2;
   const int64_t kfirst = asc ? 0 : nb - 1, klast = asc ? nb - 1 : 0, step = asc ? 1 : -1;
-  const double *tblock = (tdinv ? tdinv : dinv) + klast * NB2;
-  if (first) {                                            // z = v, and the first block solved
-    a.v = v; a.xl = 0; a.r0 = 0; a.r1 = n; a.nchunks = (int)nb; a.gd = (int)kfirst;
-    a.dinv = dinv + kfirst * NB2;
-    a.dinv2 = (turn && nb == 1) ? tblock : nullptr;
-    a.epi = epi && nb == 1;
-    MXLO_TRY((launch_sweep<T, LDL>(ctx, a)));
+  const double *tblock = (s.tdinv ? s.tdinv : t.dinv) + klast * NB2;
+  if (s.first) {                                          // z = v, and the first block solved
+    a.v = s.v; a.xl = 0; a.r0 = 0; a.r1 = n; a.nchunks = (int)nb; a.gd = (int)kfirst;
+    a.dinv = t.dinv + kfirst * NB2;
+    a.dinv2 = (s.turn && nb == 1) ? tblock : nullptr;
+    a.epi = s.epi && nb == 1;
+    MXLO_TRY(launch_sweep<T>(ap.ctx, a));
     a.v = nullptr;
   }
   for (int64_t k = kfirst; k != klast; k += step) {       // panel k, then block k + step
@@ -970,11 +1006,11 @@ int32_t sweep(mxlo_ctx *ctx, const T *Tm, int64_t ld, int64_t n, bool upper, boo
     if (asc) { a.r0 = (k + 1) * NB; a.r1 = n; a.gd = 0; }
     else { a.r0 = 0; a.r1 = k * NB; a.gd = (int)(k - 1); }
     a.nchunks = (int)((a.r1 - a.r0 + NB - 1) / NB);
-    a.dinv = dinv + kn * NB2;
-    a.dinv2 = (turn && kn == klast) ? tblock : nullptr;
-    a.epi = epi && kn == klast;
-    a.zscale = LDL && !first && k == kfirst;
-    MXLO_TRY((launch_sweep<T, LDL>(ctx, a)));
+    a.dinv = t.dinv + kn * NB2;
+    a.dinv2 = (s.turn && kn == klast) ? tblock : nullptr;
+    a.epi = s.epi && kn == klast;
+    a.zscale = s.dsc && !s.first && k == kfirst;
+    MXLO_TRY(launch_sweep<T>(ap.ctx, a));
   }
   return MXLO_OK;
 }
@@ -1026,6 +1062,12 @@ int32_t disjoint(std::initializer_list<Buf> bufs, const char *what) {
   return MXLO_OK;
 }
 
+// x against each of `others`, which may overlap one another (operands that are only read)
+int32_t apart(const Buf &x, std::initializer_list<Buf> others, const char *what) {
+  for (const Buf &y : others) MXLO_TRY(disjoint({x, y}, what));
+  return MXLO_OK;
+}
+
 // the tail of a factorisation: it reads `count` info words back, the only synchronisation, which a graph capture cannot hold.
 // refuse_capture() is the last check before the device is touched, read_back() the last call of the chain.
 int32_t refuse_capture(const mxlo_ctx *ctx, const char *what) {
@@ -1040,13 +1082,18 @@ int32_t read_back(mxlo_ctx *ctx, const int32_t *info_dev, int32_t *words, int co
 }
 
 // res (rrows x k, ldr) and V (vrows x k, ldv) of an apply, columns of unit stride. A vector entry point passes vectors():
-// one column in a leading dimension of max(1, rows).
+// one column in a leading dimension of max(1, rows); a _block entry point passes columns(), and takes the block kernels
+// whatever k is.
 struct Operands {
   const void *res, *v;
   int64_t k, ldr, ldv, rrows, vrows;
+  bool block;
 };
 inline Operands vectors(const void *res, const void *v, int64_t rrows, int64_t vrows) {
-  return {res, v, 1, rrows > 1 ? rrows : 1, vrows > 1 ? vrows : 1, rrows, vrows};
+  return {res, v, 1, rrows > 1 ? rrows : 1, vrows > 1 ? vrows : 1, rrows, vrows, false};
+}
+inline Operands columns(const void *res, int64_t ldr, const void *v, int64_t ldv, int64_t k, int64_t rrows, int64_t vrows) {
+  return {res, v, k, ldr, ldv, rrows, vrows, true};
 }
 
 // res and V against the buffers an operator owns, none of which may be NULL
@@ -1137,16 +1184,27 @@ int32_t getrf_t(mxlo_ctx *ctx, const T *M, int64_t ldm, T *W, int64_t ldw, int64
 // A = P' L U. N: x = inv(U) inv(L) (P v) — v gathered, the unit lower sweep, the upper one. T: A' = U' L' P, x = P' inv(L') inv(U') v —
 // the U' sweep, the L' sweep, the epilogue scattered.
 template <typename T>
-int32_t lu_mul_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t n, const double *dinv_l, const double *dinv_u, const int *perm,
-                 double *work, const T *v, bool trans, double alpha, double beta, Group grp = {}, double *xacc = nullptr, int xmode = 0) {
+int32_t lu_mul_t(const Apply<T> &ap, const T *W, int64_t ld, int64_t n, const double *dinv_l, const double *dinv_u, const int *perm,
+                 const T *v, bool trans) {
   const bool one = n <= NB;
   const double *d1 = trans ? dinv_u : dinv_l, *d2 = trans ? dinv_l : dinv_u;
   const int *gather = (trans || !v) ? nullptr : perm, *scatter = trans ? perm : nullptr;   // a residual (!v) is already in the sweep's order
-  MXLO_TRY(sweep<T>(ctx, W, ld, n, trans, trans, d1, work, v, true, true, one, res, alpha, beta, nullptr, d2, gather, scatter, true, grp,
-                    xacc, xmode));
+  MXLO_TRY(sweep(ap, {.Tm = W, .ld = ld, .n = n, .upper = trans, .unit_lower = true, .dinv = d1},
+                 {.trans = trans, .v = v, .turn = true, .epi = one, .tdinv = d2, .gather = gather, .scatter = scatter}));
   if (one) return MXLO_OK;
-  return sweep<T>(ctx, W, ld, n, !trans, trans, d2, work, (const T *)nullptr, false, false, true, res, alpha, beta, nullptr, nullptr,
-                  nullptr, scatter, true, grp, xacc, xmode);
+  return sweep(ap, {.Tm = W, .ld = ld, .n = n, .upper = !trans, .unit_lower = true, .dinv = d2},
+               {.trans = trans, .first = false, .epi = true, .scatter = scatter});
+}
+
+// x = L^{-T} (L^{-1} v), or with the pivots d (opLDL, Lt = L D) x = Lt^{-T} (d .* (Lt^{-1} v)): the same two sweeps; where the
+// pivots come in is said at Sweep::dsc
+template <typename T>
+int32_t sym_mul_t(const Apply<T> &ap, const T *L, int64_t ld, int64_t n, const double *dinv, const double *d, const T *v) {
+  const bool one = n <= NB;                              // a single block: both products and the epilogue in one launch
+  const Tri<T> t{.Tm = L, .ld = ld, .n = n, .dinv = dinv};
+  MXLO_TRY(sweep(ap, t, {.v = v, .turn = true, .epi = one, .dsc = d}));
+  if (one) return MXLO_OK;
+  return sweep(ap, t, {.trans = true, .first = false, .epi = true, .dsc = d});
 }
 
 // LDL: the chain of mxlo_ldlt — the same launches with the LDL' diagonal step and the pivots d handed to phases (b) and (c)
@@ -1215,13 +1273,11 @@ int32_t factor(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t
   if (n == 0) return MXLO_OK;
   MXLO_REQUIRE(dinv && info_dev, MXLO_EINVAL, "%s: null storage for the block inverses / the info word", what);
   MXLO_REQUIRE(n < (1LL << 31) - NB, MXLO_ESHAPE, "%s: n = %lld is too large", what, (long long)n);
-  const int64_t es = dtype == MXLO_F64 ? 8 : 4, wb = ((n - 1) * ldw + n) * es;
-  if (M) {
-    MXLO_REQUIRE(ldm >= (n > 1 ? n : 1), MXLO_ESHAPE, "%s: ldm = %lld < n", what, (long long)ldm);
-    MXLO_REQUIRE(!bytes_overlap(M, ((n - 1) * ldm + n) * es, W, wb), MXLO_EINVAL, "%s: the factor's storage overlaps M", what);
-  }
-  if (d) MXLO_REQUIRE(!bytes_overlap(d, n * 8, W, wb) && !bytes_overlap(d, n * 8, dinv, (n + NB - 1) / NB * NB2 * 8), MXLO_EINVAL,
-                      "%s: the pivots' storage overlaps the factor or the block inverses", what);
+  if (M) MXLO_REQUIRE(ldm >= (n > 1 ? n : 1), MXLO_ESHAPE, "%s: ldm = %lld < n", what, (long long)ldm);
+  const int64_t es = esize(dtype);
+  const Buf w{W, mat_bytes(n, n, ldw, es), "the factor"};   // the block inverses are held against the pivots only
+  MXLO_TRY(disjoint({{M, M ? mat_bytes(n, n, ldm, es) : 0, "M"}, w}, what));
+  MXLO_TRY(apart({d, n * 8, "the pivots' storage"}, {w, {dinv, blocks_bytes(n), "the block inverses"}}, what));
   MXLO_TRY(refuse_capture(ctx, what));
   MXLO_DEVICE_GUARD(ctx);
   MXLO_TRY(with_real(dtype, [&]<typename T>() {
@@ -1243,66 +1299,107 @@ MXLO_API int32_t mxlo_ldlt(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t 
   return factor(ctx, dtype, M, ldm, m_rowmajor, W, ldw, n, dinv, d, info_dev, info, "mxlo_ldlt");
 }
 
-MXLO_API int32_t mxlo_trisolve_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *Tm, int64_t ld, int64_t n, int32_t upper,
-                                   int32_t op_mode, const double *dinv, double *work, const void *v, double alpha, double beta) {
+// ---------------------------------------------------------------------------------------------- the applies' entry points
+// A vector entry point and its _block form share one body, which takes the Operands. The n x k operands of the block form
+// go through the chain in groups of KB columns: one chain of launches and one read of the factor per group. A group's
+// columns of V are read completely by its first launch and its columns of res written only by its last, and the groups are
+// different columns, so res may be V (the same pointer and leading dimension).
+namespace {
+template <typename T, typename F>
+int32_t for_groups(T *res, int64_t ldr, const T *V, int64_t ldv, int64_t k, F &&apply) {
+  for (int64_t j0 = 0; j0 < k; j0 += KB) {
+    Group grp;
+    grp.kb = (int)(k - j0 < KB ? k - j0 : KB);
+    grp.ldr = ldr;
+    grp.ldv = ldv;
+    MXLO_TRY(apply(res + j0 * ldr, V + j0 * ldv, grp));
+  }
+  return MXLO_OK;
+}
+
+// The one fork between the two forms: f(res_j, V_j, grp), a generic lambda over the element type, is called once with
+// Group{} for a vector entry point, which so keeps the vector kernels, and per group of KB columns for a block one
+template <typename F>
+int32_t for_real_groups(int32_t dtype, const Operands &o, F &&f) {
+  return with_real(dtype, [&]<typename T>() {
+    if (!o.block) return f((T *)o.res, (const T *)o.v, Group{});
+    return for_groups((T *)o.res, o.ldr, (const T *)o.v, o.ldv, o.k, f);
+  });
+}
+
+int32_t trisolve_mul(mxlo_ctx *ctx, int32_t dtype, const Operands &o, const void *Tm, int64_t ld, int64_t n, int32_t upper,
+                     int32_t op_mode, const double *dinv, double *work, double alpha, double beta, const char *what) {
   bool go;
-  MXLO_TRY(check_apply(ctx, dtype, vectors(res, v, n, n), Tm, ld, n, dinv, work, "mxlo_trisolve_mul", go));
-  MXLO_TRY(check_mode(op_mode, "mxlo_trisolve_mul"));
+  MXLO_TRY(check_apply(ctx, dtype, o, Tm, ld, n, dinv, work, what, go));
+  MXLO_TRY(check_mode(op_mode, what));
+  if (!go) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  const bool tr = op_mode != MXLO_OP_N, up = upper != 0;
+  return for_real_groups(dtype, o, [&]<typename T>(T *r, const T *v, Group grp) {
+    return sweep<T>({ctx, r, alpha, beta, work, grp}, {.Tm = (const T *)Tm, .ld = ld, .n = n, .upper = up, .dinv = dinv},
+                    {.trans = tr, .v = v, .epi = true});
+  });
+}
+
+// mxlo_chol_mul* and, with the pivots d, mxlo_ldl_mul*
+int32_t sym_mul(mxlo_ctx *ctx, int32_t dtype, const Operands &o, const void *L, int64_t ld, int64_t n, const double *dinv,
+                const double *d, bool ldl, double *work, double alpha, double beta, const char *what) {
+  bool go;
+  MXLO_TRY(check_apply(ctx, dtype, o, L, ld, n, dinv, work, what, go));
+  if (ldl && go) MXLO_TRY(check_owned(dtype, o, {{d, n * 8, "the pivots"}}, what));
+  if (!go) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  return for_real_groups(dtype, o, [&]<typename T>(T *r, const T *v, Group grp) {
+    return sym_mul_t<T>({ctx, r, alpha, beta, work, grp}, (const T *)L, ld, n, dinv, d, v);
+  });
+}
+
+int32_t lu_mul(mxlo_ctx *ctx, int32_t dtype, const Operands &o, const void *W, int64_t ldw, int64_t n, const double *dinv_l,
+               const double *dinv_u, const int32_t *perm, double *work, int32_t op_mode, double alpha, double beta, const char *what) {
+  bool go;
+  MXLO_TRY(check_lu_apply(ctx, dtype, o, W, ldw, n, dinv_l, dinv_u, perm, work, what, go));
+  MXLO_TRY(check_mode(op_mode, what));
   if (!go) return MXLO_OK;
   MXLO_DEVICE_GUARD(ctx);
   const bool tr = op_mode != MXLO_OP_N;
-  return with_real(dtype, [&]<typename T>() {
-    return sweep<T>(ctx, (const T *)Tm, ld, n, upper != 0, tr, dinv, work, (const T *)v, true, false, true, (T *)res, alpha, beta);
+  return for_real_groups(dtype, o, [&]<typename T>(T *r, const T *v, Group grp) {
+    return lu_mul_t<T>({ctx, r, alpha, beta, work, grp}, (const T *)W, ldw, n, dinv_l, dinv_u, perm, v, tr);
   });
 }
-
-namespace {
-template <typename T>
-int32_t chol_mul_t(mxlo_ctx *ctx, T *res, const T *L, int64_t ld, int64_t n, const double *dinv, double *work, const T *v, double alpha,
-                   double beta, Group grp = {}, double *xacc = nullptr, int xmode = 0) {
-  const bool one = n <= NB;                              // a single block: both products and the epilogue in one launch
-  MXLO_TRY(sweep<T>(ctx, L, ld, n, false, false, dinv, work, v, true, true, one, res, alpha, beta, nullptr, nullptr, nullptr, nullptr,
-                    false, grp, xacc, xmode));
-  if (one) return MXLO_OK;
-  return sweep<T>(ctx, L, ld, n, false, true, dinv, work, (const T *)nullptr, false, false, true, res, alpha, beta, nullptr, nullptr,
-                  nullptr, nullptr, false, grp, xacc, xmode);
-}
 }  // namespace
+
+MXLO_API int32_t mxlo_trisolve_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *Tm, int64_t ld, int64_t n, int32_t upper,
+                                   int32_t op_mode, const double *dinv, double *work, const void *v, double alpha, double beta) {
+  return trisolve_mul(ctx, dtype, vectors(res, v, n, n), Tm, ld, n, upper, op_mode, dinv, work, alpha, beta, "mxlo_trisolve_mul");
+}
+
+MXLO_API int32_t mxlo_trisolve_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *Tm, int64_t ld, int64_t n,
+                                         int32_t upper, int32_t op_mode, const double *dinv, double *work, const void *V, int64_t ldv,
+                                         int64_t k, double alpha, double beta) {
+  return trisolve_mul(ctx, dtype, columns(res, ldr, V, ldv, k, n, n), Tm, ld, n, upper, op_mode, dinv, work, alpha, beta,
+                      "mxlo_trisolve_mul_block");
+}
 
 MXLO_API int32_t mxlo_chol_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *L, int64_t ld, int64_t n, const double *dinv,
                                double *work, const void *v, double alpha, double beta) {
-  bool go;
-  MXLO_TRY(check_apply(ctx, dtype, vectors(res, v, n, n), L, ld, n, dinv, work, "mxlo_chol_mul", go));
-  if (!go) return MXLO_OK;
-  MXLO_DEVICE_GUARD(ctx);
-  return with_real(dtype, [&]<typename T>() {
-    return chol_mul_t<T>(ctx, (T *)res, (const T *)L, ld, n, dinv, work, (const T *)v, alpha, beta);
-  });
+  return sym_mul(ctx, dtype, vectors(res, v, n, n), L, ld, n, dinv, nullptr, false, work, alpha, beta, "mxlo_chol_mul");
 }
 
-namespace {
-// x = Lt^{-T} (d .* (Lt^{-1} v)) with Lt = L D: the two sweeps of chol_mul_t; where the pivots come in is said at sweep()
-template <typename T>
-int32_t ldl_mul_t(mxlo_ctx *ctx, T *res, const T *L, int64_t ld, int64_t n, const double *dinv, const double *d, double *work,
-                  const T *v, double alpha, double beta, Group grp = {}, double *xacc = nullptr, int xmode = 0) {
-  const bool one = n <= NB;
-  MXLO_TRY((sweep<T, true>(ctx, L, ld, n, false, false, dinv, work, v, true, true, one, res, alpha, beta, d, nullptr, nullptr, nullptr,
-                           false, grp, xacc, xmode)));
-  if (one) return MXLO_OK;
-  return sweep<T, true>(ctx, L, ld, n, false, true, dinv, work, (const T *)nullptr, false, false, true, res, alpha, beta, d, nullptr,
-                        nullptr, nullptr, false, grp, xacc, xmode);
+MXLO_API int32_t mxlo_chol_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *L, int64_t ld, int64_t n,
+                                     const double *dinv, double *work, const void *V, int64_t ldv, int64_t k, double alpha,
+                                     double beta) {
+  return sym_mul(ctx, dtype, columns(res, ldr, V, ldv, k, n, n), L, ld, n, dinv, nullptr, false, work, alpha, beta, "mxlo_chol_mul_block");
 }
-}  // namespace
 
 MXLO_API int32_t mxlo_ldl_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *L, int64_t ld, int64_t n, const double *dinv,
                               const double *d, double *work, const void *v, double alpha, double beta) {
-  bool go;
-  MXLO_TRY(check_apply(ctx, dtype, vectors(res, v, n, n), L, ld, n, dinv, work, "mxlo_ldl_mul", go, {{d, n * 8, "the pivots"}}));
-  if (!go) return MXLO_OK;
-  MXLO_DEVICE_GUARD(ctx);
-  return with_real(dtype, [&]<typename T>() {
-    return ldl_mul_t<T>(ctx, (T *)res, (const T *)L, ld, n, dinv, d, work, (const T *)v, alpha, beta);
-  });
+  return sym_mul(ctx, dtype, vectors(res, v, n, n), L, ld, n, dinv, d, true, work, alpha, beta, "mxlo_ldl_mul");
+}
+
+MXLO_API int32_t mxlo_ldl_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *L, int64_t ld, int64_t n,
+                                    const double *dinv, const double *d, double *work, const void *V, int64_t ldv, int64_t k,
+                                    double alpha, double beta) {
+  return sym_mul(ctx, dtype, columns(res, ldr, V, ldv, k, n, n), L, ld, n, dinv, d, true, work, alpha, beta, "mxlo_ldl_mul_block");
 }
 
 MXLO_API int32_t mxlo_getrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, void *W, int64_t ldw, int64_t n, double *dinv_l,
@@ -1329,93 +1426,14 @@ MXLO_API int32_t mxlo_getrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t
 MXLO_API int32_t mxlo_lu_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t n, const double *dinv_l,
                              const double *dinv_u, const int32_t *perm, double *work, const void *v, int32_t op_mode, double alpha,
                              double beta) {
-  bool go;
-  MXLO_TRY(check_lu_apply(ctx, dtype, vectors(res, v, n, n), W, ldw, n, dinv_l, dinv_u, perm, work, "mxlo_lu_mul", go));
-  MXLO_TRY(check_mode(op_mode, "mxlo_lu_mul"));
-  if (!go) return MXLO_OK;
-  MXLO_DEVICE_GUARD(ctx);
-  const bool tr = op_mode != MXLO_OP_N;
-  return with_real(dtype, [&]<typename T>() {
-    return lu_mul_t<T>(ctx, (T *)res, (const T *)W, ldw, n, dinv_l, dinv_u, perm, work, (const T *)v, tr, alpha, beta);
-  });
-}
-
-// ---------------------------------------------------------------------------------------------- block entry points
-// The n x k operands go through the chain in groups of KB columns: one chain of launches and one read of the factor per
-// group. A group's columns of V are read completely by its first launch and its columns of res written only by its last,
-// and the groups are different columns, so res may be V (the same pointer and leading dimension).
-namespace {
-template <typename T, typename F>
-int32_t for_groups(T *res, int64_t ldr, const T *V, int64_t ldv, int64_t k, F &&apply) {
-  for (int64_t j0 = 0; j0 < k; j0 += KB) {
-    Group grp;
-    grp.kb = (int)(k - j0 < KB ? k - j0 : KB);
-    grp.ldr = ldr;
-    grp.ldv = ldv;
-    MXLO_TRY(apply(res + j0 * ldr, V + j0 * ldv, grp));
-  }
-  return MXLO_OK;
-}
-
-// with_real and for_groups in one: f(res_j, V_j, grp), a generic lambda over the element type, per group of KB columns
-template <typename F>
-int32_t for_real_groups(int32_t dtype, void *res, int64_t ldr, const void *V, int64_t ldv, int64_t k, F &&f) {
-  return with_real(dtype, [&]<typename T>() { return for_groups((T *)res, ldr, (const T *)V, ldv, k, f); });
-}
-}  // namespace
-
-MXLO_API int32_t mxlo_trisolve_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *Tm, int64_t ld, int64_t n,
-                                         int32_t upper, int32_t op_mode, const double *dinv, double *work, const void *V, int64_t ldv,
-                                         int64_t k, double alpha, double beta) {
-  bool go;
-  MXLO_TRY(check_apply(ctx, dtype, Operands{res, V, k, ldr, ldv, n, n}, Tm, ld, n, dinv, work, "mxlo_trisolve_mul_block", go));
-  MXLO_TRY(check_mode(op_mode, "mxlo_trisolve_mul_block"));
-  if (!go) return MXLO_OK;
-  MXLO_DEVICE_GUARD(ctx);
-  const bool tr = op_mode != MXLO_OP_N, up = upper != 0;
-  return for_real_groups(dtype, res, ldr, V, ldv, k, [&]<typename T>(T *r, const T *v, Group grp) {
-    return sweep<T>(ctx, (const T *)Tm, ld, n, up, tr, dinv, work, v, true, false, true, r, alpha, beta, nullptr, nullptr, nullptr, nullptr,
-                    false, grp);
-  });
-}
-
-MXLO_API int32_t mxlo_chol_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *L, int64_t ld, int64_t n,
-                                     const double *dinv, double *work, const void *V, int64_t ldv, int64_t k, double alpha,
-                                     double beta) {
-  bool go;
-  MXLO_TRY(check_apply(ctx, dtype, Operands{res, V, k, ldr, ldv, n, n}, L, ld, n, dinv, work, "mxlo_chol_mul_block", go));
-  if (!go) return MXLO_OK;
-  MXLO_DEVICE_GUARD(ctx);
-  return for_real_groups(dtype, res, ldr, V, ldv, k, [&]<typename T>(T *r, const T *v, Group grp) {
-    return chol_mul_t<T>(ctx, r, (const T *)L, ld, n, dinv, work, v, alpha, beta, grp);
-  });
-}
-
-MXLO_API int32_t mxlo_ldl_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *L, int64_t ld, int64_t n,
-                                    const double *dinv, const double *d, double *work, const void *V, int64_t ldv, int64_t k,
-                                    double alpha, double beta) {
-  bool go;
-  MXLO_TRY(check_apply(ctx, dtype, Operands{res, V, k, ldr, ldv, n, n}, L, ld, n, dinv, work, "mxlo_ldl_mul_block", go,
-                       {{d, n * 8, "the pivots"}}));
-  if (!go) return MXLO_OK;
-  MXLO_DEVICE_GUARD(ctx);
-  return for_real_groups(dtype, res, ldr, V, ldv, k, [&]<typename T>(T *r, const T *v, Group grp) {
-    return ldl_mul_t<T>(ctx, r, (const T *)L, ld, n, dinv, d, work, v, alpha, beta, grp);
-  });
+  return lu_mul(ctx, dtype, vectors(res, v, n, n), W, ldw, n, dinv_l, dinv_u, perm, work, op_mode, alpha, beta, "mxlo_lu_mul");
 }
 
 MXLO_API int32_t mxlo_lu_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t n,
                                    const double *dinv_l, const double *dinv_u, const int32_t *perm, double *work, const void *V,
                                    int64_t ldv, int64_t k, int32_t op_mode, double alpha, double beta) {
-  bool go;
-  MXLO_TRY(check_lu_apply(ctx, dtype, Operands{res, V, k, ldr, ldv, n, n}, W, ldw, n, dinv_l, dinv_u, perm, work, "mxlo_lu_mul_block", go));
-  MXLO_TRY(check_mode(op_mode, "mxlo_lu_mul_block"));
-  if (!go) return MXLO_OK;
-  MXLO_DEVICE_GUARD(ctx);
-  const bool tr = op_mode != MXLO_OP_N;
-  return for_real_groups(dtype, res, ldr, V, ldv, k, [&]<typename T>(T *r, const T *v, Group grp) {
-    return lu_mul_t<T>(ctx, r, (const T *)W, ldw, n, dinv_l, dinv_u, perm, work, v, tr, alpha, beta, grp);
-  });
+  return lu_mul(ctx, dtype, columns(res, ldr, V, ldv, k, n, n), W, ldw, n, dinv_l, dinv_u, perm, work, op_mode, alpha, beta,
+                "mxlo_lu_mul_block");
 }
 
 // ---------------------------------------------------------------------------------------------- iterative refinement
@@ -1573,8 +1591,8 @@ int32_t chol_refine_t(mxlo_ctx *ctx, T *res, int64_t ldr, const T *W, int64_t ld
     return refine_group<T>(
         v, steps,
         [&](const T *rhs, int xmode) {
-          if (d) return ldl_mul_t<T>(ctx, r, W, ld, n, dinv, d, z, rhs, alpha, beta, grp, xmode ? x : nullptr, xmode);
-          return chol_mul_t<T>(ctx, r, W, ld, n, dinv, z, rhs, alpha, beta, grp, xmode ? x : nullptr, xmode);
+          return sym_mul_t<T>({.ctx = ctx, .res = r, .alpha = alpha, .beta = beta, .z = z, .grp = grp, .xacc = xmode ? x : nullptr, .xmode = xmode},
+                              W, ld, n, dinv, d, rhs);
         },
         [&]() { return launch_residual<T>(ctx, 0, W, ld, dg, n, v, ldv, nullptr, x, z, grp.kb); });
   });
@@ -1589,7 +1607,8 @@ int32_t lu_refine_t(mxlo_ctx *ctx, T *res, int64_t ldr, const T *W, int64_t ld, 
     return refine_group<T>(
         v, steps,
         [&](const T *rhs, int xmode) {
-          return lu_mul_t<T>(ctx, r, W, ld, n, dinv_l, dinv_u, perm, z, rhs, trans, alpha, beta, grp, xmode ? x : nullptr, xmode);
+          return lu_mul_t<T>({.ctx = ctx, .res = r, .alpha = alpha, .beta = beta, .z = z, .grp = grp, .xacc = xmode ? x : nullptr, .xmode = xmode},
+                             W, ld, n, dinv_l, dinv_u, perm, rhs, trans);
         },
         [&]() { return launch_residual<T>(ctx, trans ? 2 : 1, A2, lda, (const T *)nullptr, n, v, ldv, trans ? nullptr : perm, x, z, grp.kb); });
   });
@@ -1598,7 +1617,7 @@ int32_t lu_refine_t(mxlo_ctx *ctx, T *res, int64_t ldr, const T *W, int64_t ld, 
 int32_t sym_refine(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t n, const double *dinv,
                    const double *d, const void *dg, double *work, const void *V, int64_t ldv, int64_t k, int32_t steps, double alpha,
                    double beta, bool ldl, const char *what) {
-  const Operands o{res, V, k, ldr, ldv, n, n};
+  const Operands o = columns(res, ldr, V, ldv, k, n, n);
   bool go;
   MXLO_TRY(check_apply(ctx, dtype, o, W, ldw, n, dinv, work, what, go));
   if (ldl && go) MXLO_TRY(check_owned(dtype, o, {{d, n * 8, "the pivots"}}, what));
@@ -1619,9 +1638,9 @@ MXLO_API int32_t mxlo_sym_snapshot(mxlo_ctx *ctx, int32_t dtype, const void *M, 
   if (n == 0) return MXLO_OK;
   MXLO_REQUIRE(M && dg && ldm >= (n > 1 ? n : 1), MXLO_EINVAL, "%s: null operand or ldm = %lld < n", what, (long long)ldm);
   MXLO_REQUIRE(n < (1LL << 31) - NB, MXLO_ESHAPE, "%s: n = %lld is too large", what, (long long)n);
-  const int64_t es = dtype == MXLO_F64 ? 8 : 4, wb = ((n - 1) * ldw + n) * es, mb = ((n - 1) * ldm + n) * es;
-  MXLO_REQUIRE(!bytes_overlap(M, mb, W, wb) && !bytes_overlap(M, mb, dg, n * es) && !bytes_overlap(dg, n * es, W, wb), MXLO_EINVAL,
-               "%s: M, the factor's storage and the diagonal vector overlap", what);
+  const int64_t es = esize(dtype);
+  MXLO_TRY(disjoint({{M, mat_bytes(n, n, ldm, es), "M"}, {W, mat_bytes(n, n, ldw, es), "the factor"}, {dg, n * es, "the diagonal vector"}},
+                    what));
   MXLO_DEVICE_GUARD(ctx);
   const unsigned nb = (unsigned)((n + NB - 1) / NB);
   return with_real(dtype, [&]<typename T>() -> int32_t {
@@ -1639,9 +1658,8 @@ MXLO_API int32_t mxlo_lu_snapshot(mxlo_ctx *ctx, int32_t dtype, const void *M, i
   if (n == 0) return MXLO_OK;
   MXLO_REQUIRE(M && perm && ldm >= (n > 1 ? n : 1), MXLO_EINVAL, "%s: null operand or ldm = %lld < n", what, (long long)ldm);
   MXLO_REQUIRE(n < (1LL << 31) - NB, MXLO_ESHAPE, "%s: n = %lld is too large", what, (long long)n);
-  const int64_t es = dtype == MXLO_F64 ? 8 : 4, ab = ((n - 1) * lda + n) * es, mb = ((n - 1) * ldm + n) * es;
-  MXLO_REQUIRE(!bytes_overlap(M, mb, A2, ab) && !bytes_overlap(perm, n * 4, A2, ab), MXLO_EINVAL,
-               "%s: the snapshot overlaps M or the permutation", what);
+  const int64_t es = esize(dtype);
+  MXLO_TRY(apart({A2, mat_bytes(n, n, lda, es), "the snapshot"}, {{M, mat_bytes(n, n, ldm, es), "M"}, {perm, n * 4, "the permutation"}}, what));
   MXLO_DEVICE_GUARD(ctx);
   const dim3 grid((unsigned)((n + kBlock - 1) / kBlock), (unsigned)(n < 1024 ? n : 1024));
   return with_real(dtype, [&]<typename T>() -> int32_t {
@@ -1661,11 +1679,10 @@ int32_t check_residual(mxlo_ctx *ctx, int32_t dtype, const double *R, const void
   if (n == 0 || k == 0) return MXLO_OK;
   MXLO_REQUIRE(R && V && X, MXLO_EINVAL, "%s: null operand", what);
   MXLO_REQUIRE(n < (1LL << 31) - NB, MXLO_ESHAPE, "%s: n = %lld is too large", what, (long long)n);
-  const int64_t es = dtype == MXLO_F64 ? 8 : 4, rb = n * k * 8;
-  MXLO_REQUIRE(!bytes_overlap(R, rb, X, rb) && !bytes_overlap(R, rb, V, ((k - 1) * ldv + n) * es) &&
-                   !bytes_overlap(R, rb, A, ((n - 1) * ld + n) * es) && !(dg && bytes_overlap(R, rb, dg, n * es)),
-               MXLO_EINVAL, "%s: R overlaps an operand it reads", what);
-  return MXLO_OK;
+  const int64_t es = esize(dtype);
+  return apart({R, n * k * 8, "R"},
+               {{X, n * k * 8, "X"}, {V, mat_bytes(n, k, ldv, es), "V"}, {A, mat_bytes(n, n, ld, es), "the matrix"}, {dg, n * es, "the diagonal"}},
+               what);
 }
 }  // namespace
 
@@ -1709,7 +1726,7 @@ MXLO_API int32_t mxlo_lu_mul_refine(mxlo_ctx *ctx, int32_t dtype, void *res, int
                                     double *work, const void *V, int64_t ldv, int64_t k, int32_t steps, int32_t op_mode, double alpha,
                                     double beta) {
   const char *what = "mxlo_lu_mul_refine";
-  const Operands o{res, V, k, ldr, ldv, n, n};
+  const Operands o = columns(res, ldr, V, ldv, k, n, n);
   bool go;
   MXLO_TRY(check_lu_apply(ctx, dtype, o, W, ldw, n, dinv_l, dinv_u, perm, work, what, go));
   MXLO_TRY(check_mode(op_mode, what));
@@ -2375,19 +2392,21 @@ int32_t reflect_chain(mxlo_ctx *ctx, QrArgs a, const T *W, int64_t ld, int64_t r
   return MXLO_OK;
 }
 
-// what the stages of an apply share, on the vector apply's work (grp.kb == 0: z (mf), then two sets of QG x NB slots) or the
-// block apply's (z (mf x KB), two sets of slots per right-hand side, then zc); zs is what the sweep with R works on
+// what the stages of an apply share, on the vector apply's work (ap.z; grp.kb == 0: z (mf), then two sets of QG x NB slots) or
+// the block apply's (z (mf x KB), two sets of slots per right-hand side, then zc); sw is the apply as the sweep with R sees it,
+// on the matrix it works on
+template <typename T>
 struct QrStages {
   QrArgs a{};
-  double *pb[2], *zs;
-  template <typename T>
-  QrStages(T *res, int64_t mf, double *work, double alpha, double beta, Group grp) {
-    const bool blk = grp.kb > 0;
+  double *pb[2];
+  Apply<T> sw;
+  QrStages(const Apply<T> &ap, int64_t mf) : sw(ap) {
+    const bool blk = ap.grp.kb > 0;
     const int64_t slots = (int64_t)(blk ? KB : 1) * QG * NB, zlen = (blk ? KB : 1) * mf;
-    pb[0] = work + zlen; pb[1] = work + zlen + slots;
-    a.z = work; a.res = res; a.alpha = alpha; a.beta = beta;
-    a.kb = grp.kb; a.ldr = grp.ldr; a.ldv = grp.ldv; a.zc = blk ? pb[1] + slots : nullptr;
-    zs = blk ? a.zc : work;
+    pb[0] = ap.z + zlen; pb[1] = ap.z + zlen + slots;
+    a.z = ap.z; a.res = ap.res; a.alpha = ap.alpha; a.beta = ap.beta;
+    a.kb = ap.grp.kb; a.ldr = ap.grp.ldr; a.ldv = ap.grp.ldv; a.zc = blk ? pb[1] + slots : nullptr;
+    sw.z = blk ? a.zc : ap.z;
   }
 };
 
@@ -2396,18 +2415,15 @@ struct QrStages {
 // launches either way, for a vector and for a group of grp.kb columns alike; the sweep with R keeps its own kernel and, for a
 // group, its own nf x kb matrix zc. jpvt (the pivoted form): nf is the rank, nfull the number of columns.
 template <typename T>
-int32_t qr_mul_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t mf, int64_t nf, const double *tfac, const double *dinv,
-                 double *work, const T *v, bool trans, double alpha, double beta, Group grp = {}, const int *jpvt = nullptr,
-                 int64_t nfull = 0) {
-  const QrStages s(res, mf, work, alpha, beta, grp);
+int32_t qr_mul_t(const Apply<T> &ap, const T *W, int64_t ld, int64_t mf, int64_t nf, const double *tfac, const double *dinv, const T *v,
+                 bool trans, const int *jpvt, int64_t nfull) {
+  const QrStages<T> s(ap, mf);
+  const Tri<T> r{.Tm = W, .ld = ld, .n = nf, .upper = true, .dinv = dinv};
   const Fill fill{jpvt, nf, nfull};
-  if (trans)
-    MXLO_TRY(sweep<T>(ctx, W, ld, nf, true, true, dinv, s.zs, v, true, false, false, res, alpha, beta, nullptr, nullptr, jpvt, nullptr, false,
-                      grp));
-  MXLO_TRY(reflect_chain<T>(ctx, s.a, W, ld, mf, nf, tfac, s.pb, trans, v, nullptr, jpvt ? &fill : nullptr));
+  if (trans) MXLO_TRY(sweep(s.sw, r, {.trans = true, .v = v, .gather = jpvt}));
+  MXLO_TRY(reflect_chain<T>(ap.ctx, s.a, W, ld, mf, nf, tfac, s.pb, trans, v, nullptr, jpvt ? &fill : nullptr));
   if (trans) return MXLO_OK;
-  return sweep<T>(ctx, W, ld, nf, true, false, dinv, s.zs, (const T *)nullptr, true, false, true, res, alpha, beta, nullptr, nullptr,
-                  nullptr, jpvt, false, grp);
+  return sweep(s.sw, r, {.epi = true, .scatter = jpvt});
 }
 
 // ---------------------------------------------------------------------------------------------- cod / pinv_mul
@@ -2451,14 +2467,13 @@ int32_t cod_factor_t(mxlo_ctx *ctx, const T *W, int64_t ldw, int64_t nf, int64_t
 // z[0:r], Q1 [w; 0]. work is qr_mul_t's, for a vector or for a group: the second chain's z has nf <= mf rows, its sweep
 // matrix r <= nf, and both chains use the same two sets of slots, so nothing more is needed.
 template <typename T>
-int32_t pinv_mul_t(mxlo_ctx *ctx, T *res, const T *W, int64_t ld, int64_t mf, int64_t nf, const double *tfac, const int *jpvt, int64_t r,
-                   const T *W2, const double *tfac2, const double *dinv2, double *work, const T *v, bool trans, double alpha, double beta,
-                   Group grp = {}) {
-  const QrStages s(res, mf, work, alpha, beta, grp);
+int32_t pinv_mul_t(const Apply<T> &ap, const T *W, int64_t ld, int64_t mf, int64_t nf, const double *tfac, const int *jpvt, int64_t r,
+                   const T *W2, const double *tfac2, const double *dinv2, const T *v, bool trans) {
+  mxlo_ctx *ctx = ap.ctx;
+  const QrStages<T> s(ap, mf);
   if (!trans) MXLO_TRY(reflect_chain<T>(ctx, s.a, W, ld, mf, r, tfac, s.pb, false, v));
   else MXLO_TRY(reflect_chain<T>(ctx, s.a, W2, nf, nf, r, tfac2, s.pb, false, v, jpvt));
-  MXLO_TRY(sweep<T>(ctx, W2, nf, r, true, !trans, dinv2, s.zs, (const T *)nullptr, true, false, false, res, alpha, beta, nullptr, nullptr,
-                    nullptr, nullptr, false, grp));
+  MXLO_TRY(sweep(s.sw, {.Tm = W2, .ld = nf, .n = r, .upper = true, .dinv = dinv2}, {.trans = !trans}));
   if (!trans) return reflect_chain<T>(ctx, s.a, W2, nf, nf, r, tfac2, s.pb, true, (const T *)nullptr, jpvt);
   return reflect_chain<T>(ctx, s.a, W, ld, mf, r, tfac, s.pb, true, (const T *)nullptr);
 }
@@ -2844,45 +2859,79 @@ int32_t check_qr_shape(mxlo_ctx *ctx, int32_t dtype, int32_t op_mode, int64_t ld
   return MXLO_OK;
 }
 
+// res and V of a rectangular apply: columns() with the rows op_mode gives them. A vector entry point passes qr_vectors(): k = 1 in the
+// leading dimension mf, which holds either operand.
 inline Operands qr_operands(const void *res, int64_t ldr, const void *V, int64_t ldv, int64_t k, int64_t mf, int64_t nf, int32_t op_mode) {
   const bool tr = op_mode != MXLO_OP_N;
-  return {res, V, k, ldr, ldv, tr ? mf : nf, tr ? nf : mf};
+  return columns(res, ldr, V, ldv, k, tr ? mf : nf, tr ? nf : mf);
+}
+inline Operands qr_vectors(const void *res, const void *v, int64_t mf, int64_t nf, int32_t op_mode) {
+  Operands o = qr_operands(res, mf, v, mf, 1, mf, nf, op_mode);
+  o.block = false;
+  return o;
 }
 
-// mxlo_qr_mul* and, with jpvt and the rank, mxlo_qrp_mul*; block: the work space is qr_block_work's. The T factors and the
+// mxlo_qr_mul* and, with jpvt and the rank, mxlo_qrp_mul*; o.block: the work space is qr_block_work's. The T factors and the
 // block inverses count as those of all nf columns, whatever the rank.
-int32_t check_qr_apply(mxlo_ctx *ctx, int32_t dtype, const void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf, int64_t nf,
+int32_t check_qr_apply(mxlo_ctx *ctx, int32_t dtype, const Operands &o, const void *W, int64_t ldw, int64_t mf, int64_t nf,
                        const double *tfac, const double *dinv, bool pivoted, const int32_t *jpvt, int64_t rank, const double *work,
-                       bool block, const void *V, int64_t ldv, int64_t k, int32_t op_mode, const char *what, bool &go) {
+                       int32_t op_mode, const char *what, bool &go) {
   go = false;
   MXLO_TRY(check_qr_shape(ctx, dtype, op_mode, ldw, mf, nf, rank, pivoted ? nf : -1, what));
-  const Operands o = qr_operands(res, ldr, V, ldv, k, mf, nf, op_mode);
   MXLO_TRY(check_operands(dtype, o, false,
                           {{W, mat_bytes(mf, nf, ldw, esize(dtype)), "the factor"},
                            {tfac, blocks_bytes(nf), "the T factors"},
                            {dinv, blocks_bytes(nf), "the block inverses"},
-                           {work, (block ? qr_block_work(mf, nf) : qr_work(mf)) * 8, "the work space"}},
+                           {work, (o.block ? qr_block_work(mf, nf) : qr_work(mf)) * 8, "the work space"}},
                           what, go));
   return pivoted && go ? check_owned(dtype, o, {{jpvt, nf * 4, "the permutation"}}, what) : MXLO_OK;
 }
 
 // mxlo_pinv_mul*: rank < nf (rank == nf is mxlo_qrp_mul's), and both factors; the T factors and the block inverses of both
 // count as those of `rank` columns
-int32_t check_pinv(mxlo_ctx *ctx, int32_t dtype, const void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf, int64_t nf,
-                   const double *tfac, const int32_t *jpvt, int64_t rank, const void *W2, const double *tfac2, const double *dinv2,
-                   const double *work, bool block, const void *V, int64_t ldv, int64_t k, int32_t op_mode, const char *what, bool &go) {
+int32_t check_pinv(mxlo_ctx *ctx, int32_t dtype, const Operands &o, const void *W, int64_t ldw, int64_t mf, int64_t nf, const double *tfac,
+                   const int32_t *jpvt, int64_t rank, const void *W2, const double *tfac2, const double *dinv2, const double *work,
+                   int32_t op_mode, const char *what, bool &go) {
   go = false;
   MXLO_TRY(check_qr_shape(ctx, dtype, op_mode, ldw, mf, nf, rank, nf - 1, what));
   const int64_t es = esize(dtype);
-  return check_operands(dtype, qr_operands(res, ldr, V, ldv, k, mf, nf, op_mode), false,
+  return check_operands(dtype, o, false,
                         {{W, mat_bytes(mf, nf, ldw, es), "the factor"},
                          {tfac, blocks_bytes(rank), "the T factors"},
                          {jpvt, nf * 4, "the permutation"},
                          {W2, nf * rank * es, "the second factor"},
                          {tfac2, blocks_bytes(rank), "the second T factors"},
                          {dinv2, blocks_bytes(rank), "the block inverses"},
-                         {work, (block ? qr_block_work(mf, nf) : qr_work(mf)) * 8, "the work space"}},
+                         {work, (o.block ? qr_block_work(mf, nf) : qr_work(mf)) * 8, "the work space"}},
                         what, go);
+}
+
+// the one body of mxlo_qr_mul* and, pivoted, of mxlo_qrp_mul*, where the chain takes the leading `rank` columns
+int32_t qr_mul(mxlo_ctx *ctx, int32_t dtype, const Operands &o, const void *W, int64_t ldw, int64_t mf, int64_t nf, const double *tfac,
+               const double *dinv, bool pivoted, const int32_t *jpvt, int64_t rank, double *work, int32_t op_mode, double alpha,
+               double beta, const char *what) {
+  bool go;
+  MXLO_TRY(check_qr_apply(ctx, dtype, o, W, ldw, mf, nf, tfac, dinv, pivoted, jpvt, rank, work, op_mode, what, go));
+  if (!go) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  const bool tr = op_mode != MXLO_OP_N;
+  return for_real_groups(dtype, o, [&]<typename T>(T *r, const T *v, Group grp) {
+    return qr_mul_t<T>({ctx, r, alpha, beta, work, grp}, (const T *)W, ldw, mf, pivoted ? rank : nf, tfac, dinv, v, tr,
+                       pivoted ? jpvt : nullptr, nf);
+  });
+}
+
+int32_t pinv_mul(mxlo_ctx *ctx, int32_t dtype, const Operands &o, const void *W, int64_t ldw, int64_t mf, int64_t nf, const double *tfac,
+                 const int32_t *jpvt, int64_t rank, const void *W2, const double *tfac2, const double *dinv2, double *work,
+                 int32_t op_mode, double alpha, double beta, const char *what) {
+  bool go;
+  MXLO_TRY(check_pinv(ctx, dtype, o, W, ldw, mf, nf, tfac, jpvt, rank, W2, tfac2, dinv2, work, op_mode, what, go));
+  if (!go) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  const bool tr = op_mode != MXLO_OP_N;
+  return for_real_groups(dtype, o, [&]<typename T>(T *r, const T *v, Group grp) {
+    return pinv_mul_t<T>({ctx, r, alpha, beta, work, grp}, (const T *)W, ldw, mf, nf, tfac, jpvt, rank, (const T *)W2, tfac2, dinv2, v, tr);
+  });
 }
 }  // namespace
 
@@ -2912,29 +2961,15 @@ MXLO_API int32_t mxlo_geqrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t
 MXLO_API int32_t mxlo_qr_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t mf, int64_t nf,
                              const double *tfac, const double *dinv, double *work, const void *v, int32_t op_mode, double alpha,
                              double beta) {
-  bool go;
-  MXLO_TRY(check_qr_apply(ctx, dtype, res, mf, W, ldw, mf, nf, tfac, dinv, false, nullptr, 0, work, false, v, mf, 1, op_mode, "mxlo_qr_mul",
-                          go));
-  if (!go) return MXLO_OK;
-  MXLO_DEVICE_GUARD(ctx);
-  const bool tr = op_mode != MXLO_OP_N;
-  return with_real(dtype, [&]<typename T>() {
-    return qr_mul_t<T>(ctx, (T *)res, (const T *)W, ldw, mf, nf, tfac, dinv, work, (const T *)v, tr, alpha, beta);
-  });
+  return qr_mul(ctx, dtype, qr_vectors(res, v, mf, nf, op_mode), W, ldw, mf, nf, tfac, dinv, false, nullptr, 0, work, op_mode, alpha, beta,
+                "mxlo_qr_mul");
 }
 
 MXLO_API int32_t mxlo_qr_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf,
                                    int64_t nf, const double *tfac, const double *dinv, double *work, const void *V, int64_t ldv,
                                    int64_t k, int32_t op_mode, double alpha, double beta) {
-  bool go;
-  MXLO_TRY(check_qr_apply(ctx, dtype, res, ldr, W, ldw, mf, nf, tfac, dinv, false, nullptr, 0, work, true, V, ldv, k, op_mode,
-                          "mxlo_qr_mul_block", go));
-  if (!go) return MXLO_OK;
-  MXLO_DEVICE_GUARD(ctx);
-  const bool tr = op_mode != MXLO_OP_N;
-  return for_real_groups(dtype, res, ldr, V, ldv, k, [&]<typename T>(T *r, const T *v, Group grp) {
-    return qr_mul_t<T>(ctx, r, (const T *)W, ldw, mf, nf, tfac, dinv, work, v, tr, alpha, beta, grp);
-  });
+  return qr_mul(ctx, dtype, qr_operands(res, ldr, V, ldv, k, mf, nf, op_mode), W, ldw, mf, nf, tfac, dinv, false, nullptr, 0, work,
+                op_mode, alpha, beta, "mxlo_qr_mul_block");
 }
 
 MXLO_API int32_t mxlo_geqp3(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t ldm, int32_t m_trans, void *W, int64_t ldw, int64_t mf,
@@ -2972,29 +3007,15 @@ MXLO_API int32_t mxlo_geqp3(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t
 MXLO_API int32_t mxlo_qrp_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t mf, int64_t nf,
                               const double *tfac, const double *dinv, const int32_t *jpvt, int64_t rank, double *work, const void *v,
                               int32_t op_mode, double alpha, double beta) {
-  bool go;
-  MXLO_TRY(check_qr_apply(ctx, dtype, res, mf, W, ldw, mf, nf, tfac, dinv, true, jpvt, rank, work, false, v, mf, 1, op_mode, "mxlo_qrp_mul",
-                          go));
-  if (!go) return MXLO_OK;
-  MXLO_DEVICE_GUARD(ctx);
-  const bool tr = op_mode != MXLO_OP_N;
-  return with_real(dtype, [&]<typename T>() {
-    return qr_mul_t<T>(ctx, (T *)res, (const T *)W, ldw, mf, rank, tfac, dinv, work, (const T *)v, tr, alpha, beta, Group{}, jpvt, nf);
-  });
+  return qr_mul(ctx, dtype, qr_vectors(res, v, mf, nf, op_mode), W, ldw, mf, nf, tfac, dinv, true, jpvt, rank, work, op_mode, alpha, beta,
+                "mxlo_qrp_mul");
 }
 
 MXLO_API int32_t mxlo_qrp_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf,
                                     int64_t nf, const double *tfac, const double *dinv, const int32_t *jpvt, int64_t rank, double *work,
                                     const void *V, int64_t ldv, int64_t k, int32_t op_mode, double alpha, double beta) {
-  bool go;
-  MXLO_TRY(check_qr_apply(ctx, dtype, res, ldr, W, ldw, mf, nf, tfac, dinv, true, jpvt, rank, work, true, V, ldv, k, op_mode,
-                          "mxlo_qrp_mul_block", go));
-  if (!go) return MXLO_OK;
-  MXLO_DEVICE_GUARD(ctx);
-  const bool tr = op_mode != MXLO_OP_N;
-  return for_real_groups(dtype, res, ldr, V, ldv, k, [&]<typename T>(T *r, const T *v, Group grp) {
-    return qr_mul_t<T>(ctx, r, (const T *)W, ldw, mf, rank, tfac, dinv, work, v, tr, alpha, beta, grp, jpvt, nf);
-  });
+  return qr_mul(ctx, dtype, qr_operands(res, ldr, V, ldv, k, mf, nf, op_mode), W, ldw, mf, nf, tfac, dinv, true, jpvt, rank, work, op_mode,
+                alpha, beta, "mxlo_qrp_mul_block");
 }
 
 MXLO_API int32_t mxlo_cod_factor(mxlo_ctx *ctx, int32_t dtype, const void *W, int64_t ldw, int64_t nf, int64_t rank, void *W2,
@@ -3022,31 +3043,16 @@ MXLO_API int32_t mxlo_cod_factor(mxlo_ctx *ctx, int32_t dtype, const void *W, in
 MXLO_API int32_t mxlo_pinv_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *W, int64_t ldw, int64_t mf, int64_t nf,
                                const double *tfac, const int32_t *jpvt, int64_t rank, const void *W2, const double *tfac2,
                                const double *dinv2, double *work, const void *v, int32_t op_mode, double alpha, double beta) {
-  bool go;
-  MXLO_TRY(check_pinv(ctx, dtype, res, mf, W, ldw, mf, nf, tfac, jpvt, rank, W2, tfac2, dinv2, work, false, v, mf, 1, op_mode,
-                      "mxlo_pinv_mul", go));
-  if (!go) return MXLO_OK;
-  MXLO_DEVICE_GUARD(ctx);
-  const bool tr = op_mode != MXLO_OP_N;
-  return with_real(dtype, [&]<typename T>() {
-    return pinv_mul_t<T>(ctx, (T *)res, (const T *)W, ldw, mf, nf, tfac, jpvt, rank, (const T *)W2, tfac2, dinv2, work, (const T *)v, tr, alpha,
-                         beta);
-  });
+  return pinv_mul(ctx, dtype, qr_vectors(res, v, mf, nf, op_mode), W, ldw, mf, nf, tfac, jpvt, rank, W2, tfac2, dinv2, work, op_mode, alpha,
+                  beta, "mxlo_pinv_mul");
 }
 
 MXLO_API int32_t mxlo_pinv_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *W, int64_t ldw, int64_t mf,
                                      int64_t nf, const double *tfac, const int32_t *jpvt, int64_t rank, const void *W2,
                                      const double *tfac2, const double *dinv2, double *work, const void *V, int64_t ldv, int64_t k,
                                      int32_t op_mode, double alpha, double beta) {
-  bool go;
-  MXLO_TRY(check_pinv(ctx, dtype, res, ldr, W, ldw, mf, nf, tfac, jpvt, rank, W2, tfac2, dinv2, work, true, V, ldv, k, op_mode,
-                      "mxlo_pinv_mul_block", go));
-  if (!go) return MXLO_OK;
-  MXLO_DEVICE_GUARD(ctx);
-  const bool tr = op_mode != MXLO_OP_N;
-  return for_real_groups(dtype, res, ldr, V, ldv, k, [&]<typename T>(T *r, const T *v, Group grp) {
-    return pinv_mul_t<T>(ctx, r, (const T *)W, ldw, mf, nf, tfac, jpvt, rank, (const T *)W2, tfac2, dinv2, work, v, tr, alpha, beta, grp);
-  });
+  return pinv_mul(ctx, dtype, qr_operands(res, ldr, V, ldv, k, mf, nf, op_mode), W, ldw, mf, nf, tfac, jpvt, rank, W2, tfac2, dinv2, work,
+                  op_mode, alpha, beta, "mxlo_pinv_mul_block");
 }
 
 // ---------------------------------------------------------------------------------------------- sytrf (Bunch-Kaufman)
@@ -3391,23 +3397,28 @@ __global__ void __launch_bounds__(kBlock) ldlp_dsolve_kernel(double *__restrict_
 // x = P L^{-T} inv(D) L^{-1} P' v: v gathered by perm, the unit lower sweep up, inv(D), the transposed sweep down with the
 // epilogue scattered by perm. ceil(n / 64) + 1 + ceil(n / 64) launches.
 template <typename T>
-int32_t ldlp_mul_t(mxlo_ctx *ctx, T *res, const T *L, int64_t ld, int64_t n, const double *dinv, const double *d, const double *e,
-                   const int *perm, double *work, const T *v, double alpha, double beta, Group grp = {}) {
-  MXLO_TRY(sweep<T>(ctx, L, ld, n, false, false, dinv, work, v, true, false, false, res, alpha, beta, nullptr, nullptr, perm, nullptr,
-                    true, grp));
-  hipLaunchKernelGGL(ldlp_dsolve_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, work, n, d, e,
-                     grp.kb > 0 ? grp.kb : 1);
+int32_t ldlp_mul_t(const Apply<T> &ap, const T *L, int64_t ld, int64_t n, const double *dinv, const double *d, const double *e,
+                   const int *perm, const T *v) {
+  const Tri<T> t{.Tm = L, .ld = ld, .n = n, .unit_lower = true, .dinv = dinv};
+  MXLO_TRY(sweep(ap, t, {.v = v, .gather = perm}));
+  hipLaunchKernelGGL(ldlp_dsolve_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ap.ctx->stream, ap.z, n, d, e,
+                     ap.grp.kb > 0 ? ap.grp.kb : 1);
   MXLO_LAUNCH_CHECK();
-  return sweep<T>(ctx, L, ld, n, false, true, dinv, work, (const T *)nullptr, true, false, true, res, alpha, beta, nullptr, nullptr,
-                  nullptr, perm, true, grp);
+  return sweep(ap, t, {.trans = true, .epi = true, .scatter = perm});
 }
 
 inline int64_t sytrf_perm_bytes(int64_t n) { return (2 * n + (n + NB - 1) / NB + 1) * 4; }
 
-int32_t check_ldlp_apply(mxlo_ctx *ctx, int32_t dtype, const Operands &o, const void *L, int64_t ld, int64_t n, const double *dinv,
-                         const double *d, const double *e, const int32_t *perm, const double *work, const char *what, bool &go) {
-  return check_apply(ctx, dtype, o, L, ld, n, dinv, work, what, go,
-                     {{d, n * 8, "the diagonal of D"}, {e, n * 8, "the sub-diagonal of D"}, {perm, n * 4, "the permutation"}});
+int32_t ldlp_mul(mxlo_ctx *ctx, int32_t dtype, const Operands &o, const void *L, int64_t ld, int64_t n, const double *dinv, const double *d,
+                 const double *e, const int32_t *perm, double *work, double alpha, double beta, const char *what) {
+  bool go;
+  MXLO_TRY(check_apply(ctx, dtype, o, L, ld, n, dinv, work, what, go,
+                       {{d, n * 8, "the diagonal of D"}, {e, n * 8, "the sub-diagonal of D"}, {perm, n * 4, "the permutation"}}));
+  if (!go) return MXLO_OK;
+  MXLO_DEVICE_GUARD(ctx);
+  return for_real_groups(dtype, o, [&]<typename T>(T *r, const T *v, Group grp) {
+    return ldlp_mul_t<T>({ctx, r, alpha, beta, work, grp}, (const T *)L, ld, n, dinv, d, e, perm, v);
+  });
 }
 }  // namespace
 
@@ -3439,23 +3450,11 @@ MXLO_API int32_t mxlo_sytrf(mxlo_ctx *ctx, int32_t dtype, const void *M, int64_t
 MXLO_API int32_t mxlo_ldlp_mul(mxlo_ctx *ctx, int32_t dtype, void *res, const void *L, int64_t ld, int64_t n, const double *dinv,
                                const double *d, const double *e, const int32_t *perm, double *work, const void *v, double alpha,
                                double beta) {
-  bool go;
-  MXLO_TRY(check_ldlp_apply(ctx, dtype, vectors(res, v, n, n), L, ld, n, dinv, d, e, perm, work, "mxlo_ldlp_mul", go));
-  if (!go) return MXLO_OK;
-  MXLO_DEVICE_GUARD(ctx);
-  return with_real(dtype, [&]<typename T>() {
-    return ldlp_mul_t<T>(ctx, (T *)res, (const T *)L, ld, n, dinv, d, e, perm, work, (const T *)v, alpha, beta);
-  });
+  return ldlp_mul(ctx, dtype, vectors(res, v, n, n), L, ld, n, dinv, d, e, perm, work, alpha, beta, "mxlo_ldlp_mul");
 }
 
 MXLO_API int32_t mxlo_ldlp_mul_block(mxlo_ctx *ctx, int32_t dtype, void *res, int64_t ldr, const void *L, int64_t ld, int64_t n,
                                      const double *dinv, const double *d, const double *e, const int32_t *perm, double *work,
                                      const void *V, int64_t ldv, int64_t k, double alpha, double beta) {
-  bool go;
-  MXLO_TRY(check_ldlp_apply(ctx, dtype, Operands{res, V, k, ldr, ldv, n, n}, L, ld, n, dinv, d, e, perm, work, "mxlo_ldlp_mul_block", go));
-  if (!go) return MXLO_OK;
-  MXLO_DEVICE_GUARD(ctx);
-  return for_real_groups(dtype, res, ldr, V, ldv, k, [&]<typename T>(T *r, const T *v, Group grp) {
-    return ldlp_mul_t<T>(ctx, r, (const T *)L, ld, n, dinv, d, e, perm, work, v, alpha, beta, grp);
-  });
+  return ldlp_mul(ctx, dtype, columns(res, ldr, V, ldv, k, n, n), L, ld, n, dinv, d, e, perm, work, alpha, beta, "mxlo_ldlp_mul_block");
 }

@@ -105,7 +105,51 @@ def cases_persist(lo, torch, dev):
                 del op
 
 
-SECTIONS = {"herm": cases_herm, "dense": cases_dense, "qn": cases_qn, "persist": cases_persist}
+def cases_linalg(lo, torch, dev):
+    """every apply of the factorisation operators (linalg.hip) at the smallest shapes that cross a block boundary (64), a group
+    boundary (8 columns) and a rank deficiency: both modes, k = 1 (the vector entry points), 8, 9, beta = 0 and beta != 0"""
+    def applies(tag, op, dt, g):
+        for mode, o in (("N", op), ("T", op.T)):
+            rows, cols = o.shape
+            for k in (1, 8, 9):
+                V = (torch.rand(k, cols, dtype=dt, generator=g) - 0.5).to(dev).t()
+                R = (torch.rand(k, rows, dtype=dt, generator=g) - 0.5).to(dev).t()
+                if k == 1:
+                    V, R = V[:, 0].contiguous(), R[:, 0].contiguous()
+                for name, a, b in (("b0", 1.0, 0.0), ("ab", 0.7, -0.75)):
+                    r = R.clone()
+                    lo.mul(r, o, V, a, b)
+                    yield f"linalg {tag} {str(dt)[6:]} {mode} k={k} {name}", r
+
+    for dt in (torch.float64, torch.float32):
+        for n in (1, 64, 65, 200):
+            g = torch.Generator(device="cpu").manual_seed(1000 + n)
+            B = torch.rand(n, n, dtype=torch.float64, generator=g) - 0.5
+            spd = (B @ B.t() + n * torch.eye(n, dtype=torch.float64)).to(dt)
+            sym = (B + B.t() + torch.diag(torch.arange(1, n + 1, dtype=torch.float64) * (-1.0) ** torch.arange(n))).to(dt)
+            gen = (B + 2.0 * torch.eye(n, dtype=torch.float64)).to(dt)
+            col = lambda M: M.t().contiguous().to(dev).t()                          # column-major on the device
+            for refine in (0, 2):
+                yield from applies(f"opCholesky n={n} refine={refine}", lo.opCholesky(col(spd), refine=refine), dt, g)
+                yield from applies(f"opLDL n={n} refine={refine}", lo.opLDL(col(sym), refine=refine), dt, g)
+                yield from applies(f"opLU n={n} refine={refine}", lo.opLU(col(gen), refine=refine), dt, g)
+            yield from applies(f"opLDL pivot n={n}", lo.opLDL(col(sym), pivot=True), dt, g)
+            yield from applies(f"opLU row-major n={n}", lo.opLU(gen.contiguous().to(dev)), dt, g)
+            yield from applies(f"opInverse lower n={n}", lo.opInverse(col(torch.tril(gen))), dt, g)
+            yield from applies(f"opInverse upper n={n}", lo.opInverse(col(torch.triu(gen))), dt, g)
+        for m, n, rank in ((5, 3, 2), (64, 64, 64), (129, 65, 64), (200, 129, 129), (200, 129, 65), (65, 200, 65)):
+            g = torch.Generator(device="cpu").manual_seed(m * 1000 + n + rank)
+            A = ((torch.rand(m, rank, dtype=torch.float64, generator=g) - 0.5) @
+                 (torch.rand(rank, n, dtype=torch.float64, generator=g) - 0.5)).to(dt)
+            for lay, Ad in (("col", A.t().contiguous().to(dev).t()), ("row", A.contiguous().to(dev))):
+                tag = f"{m}x{n} r={rank} {lay}"
+                if rank == min(m, n):
+                    yield from applies(f"opQR {tag}", lo.opQR(Ad), dt, g)
+                yield from applies(f"opQR pivot {tag}", lo.opQR(Ad, pivot=True), dt, g)
+                yield from applies(f"opPinv {tag}", lo.opPinv(Ad), dt, g)
+
+
+SECTIONS = {"herm": cases_herm, "dense": cases_dense, "qn": cases_qn, "persist": cases_persist, "linalg": cases_linalg}
 
 
 def run(sections):

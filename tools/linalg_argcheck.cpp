@@ -1,7 +1,9 @@
 // Host-side check of the argument checks of the factorisation entry points of linalg.hip: the three factorisations of the
-// rectangular family (mxlo_geqrf, mxlo_geqp3, mxlo_cod_factor) and their six applies, mxlo_getrf / mxlo_potrf / mxlo_ldlt, one
-// square apply per check path, and mxlo_sytrf with its two applies. Every call below is refused (null operands, bad shapes, a bad rank, overlaps, a scratch one
-// double too short), or is a no-op, before anything touches a device, so the program needs no GPU. The pointers are addresses
+// rectangular family (mxlo_geqrf, mxlo_geqp3, mxlo_cod_factor) and their six applies, mxlo_getrf / mxlo_potrf / mxlo_ldlt, the
+// square applies, mxlo_sytrf with its two applies, the snapshot and residual entry points of the refined applies, and one
+// common list of cases for both members of each of the eight vector / block pairs of applies. Every call below is refused
+// (null operands, bad shapes, a bad rank, overlaps, a scratch one double too short), or is a no-op, before anything touches
+// a device, so the program needs no GPU. The pointers are addresses
 // inside one host buffer that is never dereferenced by the library. Calls that break two rules at once pin which refusal wins.
 // Build the host code with AddressSanitizer and UBSan and run it (from the repository root):
 //
@@ -38,6 +40,7 @@ struct Args {
   int32_t *jpvt, *info_dev, *info, *rank_out;
   double *e, *panel;                                                  // mxlo_sytrf: the sub-diagonal of D, the n x 65 workspace and
   int32_t *perm;                                                      // its 2 n + ceil(n/64) + 1 words
+  double *R, *X;                                                      // the residual entry points: n x k doubles each
   int64_t slen = 0;
   Args tr() const { Args a = *this; a.op = T; a.ldr = mf; a.ldv = nf; return a; }            // the valid transposed apply
   Args sq() const { Args a = *this; a.ldr = a.ldv = n; return a; }                           // the valid square apply
@@ -70,6 +73,12 @@ int32_t pinv_mul_block(const Args &a) { return mxlo_pinv_mul_block(a.ctx, a.dtyp
 int32_t getrf(const Args &a) { return mxlo_getrf(a.ctx, a.dtype, a.M, a.ldm, a.W, a.ldw, a.n, a.dinv, a.dinv_u, a.jpvt, a.info_dev, a.info); }
 int32_t potrf(const Args &a) { return mxlo_potrf(a.ctx, a.dtype, a.M, a.ldm, a.rowmajor, a.W, a.ldw, a.n, a.dinv, a.info_dev, a.info); }
 int32_t ldlt(const Args &a) { return mxlo_ldlt(a.ctx, a.dtype, a.M, a.ldm, a.rowmajor, a.W, a.ldw, a.n, a.dinv, a.d, a.info_dev, a.info); }
+int32_t trisolve_mul_block(const Args &a) { return mxlo_trisolve_mul_block(a.ctx, a.dtype, a.res, a.ldr, a.W, a.ldw, a.n, a.upper, a.op, a.dinv, a.work, a.v, a.ldv, a.k, 1.0, 0.0); }
+int32_t chol_mul(const Args &a) { return mxlo_chol_mul(a.ctx, a.dtype, a.res, a.W, a.ldw, a.n, a.dinv, a.work, a.v, 1.0, 0.0); }
+int32_t sym_snapshot(const Args &a) { return mxlo_sym_snapshot(a.ctx, a.dtype, a.M, a.ldm, a.rowmajor, a.W, a.ldw, a.n, a.dg); }
+int32_t lu_snapshot(const Args &a) { return mxlo_lu_snapshot(a.ctx, a.dtype, a.M, a.ldm, a.jpvt, a.A2, a.lda, a.n); }
+int32_t sym_residual(const Args &a) { return mxlo_sym_residual(a.ctx, a.dtype, a.R, a.W, a.ldw, a.dg, a.n, a.v, a.ldv, a.X, a.k); }
+int32_t gen_residual(const Args &a) { return mxlo_gen_residual(a.ctx, a.dtype, a.R, a.A2, a.lda, a.n, a.v, a.ldv, a.X, a.k, a.op); }
 int32_t trisolve_mul(const Args &a) { return mxlo_trisolve_mul(a.ctx, a.dtype, a.res, a.W, a.ldw, a.n, a.upper, a.op, a.dinv, a.work, a.v, 1.0, 0.0); }
 int32_t chol_mul_block(const Args &a) { return mxlo_chol_mul_block(a.ctx, a.dtype, a.res, a.ldr, a.W, a.ldw, a.n, a.dinv, a.work, a.v, a.ldv, a.k, 1.0, 0.0); }
 int32_t ldl_mul(const Args &a) { return mxlo_ldl_mul(a.ctx, a.dtype, a.res, a.W, a.ldw, a.n, a.dinv, a.d, a.work, a.v, 1.0, 0.0); }
@@ -81,6 +90,44 @@ int32_t lu_mul_refine(const Args &a) { return mxlo_lu_mul_refine(a.ctx, a.dtype,
 int32_t sytrf(const Args &a) { return mxlo_sytrf(a.ctx, a.dtype, a.M, a.ldm, a.rowmajor, a.W, a.ldw, a.n, a.dinv, a.d, a.e, a.perm, a.panel, a.info_dev, a.info); }
 int32_t ldlp_mul(const Args &a) { return mxlo_ldlp_mul(a.ctx, a.dtype, a.res, a.W, a.ldw, a.n, a.dinv, a.d, a.e, a.perm, a.work, a.v, 1.0, 0.0); }
 int32_t ldlp_mul_block(const Args &a) { return mxlo_ldlp_mul_block(a.ctx, a.dtype, a.res, a.ldr, a.W, a.ldw, a.n, a.dinv, a.d, a.e, a.perm, a.work, a.v, a.ldv, a.k, 1.0, 0.0); }
+
+// What both members of a vector / block pair of applies are asked, so that the two forms of an operator cannot drift apart:
+// null res, null V, a leading dimension one too small, res overlapping the factor, res overlapping V without being V, the
+// no-ops, and calls that break two rules. sq: the square family (n, ldw), else the rectangular one (mf, nf, ldw; op N, whose
+// res has nf rows). A vector entry point has no ldr / ldv and no k: its no-op is n == 0, which the rectangular family refuses.
+template <typename F>
+void pair_cases(const char *name, const Args &base, F &&call, bool block, bool sq) {
+  char what[96];
+  auto run = [&](const char *c, int32_t want, auto &&change) {
+    std::snprintf(what, sizeof what, "%s, pair: %s", name, c);
+    expect(what, base, call, change, want);
+  };
+  const int64_t rows = sq ? base.n : base.mf;
+  run("null res", EINVAL_, [](Args &a) { a.res = nullptr; });
+  run("null V", EINVAL_, [](Args &a) { a.v = nullptr; });
+  run("the factor's ld one too small", ESHAPE, [&](Args &a) { a.ldw = rows - 1; });
+  run("res overlaps the factor", EINVAL_, [](Args &a) { a.res = a.W + 3; });
+  run("res ends at the factor's first element", EINVAL_, [&](Args &a) { a.res = a.W - (block ? (a.k - 1) * a.ldr : 0) - (sq ? a.n : a.nf) + 1; });
+  run("res overlaps V without being V", EINVAL_, [](Args &a) { a.res = a.v + 1; });
+  run("float: res overlaps V without being V", EINVAL_, [](Args &a) { a.dtype = F32; a.res = (double *)((float *)a.v + 1); });
+  run("ld too small + null res", ESHAPE, [&](Args &a) { a.ldw = rows - 1; a.res = nullptr; });
+  run("null V + res overlaps the factor", EINVAL_, [](Args &a) { a.v = nullptr; a.res = a.W + 3; });
+  run("res overlaps V + res overlaps the factor", EINVAL_, [](Args &a) { a.v = a.W + 1; a.res = a.W + 3; });
+  if (sq) {
+    run("n == 0 launches nothing", OK, [](Args &a) { a.n = 0; a.res = nullptr; a.v = nullptr; a.W = nullptr; });
+    run("n == 0 + ld 0", ESHAPE, [](Args &a) { a.n = 0; a.ldw = 0; });
+  } else {
+    run("nf == 0 is no no-op", ESHAPE, [](Args &a) { a.nf = 0; a.res = nullptr; a.v = nullptr; });
+  }
+  if (block) {
+    run("ldr one too small", ESHAPE, [&](Args &a) { a.ldr = (sq ? a.n : a.nf) - 1; });
+    run("ldv one too small", ESHAPE, [&](Args &a) { a.ldv = rows - 1; });
+    run("k == 0 launches nothing", OK, [](Args &a) { a.k = 0; a.res = nullptr; a.v = nullptr; });
+    run("k == 0 + ldr one too small", ESHAPE, [&](Args &a) { a.k = 0; a.ldr = (sq ? a.n : a.nf) - 1; });
+    run("ldv one too small + null V", ESHAPE, [&](Args &a) { a.ldv = rows - 1; a.v = nullptr; });
+    run("res is V in another leading dimension", EINVAL_, [](Args &a) { a.res = a.v; a.ldv = a.ldv + 1; a.k = 7; });
+  }
+}
 }  // namespace
 
 #define CASE(what, base, call, want, ...) expect(what, base, call, [&](Args &a) { __VA_ARGS__; }, want)
@@ -117,6 +164,8 @@ int main() {
   b.e = p; p += n;
   b.panel = p; p += 65 * n;
   b.perm = (int32_t *)p; p += n + 3;                    // 2 n + 4 + 1 words
+  b.R = b.work;                                         // the residual entry points borrow the work space: 8 n doubles each
+  b.X = b.work + 8 * n;
   b.info = &info;
   b.rank_out = &rank;
   double *const M = b.M, *const W = b.W, *const W2 = b.W2, *const tfac2 = b.tfac2, *const dinv2 = b.dinv2, *const scratch = b.scratch;
@@ -532,6 +581,104 @@ int main() {
   CASE("ldlp_mul_block: last column of res inside L", y, ldlp_mul_block, EINVAL_, a.res = W - 7 * n);
   CASE("ldlp_mul_block: V inside the work matrix's eighth column", y, ldlp_mul_block, EINVAL_, a.v = work + 8 * n - 1);
   CASE("ldlp_mul_block: bad ldv + null perm", y, ldlp_mul_block, ESHAPE, a.ldv = 1; a.perm = nullptr);
+
+  // ---- the snapshots and the residuals of the refined applies
+  CASE("sym_snapshot: null ctx", s, sym_snapshot, EINVAL_, a.ctx = nullptr);
+  CASE("sym_snapshot: complex dtype", s, sym_snapshot, EINVAL_, a.dtype = MXLO_C64);
+  CASE("sym_snapshot: ldw < n", s, sym_snapshot, ESHAPE, a.ldw = n - 1);
+  CASE("sym_snapshot: null W", s, sym_snapshot, EINVAL_, a.W = nullptr);
+  CASE("sym_snapshot: n == 0 launches nothing", s, sym_snapshot, OK, a.n = 0; a.M = nullptr; a.W = nullptr; a.dg = nullptr);
+  CASE("sym_snapshot: null M", s, sym_snapshot, EINVAL_, a.M = nullptr);
+  CASE("sym_snapshot: null diagonal", s, sym_snapshot, EINVAL_, a.dg = nullptr);
+  CASE("sym_snapshot: ldm one too small", s, sym_snapshot, EINVAL_, a.ldm = n - 1);
+  CASE("sym_snapshot: n too large", s, sym_snapshot, ESHAPE, a.n = a.ldw = a.ldm = 1LL << 31);
+  CASE("sym_snapshot: W is M", s, sym_snapshot, EINVAL_, a.W = M);
+  CASE("sym_snapshot: W starts at the last element of M, row-major", s, sym_snapshot, EINVAL_, a.rowmajor = 1; a.W = M + n * n - 1);
+  CASE("sym_snapshot: diagonal inside M", s, sym_snapshot, EINVAL_, a.dg = M + 7);
+  CASE("sym_snapshot: diagonal ends at the first element of W", s, sym_snapshot, EINVAL_, a.dg = W - n + 1);
+  CASE("sym_snapshot: diagonal inside W, float", s, sym_snapshot, EINVAL_, a.dtype = F32; a.dg = (double *)((float *)W + n * n - 1));
+  CASE("sym_snapshot: bad ldw + null M", s, sym_snapshot, ESHAPE, a.ldw = 1; a.M = nullptr);
+  CASE("sym_snapshot: short ldm + overlap", s, sym_snapshot, EINVAL_, a.ldm = 1; a.W = M);
+  CASE("sym_snapshot: null diagonal + too large", s, sym_snapshot, EINVAL_, a.dg = nullptr; a.n = a.ldw = a.ldm = 1LL << 31);
+  CASE("sym_snapshot: too large + overlap", s, sym_snapshot, ESHAPE, a.n = a.ldw = a.ldm = 1LL << 31; a.W = M);
+  CASE("lu_snapshot: null ctx", s, lu_snapshot, EINVAL_, a.ctx = nullptr);
+  CASE("lu_snapshot: complex dtype", s, lu_snapshot, EINVAL_, a.dtype = MXLO_C32);
+  CASE("lu_snapshot: lda < n", s, lu_snapshot, ESHAPE, a.lda = n - 1);
+  CASE("lu_snapshot: null snapshot", s, lu_snapshot, EINVAL_, a.A2 = nullptr);
+  CASE("lu_snapshot: n == 0 launches nothing", s, lu_snapshot, OK, a.n = 0; a.M = nullptr; a.A2 = nullptr; a.jpvt = nullptr);
+  CASE("lu_snapshot: null M", s, lu_snapshot, EINVAL_, a.M = nullptr);
+  CASE("lu_snapshot: null permutation", s, lu_snapshot, EINVAL_, a.jpvt = nullptr);
+  CASE("lu_snapshot: ldm one too small", s, lu_snapshot, EINVAL_, a.ldm = n - 1);
+  CASE("lu_snapshot: n too large", s, lu_snapshot, ESHAPE, a.n = a.lda = a.ldm = 1LL << 31);
+  CASE("lu_snapshot: snapshot is M", s, lu_snapshot, EINVAL_, a.A2 = M);
+  CASE("lu_snapshot: snapshot ends at the first element of M", s, lu_snapshot, EINVAL_, a.A2 = M - n * n + 1);
+  CASE("lu_snapshot: permutation inside the snapshot", s, lu_snapshot, EINVAL_, a.jpvt = (int32_t *)(s.A2 + 9));
+  CASE("lu_snapshot: permutation's last word inside the snapshot", s, lu_snapshot, EINVAL_, a.jpvt = (int32_t *)s.A2 - n + 1);
+  CASE("lu_snapshot: bad lda + null M", s, lu_snapshot, ESHAPE, a.lda = 1; a.M = nullptr);
+  CASE("lu_snapshot: short ldm + overlap", s, lu_snapshot, EINVAL_, a.ldm = 1; a.A2 = M);
+  CASE("lu_snapshot: null permutation + too large", s, lu_snapshot, EINVAL_, a.jpvt = nullptr; a.n = a.lda = a.ldm = 1LL << 31);
+  CASE("lu_snapshot: too large + overlap", s, lu_snapshot, ESHAPE, a.n = a.lda = a.ldm = 1LL << 31; a.A2 = M);
+  CASE("sym_residual: null ctx", s, sym_residual, EINVAL_, a.ctx = nullptr);
+  CASE("sym_residual: complex dtype", s, sym_residual, EINVAL_, a.dtype = MXLO_C64);
+  CASE("sym_residual: ld < n", s, sym_residual, ESHAPE, a.ldw = n - 1);
+  CASE("sym_residual: null matrix", s, sym_residual, EINVAL_, a.W = nullptr);
+  CASE("sym_residual: k < 0", s, sym_residual, ESHAPE, a.k = -1);
+  CASE("sym_residual: k == 9", s, sym_residual, ESHAPE, a.k = 9);
+  CASE("sym_residual: ldv one too small", s, sym_residual, ESHAPE, a.ldv = n - 1);
+  CASE("sym_residual: n == 0 launches nothing", s, sym_residual, OK, a.n = 0; a.R = nullptr; a.X = nullptr; a.v = nullptr; a.dg = nullptr);
+  CASE("sym_residual: k == 0 launches nothing", s, sym_residual, OK, a.k = 0; a.R = nullptr; a.X = nullptr; a.v = nullptr; a.dg = nullptr);
+  CASE("sym_residual: null R", s, sym_residual, EINVAL_, a.R = nullptr);
+  CASE("sym_residual: null V", s, sym_residual, EINVAL_, a.v = nullptr);
+  CASE("sym_residual: null X", s, sym_residual, EINVAL_, a.X = nullptr);
+  CASE("sym_residual: null diagonal", s, sym_residual, EINVAL_, a.dg = nullptr);
+  CASE("sym_residual: n too large", s, sym_residual, ESHAPE, a.n = a.ldw = a.ldv = 1LL << 31);
+  CASE("sym_residual: R is X", s, sym_residual, EINVAL_, a.R = s.X);
+  CASE("sym_residual: R ends at the first double of X", s, sym_residual, EINVAL_, a.R = s.X - 8 * n + 1);
+  CASE("sym_residual: R inside the last column of V", s, sym_residual, EINVAL_, a.R = v + 8 * n - 1);
+  CASE("sym_residual: R inside the matrix", s, sym_residual, EINVAL_, a.R = W + n * n - 1);
+  CASE("sym_residual: R inside the diagonal", s, sym_residual, EINVAL_, a.R = s.dg + n - 1);
+  CASE("sym_residual: X is V, which is allowed, + null diagonal", s, sym_residual, EINVAL_, a.X = v; a.dg = nullptr);
+  CASE("sym_residual: bad k + null matrix", s, sym_residual, EINVAL_, a.k = 9; a.W = nullptr);
+  CASE("sym_residual: short ldv + null R", s, sym_residual, ESHAPE, a.ldv = 1; a.R = nullptr);
+  CASE("sym_residual: null X + too large", s, sym_residual, EINVAL_, a.X = nullptr; a.n = a.ldw = a.ldv = 1LL << 31);
+  CASE("sym_residual: too large + overlap", s, sym_residual, ESHAPE, a.n = a.ldw = a.ldv = 1LL << 31; a.R = s.X);
+  CASE("sym_residual: overlap + null diagonal", s, sym_residual, EINVAL_, a.R = s.X; a.dg = nullptr);
+  CASE("gen_residual: null ctx", s, gen_residual, EINVAL_, a.ctx = nullptr);
+  CASE("gen_residual: lda < n", s, gen_residual, ESHAPE, a.lda = n - 1);
+  CASE("gen_residual: k == 9", s, gen_residual, ESHAPE, a.k = 9);
+  CASE("gen_residual: ldv one too small", s, gen_residual, ESHAPE, a.ldv = n - 1);
+  CASE("gen_residual: bad op_mode", s, gen_residual, EINVAL_, a.op = 77);
+  CASE("gen_residual: n == 0 launches nothing", s, gen_residual, OK, a.n = 0; a.R = nullptr; a.X = nullptr; a.v = nullptr; a.A2 = nullptr);
+  CASE("gen_residual: k == 0 launches nothing, transposed", s, gen_residual, OK, a.k = 0; a.op = T; a.R = nullptr);
+  CASE("gen_residual: k == 0 + bad op_mode", s, gen_residual, EINVAL_, a.k = 0; a.op = 77);
+  CASE("gen_residual: null R", s, gen_residual, EINVAL_, a.R = nullptr);
+  CASE("gen_residual: null V", s, gen_residual, EINVAL_, a.v = nullptr);
+  CASE("gen_residual: R is X", s, gen_residual, EINVAL_, a.R = s.X);
+  CASE("gen_residual: R ends at the first element of V", s, gen_residual, EINVAL_, a.R = v - 8 * n + 1);
+  CASE("gen_residual: R inside the matrix, float", s, gen_residual, EINVAL_, a.dtype = F32; a.R = (double *)((float *)s.A2 + n * n - 1));
+  CASE("gen_residual: short ldv + bad op_mode", s, gen_residual, ESHAPE, a.ldv = 1; a.op = 77);
+  CASE("gen_residual: overlap + bad op_mode", s, gen_residual, EINVAL_, a.R = s.X; a.op = 77);
+  CASE("gen_residual: too large + bad op_mode", s, gen_residual, ESHAPE, a.n = a.lda = a.ldv = 1LL << 31; a.op = 77);
+
+  // ---- both members of each vector / block pair, the same cases
+  pair_cases("trisolve_mul", s, trisolve_mul, false, true);
+  pair_cases("trisolve_mul_block", s, trisolve_mul_block, true, true);
+  pair_cases("chol_mul", s, chol_mul, false, true);
+  pair_cases("chol_mul_block", s, chol_mul_block, true, true);
+  pair_cases("ldl_mul", s, ldl_mul, false, true);
+  pair_cases("ldl_mul_block", s, ldl_mul_block, true, true);
+  pair_cases("lu_mul", s, lu_mul, false, true);
+  pair_cases("lu_mul_block", s, lu_mul_block, true, true);
+  pair_cases("ldlp_mul", s, ldlp_mul, false, true);
+  pair_cases("ldlp_mul_block", s, ldlp_mul_block, true, true);
+  pair_cases("qr_mul", b, qr_mul, false, false);
+  pair_cases("qr_mul_block", b, qr_mul_block, true, false);
+  pair_cases("qrp_mul", b, qrp_mul, false, false);
+  pair_cases("qrp_mul_block", b, qrp_mul_block, true, false);
+  pair_cases("pinv_mul", b, pinv_mul, false, false);
+  pair_cases("pinv_mul_block", b, pinv_mul_block, true, false);
+  pair_cases("lu_mul, transposed", [&] { Args a = s; a.op = T; return a; }(), lu_mul, false, true);
+  pair_cases("lu_mul_block, transposed", [&] { Args a = s; a.op = T; return a; }(), lu_mul_block, true, true);
 
   std::printf("%d calls, %d unexpected\n", lines, failures);
   return failures ? 1 : 0;
