@@ -17,6 +17,9 @@ A row is a dict:
   bitwise   True: every output must have the bits of the default-form result (key at its enumerated default, `fixed`
             applied). Decided by reading the kernel: `why` says why in one line, `at` is the file:line it rests on.
             False: the two results are compared at the tolerance of tests/test_gpu_qn.py:871 (1e-12 / 2e-5 relative L2).
+            These norms are parity with the oracle, not the accumulation contract: tests/f32_contract_cases.py and
+            tests/test_gpu_f32_contract.py hold the Float32 / ComplexF32 reductions of the dots, Householder, dense, Hermitian,
+            sparse and block-diagonal families, under the same keys and shapes, to Float64 accumulation per element, to the bit.
   engaged   {value: kernel launches of one apply} at the row's `probe` shape (mxlo_debug_counters()[10]); for the dense family
             a pair: the launches of M v and of M V.
 """

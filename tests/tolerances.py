@@ -22,6 +22,16 @@ QN_F32_FUZZ_LSR1 = 2e-3  # random operation sequences, LSR1Operator (conditionin
 QN_F32_SOLVE = 2e-4      # solve_shifted_system! in coefficient space vs the oracle's recursion (src/utilities.jl:207-248)
 QN_F32_ROUNDTRIP = 1e-3  # B * solve(B, b) ≈ b, the reference's own kind of check (test/test_solve_shifted_system.jl)
 
+# ---- Float64 side of the accumulation contract (tests/test_gpu_f32_contract.py): R = Float64 roundings AFTER the sum, counted
+# in the code; the per-element bound is (terms + R) * 2^-53 * (|alpha| S_i + |beta| |r_i|). Derived, nothing measured.
+F64_CONTRACT_R = {
+    "fin_ab": 3,         # alpha * acc, beta * r, their sum: csrc/stream_kernels.h:212 behind csrc/dense.hip:307 (per component:
+                         # csrc/complex_scalars.h:23-29,41-42 with Real scalars)
+    "hermitian": 6,      # d_i * v_i, + a1, + a2 (csrc/dense.hip:1526; csrc/complex.hip:935), then fin_ab's three
+    "householder": 5,    # c * h, v - c h (csrc/stream_kernels.h:276), then fin_ab's three; c = 2 * dot is exact
+    "householder_complex": 7,   # per component: two products and their sum in c .* h (csrc/complex.hip:101), v - p (:102), cfin's three
+}
+
 # ---- observed envelope: every Float32 quasi-Newton comparison reports its relative error here; with
 # MXLO_ENVELOPE_OUT=<file> in the environment conftest.py writes the per-path maxima at the end of the session
 # (profiles/r03_qn_f32_envelope.json is such a run over MXLO_QNFUZZ32_SEEDS=4010). The bounds above are set from it.
