@@ -194,6 +194,25 @@ inline bool bytes_overlap(const void *a, int64_t na, const void *b, int64_t nb) 
 int32_t stage_alias(mxlo_ctx *ctx, const void *res, int64_t res_bytes, const void **v, int64_t v_bytes, bool same_ok,
                     const char *what);   // api_ctx.hip
 
+// ---- ctx->scratch: the grow-on-demand workspace of the dense leaves (tile / chunk partials) --------------------------------
+// At least `need` bytes behind ctx->scratch; `what` names the user in the out-of-memory message ("<what> scratch: ...").
+inline int32_t ensure_scratch(mxlo_ctx *ctx, size_t need, const char *what) {
+  if (ctx->scratch_bytes < need) {            // stream-ordered users only: drain before the buffer is replaced
+    if (ctx->scratch) {
+      MXLO_HIP(hipStreamSynchronize(ctx->stream));
+      MXLO_HIP(hipFree(ctx->scratch));
+    }
+    ctx->scratch = nullptr;
+    ctx->scratch_bytes = 0;
+    hipError_t e = hipMalloc(&ctx->scratch, need);
+    MXLO_REQUIRE(e == hipSuccess, MXLO_ENOMEM, "%s scratch: %s", what, hipGetErrorString(e));
+    ctx->scratch_bytes = need;
+    ++ctx->scratch_generation;     // graphs that recorded the old workspace pointer are stale now
+  }
+  if (ctx->capturing) ctx->scratch_used_in_capture = true;
+  return MXLO_OK;
+}
+
 // ---- single-launch (grid-exchange) kernels: the exchange, its bounded wait and the fault codes are grid_exchange.h ------
 int32_t fused_fault_check(mxlo_ctx *ctx);           // api_ctx.hip
 inline unsigned long long fused_timeout_ticks(const mxlo_ctx *ctx) {   // wall_clock64() ticks: the device's constant-rate clock

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "stream_kernels.h"
 #include "complex_scalars.h"
+#include "launch_plans.h"
 
 using namespace mxlo;
 
@@ -201,10 +202,10 @@ template <typename R>
 int32_t cdiag(mxlo_ctx *ctx, C<R> *res, const C<R> *d, const C<R> *v, int64_t n_min, int64_t nrow, const ScalArgs &s,
               bool conj_d) {
   MXLO_TRY((dispatch_c<R>(s, [&]<typename RA, typename RB, bool B0>() -> int32_t {
-    const Sc<RA> a{(RA)s.are, (RA)s.aim, s.a_real};
-    const Sc<RB> b{(RB)s.bre, (RB)s.bim, s.b_real};
-    if (conj_d) return launch_map<C<R>, 2, !B0, false>(ctx, res, d, v, n_min, CDiagOp<R, RA, RB, B0, true>{a, b});
-    return launch_map<C<R>, 2, !B0, false>(ctx, res, d, v, n_min, CDiagOp<R, RA, RB, B0, false>{a, b});
+    const auto ab = sc_ab<RA, RB>(s);
+    return with_bool(conj_d, [&](auto CONJD) {
+      return launch_map<C<R>, 2, !B0, false>(ctx, res, d, v, n_min, CDiagOp<R, RA, RB, B0, CONJD.value>{ab.a, ab.b});
+    });
   })));
   return cfill<R>(ctx, res + n_min, nrow - n_min, C<R>());   // res[n_min+1:end] .= 0 regardless of β (:150)
 }
@@ -212,9 +213,8 @@ int32_t cdiag(mxlo_ctx *ctx, C<R> *res, const C<R> *d, const C<R> *v, int64_t n_
 template <typename R>
 int32_t ceye(mxlo_ctx *ctx, C<R> *res, const C<R> *v, int64_t n_min, int64_t nrow, const ScalArgs &s, int32_t flags) {
   MXLO_TRY((dispatch_c<R>(s, [&]<typename RA, typename RB, bool B0>() -> int32_t {
-    const Sc<RA> a{(RA)s.are, (RA)s.aim, s.a_real};
-    const Sc<RB> b{(RB)s.bre, (RB)s.bim, s.b_real};
-    return launch_map<C<R>, 1, !B0, false>(ctx, res, v, (const C<R> *)nullptr, n_min, CAxpbyOp<R, RA, RB, B0>{a, b});
+    const auto ab = sc_ab<RA, RB>(s);
+    return launch_map<C<R>, 1, !B0, false>(ctx, res, v, (const C<R> *)nullptr, n_min, CAxpbyOp<R, RA, RB, B0>{ab.a, ab.b});
   })));
   const int64_t ntail = nrow - n_min;
   if (ntail <= 0) return MXLO_OK;
@@ -229,9 +229,9 @@ int32_t chouse(mxlo_ctx *ctx, C<R> *res, const C<R> *h, const C<R> *v, int64_t n
   MXLO_TRY(cdotc<R>(ctx, h, v, n, dot));
   const bool rev = ctx->tune.house_reverse != 0;
   return dispatch_c<R>(s, [&]<typename RA, typename RB, bool B0>() -> int32_t {
-    CHouseholderOp<R, RA, RB, B0> op{{(RA)s.are, (RA)s.aim, s.a_real}, {(RB)s.bre, (RB)s.bim, s.b_real}, dot, R(0), R(0)};
-    if (rev) return launch_map<C<R>, 2, !B0, true>(ctx, res, h, v, n, op);
-    return launch_map<C<R>, 2, !B0, false>(ctx, res, h, v, n, op);
+    const auto ab = sc_ab<RA, RB>(s);
+    CHouseholderOp<R, RA, RB, B0> op{ab.a, ab.b, dot, R(0), R(0)};
+    return with_bool(rev, [&](auto REV) { return launch_map<C<R>, 2, !B0, REV.value>(ctx, res, h, v, n, op); });
   });
 }
 
@@ -412,28 +412,17 @@ int32_t cgemv_rows(mxlo_ctx *ctx, C<R> *res, const C<R> *M, int64_t m, int64_t n
   const int64_t cap = (int64_t)kMaxRedCols * kMaxRedBlocks / 2;        // complex partials in ctx->partials
   MXLO_REQUIRE(m <= cap, MXLO_ESHAPE, "complex gemv: m = %lld exceeds the partial workspace (%lld rows)", (long long)m,
                (long long)cap);
-  const int64_t row_blocks = (m + kBlock - 1) / kBlock;
-  int64_t nchunks = (n + 63) / 64;
-  const int64_t want = (int64_t)ctx->num_cu * 8 / (row_blocks > 0 ? row_blocks : 1) + 1;
-  if (nchunks > want) nchunks = want;
-  if (nchunks > cap / (m > 0 ? m : 1)) nchunks = cap / (m > 0 ? m : 1);
-  if (nchunks > 65535) nchunks = 65535;
-  if (nchunks < 1) nchunks = 1;
-  const int64_t cpc = n > 0 ? (n + nchunks - 1) / nchunks : 1;
-  nchunks = n > 0 ? (n + cpc - 1) / cpc : 1;
-  dim3 grid((unsigned)row_blocks, (unsigned)nchunks);
-  if (conj)
-    hipLaunchKernelGGL((cgemv_rows_partial_kernel<R, true, LOWER>), grid, dim3(kBlock), 0, ctx->stream, ctx->partials, M, m,
-                       n, ld, v, cpc);
-  else
-    hipLaunchKernelGGL((cgemv_rows_partial_kernel<R, false, LOWER>), grid, dim3(kBlock), 0, ctx->stream, ctx->partials, M, m,
-                       n, ld, v, cpc);
-  MXLO_LAUNCH_CHECK();
+  const ColChunks cc = gemv_col_chunks(m, n, kBlock, ctx->num_cu, cap);
+  MXLO_TRY(with_bool(conj, [&](auto CONJ) -> int32_t {
+    hipLaunchKernelGGL((cgemv_rows_partial_kernel<R, CONJ.value, LOWER>), dim3((unsigned)cc.row_blocks, (unsigned)cc.nchunks), dim3(kBlock), 0,
+                       ctx->stream, ctx->partials, M, m, n, ld, v, cc.cpc);
+    MXLO_LAUNCH_CHECK();
+    return MXLO_OK;
+  }));
   return dispatch_c<R>(s, [&]<typename RA, typename RB, bool B0>() -> int32_t {
-    const Sc<RA> a{(RA)s.are, (RA)s.aim, s.a_real};
-    const Sc<RB> b{(RB)s.bre, (RB)s.bim, s.b_real};
+    const auto ab = sc_ab<RA, RB>(s);
     hipLaunchKernelGGL((cgemv_rows_finish_kernel<R, RA, RB, B0, RAW>), dim3((unsigned)((m + 31) / 32)), dim3(kBlock), 0,
-                       ctx->stream, res, ctx->partials, m, (int)nchunks, a, b);
+                       ctx->stream, res, ctx->partials, m, (int)cc.nchunks, ab.a, ab.b);
     MXLO_LAUNCH_CHECK();
     return MXLO_OK;
   });
@@ -446,32 +435,23 @@ int32_t cgemv_cols(mxlo_ctx *ctx, C<R> *res, const C<R> *M, int64_t m, int64_t n
   const int64_t cap = (int64_t)ctx->num_cu * 16;
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
+  constexpr int VR = 16 / (int)sizeof(C<R>);
+  const bool vec = !LOWER && m >= 256 * VR && ((((uintptr_t)M | (uintptr_t)v) & 15u) == 0) && ld % VR == 0 && m % VR == 0;
+  const bool nt = (int64_t)sizeof(C<R>) * m * n >= ctx->tune.nt_min_bytes;   // cache-sized matrices keep default loads
   return dispatch_c<R>(s, [&]<typename RA, typename RB, bool B0>() -> int32_t {
-    const Sc<RA> a{(RA)s.are, (RA)s.aim, s.a_real};
-    const Sc<RB> b{(RB)s.bre, (RB)s.bim, s.b_real};
-    constexpr int VR = 16 / (int)sizeof(C<R>);
-    const bool vec = !LOWER && m >= 256 * VR && ((((uintptr_t)M | (uintptr_t)v) & 15u) == 0) && ld % VR == 0 && m % VR == 0;
-    if constexpr (!LOWER) {
-      if (vec) {
-        const bool nt = (int64_t)sizeof(C<R>) * m * n >= ctx->tune.nt_min_bytes;   // cache-sized matrices keep default loads
-#define CCOLS(CJ_, NT_)                                                                                                \
-  hipLaunchKernelGGL((cgemv_cols_kernel<R, RA, RB, B0, CJ_, LOWER, RAW, true, NT_>), dim3((unsigned)blocks), dim3(kBlock), 0, \
-                     ctx->stream, res, M, m, n, ld, v, a, b)
-        if (conj) { if (nt) CCOLS(true, true); else CCOLS(true, false); }
-        else { if (nt) CCOLS(false, true); else CCOLS(false, false); }
-#undef CCOLS
+    const auto ab = sc_ab<RA, RB>(s);
+    return with_bool(conj, [&](auto CONJ) -> int32_t {
+      auto go = [&](auto VEC, auto NT) -> int32_t {
+        hipLaunchKernelGGL((cgemv_cols_kernel<R, RA, RB, B0, CONJ.value, LOWER, RAW, VEC.value, NT.value>), dim3((unsigned)blocks), dim3(kBlock), 0,
+                           ctx->stream, res, M, m, n, ld, v, ab.a, ab.b);
         MXLO_LAUNCH_CHECK();
         return MXLO_OK;
+      };
+      if constexpr (!LOWER) {                  // 16-byte loads, with or without the hint: whole columns only
+        if (vec) return with_bool(nt, [&](auto NT) { return go(std::true_type{}, NT); });
       }
-    }
-    if (conj)
-      hipLaunchKernelGGL((cgemv_cols_kernel<R, RA, RB, B0, true, LOWER, RAW>), dim3((unsigned)blocks), dim3(kBlock), 0,
-                         ctx->stream, res, M, m, n, ld, v, a, b);
-    else
-      hipLaunchKernelGGL((cgemv_cols_kernel<R, RA, RB, B0, false, LOWER, RAW>), dim3((unsigned)blocks), dim3(kBlock), 0,
-                         ctx->stream, res, M, m, n, ld, v, a, b);
-    MXLO_LAUNCH_CHECK();
-    return MXLO_OK;
+      return go(std::false_type{}, std::true_type{});
+    });
   });
 }
 
@@ -561,21 +541,6 @@ cgemv_rows_band_kernel(C<R> *__restrict__ res, const C<R> *__restrict__ M, int64
   }
 }
 
-// band height for an m x n complex operand (0: the column-chunk schedule); policy and thresholds as dense.hip: gemv_rows_band
-template <typename R>
-int cgemv_rows_band(const mxlo_ctx *ctx, const C<R> *M, int64_t m, int64_t n, int64_t ld) {
-  constexpr int VR = 16 / (int)sizeof(C<R>);
-  const bool vec = (((uintptr_t)M & 15u) == 0) && ld % VR == 0 && m % VR == 0;
-  if (ctx->tune.gemv_n_rows != 1 || !vec || n < 1024) return 0;
-  int rb = 0;
-  if (m >= (int64_t)32 * VR * ctx->num_cu) rb = 32 * VR;
-  else if (m >= (int64_t)16 * VR * ctx->num_cu) rb = 16 * VR;
-  else if (m >= (int64_t)8 * VR * ctx->num_cu) rb = 8 * VR;
-  if (rb == 16 * VR && n >= 16384) rb = 0;
-  if (rb == 8 * VR && n > 16384) rb = 0;
-  return rb;
-}
-
 template <typename R>
 int32_t cgemv_any(mxlo_ctx *ctx, C<R> *res, const C<R> *M, int64_t m, int64_t n, int64_t ld, const C<R> *v, int mode,
                   const ScalArgs &s, int32_t flags) {
@@ -587,29 +552,23 @@ int32_t cgemv_any(mxlo_ctx *ctx, C<R> *res, const C<R> *M, int64_t m, int64_t n,
     return cscale<R>(ctx, res, nres, s.bre, s.bim, s.b_real, s.b64);
   }
   if (rows) {
-    if (const int rb = cgemv_rows_band<R>(ctx, M, m, n, ld); rb != 0) {
-      constexpr int VR = 16 / (int)sizeof(C<R>);
+    constexpr int VR = 16 / (int)sizeof(C<R>);
+    // the band rule of the real GEMV (launch_plans.h) on complex elements; a height forced by name is the real kernels' key
+    if (const int rb = gemv_row_band<C<R>>(M, m, n, ld, ctx->num_cu, 0, ctx->tune.gemv_n_rows == 1, true); rb != 0) {
+      const bool nt = (int64_t)sizeof(C<R>) * m * n >= ctx->tune.nt_min_bytes;   // cache-sized matrices keep default loads
       return dispatch_c<R>(s, [&]<typename RA, typename RB, bool B0>() -> int32_t {
-        const Sc<RA> a{(RA)s.are, (RA)s.aim, s.a_real};
-        const Sc<RB> b{(RB)s.bre, (RB)s.bim, s.b_real};
-#define CROWS(CJ_, RB_)                                                                                               \
-  if (nt) hipLaunchKernelGGL((cgemv_rows_band_kernel<R, RA, RB, B0, CJ_, RB_, true>), dim3((unsigned)((m + (RB_) - 1) / (RB_))), \
-                             dim3(kCRowsBlock), 0, ctx->stream, res, M, m, n, ld, v, a, b);                             \
-  else hipLaunchKernelGGL((cgemv_rows_band_kernel<R, RA, RB, B0, CJ_, RB_, false>), dim3((unsigned)((m + (RB_) - 1) / (RB_))), \
-                          dim3(kCRowsBlock), 0, ctx->stream, res, M, m, n, ld, v, a, b)
-        const bool nt = (int64_t)sizeof(C<R>) * m * n >= ctx->tune.nt_min_bytes;   // cache-sized matrices keep default loads
-        if (conj) {
-          if (rb == 32 * VR) { CROWS(true, 32 * VR); }
-          else if (rb == 16 * VR) { CROWS(true, 16 * VR); }
-          else { CROWS(true, 8 * VR); }
-        } else {
-          if (rb == 32 * VR) { CROWS(false, 32 * VR); }
-          else if (rb == 16 * VR) { CROWS(false, 16 * VR); }
-          else { CROWS(false, 8 * VR); }
-        }
-#undef CROWS
-        MXLO_LAUNCH_CHECK();
-        return MXLO_OK;
+        const auto ab = sc_ab<RA, RB>(s);
+        return with_bool(conj, [&](auto CONJ) {
+          return with_int<32 * VR, 16 * VR, 8 * VR>(rb, [&](auto RBAND) {
+            return with_bool(nt, [&](auto NT) -> int32_t {
+              hipLaunchKernelGGL((cgemv_rows_band_kernel<R, RA, RB, B0, CONJ.value, RBAND.value, NT.value>),
+                                 dim3((unsigned)((m + RBAND.value - 1) / RBAND.value)), dim3(kCRowsBlock), 0, ctx->stream, res, M, m, n, ld, v,
+                                 ab.a, ab.b);
+              MXLO_LAUNCH_CHECK();
+              return MXLO_OK;
+            });
+          });
+        });
       });
     }
     return cgemv_rows<R, false, false>(ctx, res, M, m, n, ld, v, conj, s);
@@ -947,72 +906,40 @@ int32_t chermitian(mxlo_ctx *ctx, C<R> *res, const void *d, bool d_real, const C
                    int64_t n, const ScalArgs &s) {
   if (n == 0) return MXLO_OK;
   if (ctx->tune.cherm_two_pass) return chermitian_two_pass<R>(ctx, res, d, d_real, A, lda, v, n, s);
-  constexpr int HR = CHermCfg<R>::HR, DT = CHermCfg<R>::DT, RPL = CHermCfg<R>::RPL;
-  const int64_t ng = (n + HR - 1) / HR, ngf = n / HR;
-  MXLO_REQUIRE(4 * ng * (ng + 1) < (1LL << 31), MXLO_ESHAPE, "complex opHermitian: n too large");
-  // tiles per strip: whole diagonal-block-wide strips once there are two of them per CU, thinner strips below that
-  const int64_t pairs = ng * (ng - 1) / 2;
-  const int CT = pairs >= 2 * ctx->num_cu ? DT : ((DT / 2) * pairs >= 2 * ctx->num_cu ? 2 : 1), Q = DT / CT;
-  const int64_t nslots = Q * (ng - 1) + DT;
-  const size_t need = sizeof(double) * 2 * (size_t)(nslots + 2 * ng) * (size_t)n;   // Prow[nslots][n], Pcol[2ng][n], complex
-  if (ctx->scratch_bytes < need) {            // stream-ordered users only: drain before the buffer is replaced
-    if (ctx->scratch) {
-      MXLO_HIP(hipStreamSynchronize(ctx->stream));
-      MXLO_HIP(hipFree(ctx->scratch));
-    }
-    ctx->scratch = nullptr;
-    ctx->scratch_bytes = 0;
-    hipError_t e = hipMalloc(&ctx->scratch, need);
-    MXLO_REQUIRE(e == hipSuccess, MXLO_ENOMEM, "complex opHermitian scratch: %s", hipGetErrorString(e));
-    ctx->scratch_bytes = need;
-    ++ctx->scratch_generation;     // graphs that recorded the old workspace pointer are stale now
-  }
-  if (ctx->capturing) ctx->scratch_used_in_capture = true;
+  using Cfg = CHermCfg<R>;
+  constexpr int DT = Cfg::DT;
+  const bool aligned = (((uintptr_t)A & 15u) == 0) && (lda % Cfg::RPL == 0);
+  const HermGeom g = herm_geom(n, Cfg::HR, DT, aligned, [&](int64_t pairs) { return cherm_strip_tiles(ctx, DT, pairs); });
+  MXLO_REQUIRE(!g.too_large, MXLO_ESHAPE, "complex opHermitian: n too large");
+  const int64_t nslots = g.Q * (g.ng - 1) + DT;
+  // Prow[nslots][n], Pcol[2ng][n], complex
+  MXLO_TRY(ensure_scratch(ctx, sizeof(double) * 2 * (size_t)(nslots + 2 * g.ng) * (size_t)n, "complex opHermitian"));
   double *Prow = (double *)ctx->scratch, *Pcol = Prow + 2 * (size_t)nslots * n;
-  const bool aligned = (((uintptr_t)A & 15u) == 0) && (lda % RPL == 0);
-  const int64_t gi = aligned ? ngf : 0;
-  const int64_t n_int = gi > 1 ? Q * gi * (gi - 1) / 2 : 0;
-  const int64_t n_dsel = (int64_t)DT * gi;
-  const int64_t n_all = !aligned && ng > 1 ? Q * ng * (ng - 1) / 2 : 0;       // mode 0, masked
-  const int64_t n_last = aligned && ng > ngf ? Q * (ng - 1) : 0;               // mode 1
-  const int64_t n_diag = (int64_t)DT * (ng - gi);                              // mode 2, row groups gi .. ng-1
-  const int64_t n_light = n_int + n_dsel, n_edge = n_all + n_last + n_diag;
-  MXLO_REQUIRE(n_light < (1LL << 31) && n_edge < (1LL << 31), MXLO_ESHAPE, "complex opHermitian: n too large");
-  // strip loads: nontemporal except for triangles of about the size of the Infinity Cache (the rule of dense.hip: herm_nt_policy)
-  const int64_t tri = (int64_t)sizeof(C<R>) * n * (n / 2);
-  const bool nt = ctx->tune.herm_nt >= 0 ? ctx->tune.herm_nt != 0
-                                         : !(tri >= ctx->tune.herm_dp_min_bytes && tri < ctx->tune.herm_nt_min_bytes);
-#define CHERM_LAUNCH(CT_)                                                                                        \
-  {                                                                                                              \
-    if (n_light > 0) {                                                                                           \
-      if (nt)                                                                                                    \
-        hipLaunchKernelGGL((cherm_pass_kernel<R, CT_, true>), dim3((unsigned)n_light), dim3(kBlock), 0, ctx->stream, A, lda, \
-                           v, n, Prow, Pcol, ng, Q, n_int, ctx->tune.herm_order ? (int)gi : 0);                  \
-      else                                                                                                       \
-        hipLaunchKernelGGL((cherm_pass_kernel<R, CT_, false>), dim3((unsigned)n_light), dim3(kBlock), 0, ctx->stream, A, lda, \
-                           v, n, Prow, Pcol, ng, Q, n_int, ctx->tune.herm_order ? (int)gi : 0);                  \
-      MXLO_LAUNCH_CHECK();                                                                                       \
-    }                                                                                                            \
-    if (n_edge > 0) {                                                                                            \
-      hipLaunchKernelGGL((cherm_edge_kernel<R, CT_>), dim3((unsigned)n_edge), dim3(kBlock), 0, ctx->stream, A, lda,  \
-                         v, n, Prow, Pcol, ng, Q, n_all, n_last, gi);                                            \
-      MXLO_LAUNCH_CHECK();                                                                                       \
-    }                                                                                                            \
-  }
-  if (CT == DT) CHERM_LAUNCH(DT) else if (CT == 2) CHERM_LAUNCH(2) else CHERM_LAUNCH(1)
-#undef CHERM_LAUNCH
+  const bool nt = herm_nt_policy(ctx, sizeof(C<R>), n);
+  MXLO_TRY((with_int<DT, 2, 1>(g.C, [&](auto CT) -> int32_t {
+    if (g.n_light > 0)
+      MXLO_TRY(with_bool(nt, [&](auto NT) -> int32_t {
+        hipLaunchKernelGGL((cherm_pass_kernel<R, CT.value, NT.value>), dim3((unsigned)g.n_light), dim3(kBlock), 0, ctx->stream, A, lda,
+                           v, n, Prow, Pcol, g.ng, g.Q, g.n_int, ctx->tune.herm_order ? (int)g.gi : 0);
+        MXLO_LAUNCH_CHECK();
+        return MXLO_OK;
+      }));
+    if (g.n_edge > 0) {
+      hipLaunchKernelGGL((cherm_edge_kernel<R, CT.value>), dim3((unsigned)g.n_edge), dim3(kBlock), 0, ctx->stream, A, lda,
+                         v, n, Prow, Pcol, g.ng, g.Q, g.n_all, g.n_last, g.gi);
+      MXLO_LAUNCH_CHECK();
+    }
+    return MXLO_OK;
+  })));
   const unsigned blocks = (unsigned)((n + 31) / 32);
   return dispatch_c<R>(s, [&]<typename RA, typename RB, bool B0>() -> int32_t {
-    const Sc<RA> a{(RA)s.are, (RA)s.aim, s.a_real};
-    const Sc<RB> b{(RB)s.bre, (RB)s.bim, s.b_real};
-    if (d_real)
-      hipLaunchKernelGGL((cherm_finish_kernel<R, RA, RB, B0, true>), dim3(blocks), dim3(kBlock), 0, ctx->stream, res, d, v,
-                         Prow, Pcol, n, (int)ng, Q, a, b);
-    else
-      hipLaunchKernelGGL((cherm_finish_kernel<R, RA, RB, B0, false>), dim3(blocks), dim3(kBlock), 0, ctx->stream, res, d, v,
-                         Prow, Pcol, n, (int)ng, Q, a, b);
-    MXLO_LAUNCH_CHECK();
-    return MXLO_OK;
+    const auto ab = sc_ab<RA, RB>(s);
+    return with_bool(d_real, [&](auto DREAL) -> int32_t {
+      hipLaunchKernelGGL((cherm_finish_kernel<R, RA, RB, B0, DREAL.value>), dim3(blocks), dim3(kBlock), 0, ctx->stream, res, d, v,
+                         Prow, Pcol, n, (int)g.ng, g.Q, ab.a, ab.b);
+      MXLO_LAUNCH_CHECK();
+      return MXLO_OK;
+    });
   });
 }
 
@@ -1022,36 +949,20 @@ template <typename R>
 int32_t chermitian_two_pass(mxlo_ctx *ctx, C<R> *res, const void *d, bool d_real, const C<R> *A, int64_t lda,
                             const C<R> *v, int64_t n, const ScalArgs &s) {
   if (n == 0) return MXLO_OK;
-  const size_t need = sizeof(C<R>) * 2 * (size_t)n;           // t1 = L*v, t2 = L'*v
-  if (ctx->scratch_bytes < need) {            // stream-ordered users only: drain before the buffer is replaced
-    if (ctx->scratch) {
-      MXLO_HIP(hipStreamSynchronize(ctx->stream));
-      MXLO_HIP(hipFree(ctx->scratch));
-    }
-    ctx->scratch = nullptr;
-    ctx->scratch_bytes = 0;
-    hipError_t e = hipMalloc(&ctx->scratch, need);
-    MXLO_REQUIRE(e == hipSuccess, MXLO_ENOMEM, "complex opHermitian scratch: %s", hipGetErrorString(e));
-    ctx->scratch_bytes = need;
-    ++ctx->scratch_generation;     // graphs that recorded the old workspace pointer are stale now
-  }
-  if (ctx->capturing) ctx->scratch_used_in_capture = true;
+  MXLO_TRY(ensure_scratch(ctx, sizeof(C<R>) * 2 * (size_t)n, "complex opHermitian"));   // t1 = L*v, t2 = L'*v
   C<R> *t1 = (C<R> *)ctx->scratch, *t2 = t1 + n;
   ScalArgs one{1.0, 0.0, 0.0, 0.0, true, true, true, true};
   MXLO_TRY((cgemv_rows<R, true, true>(ctx, t1, A, n, n, lda, v, false, one)));     // L*v
   MXLO_TRY((cgemv_cols<R, true, true>(ctx, t2, A, n, n, lda, v, true, one)));      // (v'*L)' = L'*v
   const int grid = grid_for(ctx, n, kBlock, 8);
   return dispatch_c<R>(s, [&]<typename RA, typename RB, bool B0>() -> int32_t {
-    const Sc<RA> a{(RA)s.are, (RA)s.aim, s.a_real};
-    const Sc<RB> b{(RB)s.bre, (RB)s.bim, s.b_real};
-    if (d_real)
-      hipLaunchKernelGGL((cherm_final_kernel<R, RA, RB, B0, true>), dim3(grid), dim3(kBlock), 0, ctx->stream, res, d, v,
-                         (const C<R> *)t1, (const C<R> *)t2, n, a, b);
-    else
-      hipLaunchKernelGGL((cherm_final_kernel<R, RA, RB, B0, false>), dim3(grid), dim3(kBlock), 0, ctx->stream, res, d, v,
-                         (const C<R> *)t1, (const C<R> *)t2, n, a, b);
-    MXLO_LAUNCH_CHECK();
-    return MXLO_OK;
+    const auto ab = sc_ab<RA, RB>(s);
+    return with_bool(d_real, [&](auto DREAL) -> int32_t {
+      hipLaunchKernelGGL((cherm_final_kernel<R, RA, RB, B0, DREAL.value>), dim3(grid), dim3(kBlock), 0, ctx->stream, res, d, v,
+                         (const C<R> *)t1, (const C<R> *)t2, n, ab.a, ab.b);
+      MXLO_LAUNCH_CHECK();
+      return MXLO_OK;
+    });
   });
 }
 
@@ -1129,10 +1040,9 @@ int32_t ckron(mxlo_ctx *ctx, C<R> *res, const R *Ar, const R *Ai, int64_t am, in
                            (mode_b & 2) ? -1.0 : 1.0, xr, xi, utr, uti)));
   const int grid = grid_for(ctx, nout, kBlock, 8);
   return dispatch_c<R>(s, [&]<typename RA, typename RB, bool B0>() -> int32_t {
-    const Sc<RA> a{(RA)s.are, (RA)s.aim, s.a_real};
-    const Sc<RB> b{(RB)s.bre, (RB)s.bim, s.b_real};
+    const auto ab = sc_ab<RA, RB>(s);
     hipLaunchKernelGGL((cplx_join_kernel<R, RA, RB, B0>), dim3(grid), dim3(kBlock), 0, ctx->stream, res, (const R *)rr,
-                       (const R *)ri, nout, a, b);
+                       (const R *)ri, nout, ab.a, ab.b);
     MXLO_LAUNCH_CHECK();
     return MXLO_OK;
   });
@@ -1162,14 +1072,13 @@ int32_t ckron3(mxlo_ctx *ctx, C<R> *res, const R *Ar, const R *Ai, const R *As, 
                             (mode_b & 2) ? -1.0 : 1.0, xr, xi, xd, xs, rest, kk)));
   const int grid = grid_for(ctx, nout, kBlock, 8);
   return dispatch_c<R>(s, [&]<typename RA, typename RB, bool B0>() -> int32_t {
-    const Sc<RA> a{(RA)s.are, (RA)s.aim, s.a_real};
-    const Sc<RB> b{(RB)s.bre, (RB)s.bim, s.b_real};
+    const auto ab = sc_ab<RA, RB>(s);
     if (kk[0])
       hipLaunchKernelGGL((cplx_join3_kernel<R, RA, RB, B0>), dim3(grid), dim3(kBlock), 0, ctx->stream, res, kk[0], kk[1], kk[2],
-                         nout, a, b);
+                         nout, ab.a, ab.b);
     else
       hipLaunchKernelGGL((cplx_join_kernel<R, RA, RB, B0>), dim3(grid), dim3(kBlock), 0, ctx->stream, res, (const R *)rr,
-                         (const R *)ri, nout, a, b);
+                         (const R *)ri, nout, ab.a, ab.b);
     MXLO_LAUNCH_CHECK();
     return MXLO_OK;
   });
@@ -1382,9 +1291,8 @@ template <typename R>
 int32_t cjoin(mxlo_ctx *ctx, C<R> *res, const R *re, const R *im, int64_t n, const ScalArgs &s) {
   const int grid = grid_for(ctx, n, kBlock, 8);
   return dispatch_c<R>(s, [&]<typename RA, typename RB, bool B0>() -> int32_t {
-    const Sc<RA> a{(RA)s.are, (RA)s.aim, s.a_real};
-    const Sc<RB> b{(RB)s.bre, (RB)s.bim, s.b_real};
-    hipLaunchKernelGGL((cplx_join_kernel<R, RA, RB, B0>), dim3(grid), dim3(kBlock), 0, ctx->stream, res, re, im, n, a, b);
+    const auto ab = sc_ab<RA, RB>(s);
+    hipLaunchKernelGGL((cplx_join_kernel<R, RA, RB, B0>), dim3(grid), dim3(kBlock), 0, ctx->stream, res, re, im, n, ab.a, ab.b);
     MXLO_LAUNCH_CHECK();
     return MXLO_OK;
   });

@@ -79,4 +79,15 @@ int32_t dispatch_c(const ScalArgs &s, F &&f) {
   }
 }
 
+// α and β in the component types dispatch_c chose: the two scalar arguments of every kernel launched from its lambda
+template <typename RA, typename RB>
+struct ScAB {
+  Sc<RA> a;
+  Sc<RB> b;
+};
+template <typename RA, typename RB>
+inline ScAB<RA, RB> sc_ab(const ScalArgs &s) {
+  return {{(RA)s.are, (RA)s.aim, s.a_real}, {(RB)s.bre, (RB)s.bim, s.b_real}};
+}
+
 }  // namespace mxlo

@@ -9,6 +9,7 @@
 #include "common.h"
 #include "gemm_glds.h"
 #include "stream_kernels.h"
+#include "launch_plans.h"
 
 using namespace mxlo;
 
@@ -124,60 +125,30 @@ int32_t gemm(mxlo_ctx *ctx, T *C, int64_t ldc, const T *A, int64_t lda, bool ta,
   // per-lane DMA offsets are 32-bit: one K-slab of either operand must span < 4 GiB
   const bool ld_ok = lda < (1LL << 22) && ldb < (1LL << 22) && ldc > 0;
   if (tb && K > 0 && ld_ok && ctx->tune.gemm_tile >= 0 && gemm_glds_ok<T>(A, lda, ta, B, ldb, M, N, K)) {
+    const int tile = ctx->tune.gemm_tile ? ctx->tune.gemm_tile : gemm_tile_class(M, N, ctx->num_cu);   // 0 = auto, else 32 / 64 / 128
     return dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
-      auto tiles = [&](int tm, int tn) { return ((M + tm - 1) / tm) * ((N + tn - 1) / tn); };
-      int tile = ctx->tune.gemm_tile;   // 0 = auto, else 32 / 64 / 128
-      if (tile == 0) {
-        if (tiles(128, 128) >= ctx->num_cu) tile = 128;
-        else if (tiles(64, 64) * 5 >= (int64_t)ctx->num_cu * 3) tile = 64;   // >= 0.6 workgroups per CU
-        else tile = 32;
-      }
-#define GLDS(AK_, TM_, TN_, WM_, WN_, BK_, NST_, PAIR_, PFD_, UNR_)                                               \
-  {                                                                                                               \
-    GlShape S{(int)M, (int)N, (int)K, (int)((M + TM_ - 1) / TM_), (int)((N + TN_ - 1) / TN_)};                    \
-    hipLaunchKernelGGL((gemm_glds_kernel<T, CA, CB, B0, AK_, TM_, TN_, WM_, WN_, BK_, NST_, true, true, PAIR_, PFD_, true, false, false, UNR_>), \
-                       dim3(S.gx * S.gy), dim3(WM_ * WN_ * 64), 0, ctx->stream, C, ldc, A, lda, B, ldb, S,        \
-                       (CA)alpha, (CB)beta);                                                                      \
-  }
-#define GLDS_BY_A(TM_, TN_, WM_, WN_, BK_, NST_, PAIR_, PFD_, UNR_AM_)                                            \
-  if (ta) GLDS(true, TM_, TN_, WM_, WN_, BK_, NST_, PAIR_, PFD_, true) else GLDS(false, TM_, TN_, WM_, WN_, BK_, NST_, PAIR_, PFD_, UNR_AM_)
-      // PAIR (gemm_glds.h): tile pairs interleaved so that two fragments arrive with one 16-byte LDS read. Measured
-      // (profiles/r03_tune_gemm_pair.txt): 64-tiles -2.0 % (f64) / -2.7 % (f32), f64 128-tiles -0.6 %, f32 128-tiles +0.4 %.
-      // SWAPC (always on): the MFMA runs with its operands exchanged so that the accumulator holds the transposed tile and
-      // 16 lanes store 16 consecutive rows of the column-major C (whole 128-byte lines in f64): 1024^2 f64 72.6 -> 70.4 us,
-      // f32 43.1 -> 41.0 us, 2048^2 -1 ... -4 % (profiles/r03_tune_gemm_swapc.txt).
-      // UNR (on except for the M-contiguous f32 64- / 128-tiles, where it measured +1 ... 2 %): the steady state runs NST slabs per trip with the ring index a compile-time constant, so every LDS
-      // address is base + immediate and the vector ALU does no address work between the MFMAs: 1024^2 70.2 -> 68.9 us, the
-      // transpose mode (XOR-swizzled K-contiguous A) 79.0 -> 69.8 us, 32-tiles -6 ... -8 %, 128-tiles at 2048^2 -2.9 %.
-      // PFD 2 (fragments read two k-steps ahead): the 32-tile workgroup has ONE wave per SIMD, nothing else hides its LDS
-      // latency: -0.5 ... -3 % there, +1 % on the 64-tiles (two waves per SIMD) — profiles/r03_tune_gemm_bk.txt
-      if constexpr (sizeof(T) == 8) {
-        if (tile == 128) GLDS_BY_A(128, 128, 4, 4, 16, 3, true, 1, true)
-        else if (tile == 64) GLDS_BY_A(64, 64, 4, 2, 32, 3, true, 1, true)
-        else GLDS_BY_A(32, 32, 2, 2, 32, 4, false, 2, true)
-      } else {
-        if (tile == 128) GLDS_BY_A(128, 128, 4, 4, 32, 3, false, 1, false)
-        else if (tile == 64) GLDS_BY_A(64, 64, 4, 2, 64, 3, true, 1, false)
-        else GLDS_BY_A(32, 32, 2, 2, 64, 4, false, 2, true)
-      }
-#undef GLDS_BY_A
-#undef GLDS
-      MXLO_LAUNCH_CHECK();
-      return MXLO_OK;
+      return with_bool(ta, [&](auto AK) {
+        return with_int<128, 64, 32>(tile, [&](auto TILE) -> int32_t {
+          constexpr GemmTile P = gemm_tile_params(sizeof(T), AK.value, TILE.value);
+          GlShape S{(int)M, (int)N, (int)K, (int)((M + P.TM - 1) / P.TM), (int)((N + P.TM - 1) / P.TM)};
+          hipLaunchKernelGGL((gemm_glds_kernel<T, CA, CB, B0, AK.value, P.TM, P.TM, P.WM, P.WN, P.BK, P.NST, true, true, P.PAIR, P.PFD, true, false, false, P.UNR>),
+                             dim3(S.gx * S.gy), dim3(P.WM * P.WN * 64), 0, ctx->stream, C, ldc, A, lda, B, ldb, S, (CA)alpha, (CB)beta);
+          MXLO_LAUNCH_CHECK();
+          return MXLO_OK;
+        });
+      });
     });
   }
   dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)((N + BN - 1) / BN));
   return dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
-#define GO(TA_, TB_)                                                                                  \
-  hipLaunchKernelGGL((gemm_kernel<T, CA, CB, TA_, TB_, B0>), grid, dim3(kBlock), 0, ctx->stream, C,  \
-                     ldc, A, lda, B, ldb, (int)M, (int)N, (int)K, (CA)alpha, (CB)beta)
-    if (!ta && !tb) GO(false, false);
-    else if (!ta && tb) GO(false, true);
-    else if (ta && !tb) GO(true, false);
-    else GO(true, true);
-#undef GO
-    MXLO_LAUNCH_CHECK();
-    return MXLO_OK;
+    return with_bool(ta, [&](auto TA) {
+      return with_bool(tb, [&](auto TB) -> int32_t {
+        hipLaunchKernelGGL((gemm_kernel<T, CA, CB, TA.value, TB.value, B0>), grid, dim3(kBlock), 0, ctx->stream, C, ldc, A, lda, B, ldb,
+                           (int)M, (int)N, (int)K, (CA)alpha, (CB)beta);
+        MXLO_LAUNCH_CHECK();
+        return MXLO_OK;
+      });
+    });
   });
 }
 
@@ -379,80 +350,40 @@ gemv_n_rows_kernel(T *__restrict__ res, const T *__restrict__ M, int64_t m, int6
   }
 }
 
-// the band height gemv_n uses for an m x n operand (0: keep the column-chunk schedule)
-template <typename T>
-int gemv_rows_band(const mxlo_ctx *ctx, const T *M, int64_t m, int64_t n, int64_t ld) {
-  constexpr int VR = 16 / (int)sizeof(T);
-  const bool vec = (((uintptr_t)M & 15u) == 0) && ld % VR == 0 && m % VR == 0;
-  // tune gemv_n_rows: 0 = off, 1 = auto, 8*VR / 16*VR / 32*VR = that band height (sweeps)
-  int rb = 0;
-  const int want = ctx->tune.gemv_n_rows;
-  if (want > 1) {
-    if (want == 8 * VR || want == 16 * VR || want == 32 * VR) rb = want;
-  } else if (want == 1 && n >= 1024) {
-    // the tallest band that still gives every CU a workgroup: a band reads RB * sizeof(T) contiguous bytes per column
-    // (128 B at 8 * VR), and the longer the pieces the better HBM streams them (tools/bench_gemv_n.py)
-    if (m >= (int64_t)32 * VR * ctx->num_cu) rb = 32 * VR;
-    else if (m >= (int64_t)16 * VR * ctx->num_cu) rb = 16 * VR;
-    else if (m >= (int64_t)8 * VR * ctx->num_cu) rb = 8 * VR;
-    // measured (profiles/r05_bench_gemv_n.txt): 512-byte pieces win everywhere (0.84 - 0.88 of peak); 256-byte pieces
-    // win (0.78 - 0.84) except against the column-chunk schedule on very wide matrices, whose finish launch is amortised
-    // there; 128-byte pieces top out at 0.68 - 0.73: better than the two launches up to n = 16384 columns only
-    if (rb == 16 * VR && n >= 16384) rb = 0;
-    if (rb == 8 * VR && n > 16384) rb = 0;
-  }
-  return (rb != 0 && vec && m >= rb) ? rb : 0;
-}
-
 template <typename T>
 int32_t gemv_n(mxlo_ctx *ctx, T *res, const T *M, int64_t m, int64_t n, int64_t ld, const T *v,
                double alpha, double beta, int32_t flags) {
-  {
-    constexpr int VR = 16 / (int)sizeof(T);
-    const int rb = gemv_rows_band<T>(ctx, M, m, n, ld);
-    if (rb != 0) {
-      const bool nt = (int64_t)sizeof(T) * m * n >= ctx->tune.nt_min_bytes;   // see gemv_t: cache-sized matrices keep default loads
-      return dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
-#define ROWS(RB_)                                                                                                     \
-  if (nt) hipLaunchKernelGGL((gemv_n_rows_kernel<T, CA, CB, B0, RB_, true>), dim3((unsigned)((m + (RB_) - 1) / (RB_))),   \
-                             dim3(kGemvRowsBlock), 0, ctx->stream, res, M, m, n, ld, v, (CA)alpha, (CB)beta);         \
-  else hipLaunchKernelGGL((gemv_n_rows_kernel<T, CA, CB, B0, RB_, false>), dim3((unsigned)((m + (RB_) - 1) / (RB_))),     \
-                          dim3(kGemvRowsBlock), 0, ctx->stream, res, M, m, n, ld, v, (CA)alpha, (CB)beta)
-        if (rb == 32 * VR) { ROWS(32 * VR); }
-        else if (rb == 16 * VR) { ROWS(16 * VR); }
-        else { ROWS(8 * VR); }
-#undef ROWS
-        MXLO_LAUNCH_CHECK();
-        return MXLO_OK;
+  constexpr int VR = 16 / (int)sizeof(T);
+  // tune gemv_n_rows: 0 = off, 1 = auto, 8*VR / 16*VR / 32*VR = that band height (sweeps)
+  const int want = ctx->tune.gemv_n_rows;
+  if (const int rb = gemv_row_band<T>(M, m, n, ld, ctx->num_cu, want > 1 ? want : 0, want == 1, true); rb != 0) {
+    const bool nt = (int64_t)sizeof(T) * m * n >= ctx->tune.nt_min_bytes;   // see gemv_t: cache-sized matrices keep default loads
+    return dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
+      return with_int<32 * VR, 16 * VR, 8 * VR>(rb, [&](auto RB) {
+        return with_bool(nt, [&](auto NT) -> int32_t {
+          hipLaunchKernelGGL((gemv_n_rows_kernel<T, CA, CB, B0, RB.value, NT.value>), dim3((unsigned)((m + RB.value - 1) / RB.value)),
+                             dim3(kGemvRowsBlock), 0, ctx->stream, res, M, m, n, ld, v, (CA)alpha, (CB)beta);
+          MXLO_LAUNCH_CHECK();
+          return MXLO_OK;
+        });
       });
-    }
+    });
   }
   const int64_t cap = (int64_t)kMaxRedCols * kMaxRedBlocks;  // doubles in ctx->partials
   MXLO_REQUIRE(m <= cap, MXLO_ESHAPE, "gemv: m = %lld exceeds the partial workspace", (long long)m);
   // pairs of rows per lane need 16-byte (8-byte for f32) aligned column starts
   const bool pair = m >= 2 && (((uintptr_t)M % (2 * sizeof(T))) == 0) && (ld % 2 == 0);
-  const int64_t rows_per_block = (int64_t)kBlock * (pair ? 2 : 1);
-  const int64_t row_blocks = (m + rows_per_block - 1) / rows_per_block;
-  int64_t nchunks = (n + 63) / 64;              // >= 64 columns per chunk
-  const int64_t want = (int64_t)ctx->num_cu * 8 / (row_blocks > 0 ? row_blocks : 1) + 1;
-  if (nchunks > want) nchunks = want;
-  if (nchunks > cap / (m > 0 ? m : 1)) nchunks = cap / (m > 0 ? m : 1);
-  if (nchunks < 1) nchunks = 1;
-  if (nchunks > 65535) nchunks = 65535;
-  const int64_t cpc = (n + nchunks - 1) / nchunks;
-  nchunks = n > 0 ? (n + cpc - 1) / cpc : 1;
-  dim3 grid((unsigned)row_blocks, (unsigned)nchunks);
-  if (pair)
-    hipLaunchKernelGGL((gemv_n_partial_kernel<T, true>), grid, dim3(kBlock), 0, ctx->stream, ctx->partials, M, m,
-                       n, ld, v, cpc > 0 ? cpc : 1);
-  else
-    hipLaunchKernelGGL((gemv_n_partial_kernel<T, false>), grid, dim3(kBlock), 0, ctx->stream, ctx->partials, M, m,
-                       n, ld, v, cpc > 0 ? cpc : 1);
-  MXLO_LAUNCH_CHECK();
+  const ColChunks cc = gemv_col_chunks(m, n, (int64_t)kBlock * (pair ? 2 : 1), ctx->num_cu, cap);
+  MXLO_TRY(with_bool(pair, [&](auto PAIR) -> int32_t {
+    hipLaunchKernelGGL((gemv_n_partial_kernel<T, PAIR.value>), dim3((unsigned)cc.row_blocks, (unsigned)cc.nchunks), dim3(kBlock), 0,
+                       ctx->stream, ctx->partials, M, m, n, ld, v, cc.cpc);
+    MXLO_LAUNCH_CHECK();
+    return MXLO_OK;
+  }));
   const unsigned fin_blocks = (unsigned)((m + 31) / 32);
   return dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
     hipLaunchKernelGGL((gemv_n_finish_kernel<T, CA, CB, B0>), dim3(fin_blocks), dim3(kBlock), 0, ctx->stream, res,
-                       ctx->partials, m, (int)nchunks, (CA)alpha, (CB)beta, (T *)nullptr);
+                       ctx->partials, m, (int)cc.nchunks, (CA)alpha, (CB)beta, (T *)nullptr);
     MXLO_LAUNCH_CHECK();
     return MXLO_OK;
   });
@@ -471,17 +402,16 @@ int32_t gemv_t(mxlo_ctx *ctx, T *res, const T *M, int64_t m, int64_t n, int64_t 
   // the nontemporal hint (worth 6.3 -> 7.1 TB/s on an HBM-sized read) is kept for footprints beyond nt_min_bytes only
   const bool nt = (int64_t)sizeof(T) * m * n >= ctx->tune.nt_min_bytes;
   return dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
-    if (pair && !nt)
-      hipLaunchKernelGGL((gemv_t_kernel<T, CA, CB, B0, true, false>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream,
-                         res, M, m, n, ld, v, (CA)alpha, (CB)beta);
-    else if (pair)
-      hipLaunchKernelGGL((gemv_t_kernel<T, CA, CB, B0, true>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream,
-                         res, M, m, n, ld, v, (CA)alpha, (CB)beta);
-    else
-      hipLaunchKernelGGL((gemv_t_kernel<T, CA, CB, B0, false>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream,
-                         res, M, m, n, ld, v, (CA)alpha, (CB)beta);
-    MXLO_LAUNCH_CHECK();
-    return MXLO_OK;
+    return with_bool(pair, [&](auto PAIR) -> int32_t {
+      auto go = [&](auto NT) -> int32_t {
+        hipLaunchKernelGGL((gemv_t_kernel<T, CA, CB, B0, PAIR.value, NT.value>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream,
+                           res, M, m, n, ld, v, (CA)alpha, (CB)beta);
+        MXLO_LAUNCH_CHECK();
+        return MXLO_OK;
+      };
+      if constexpr (PAIR.value) return with_bool(nt, go);
+      else return go(std::true_type{});        // the hint belongs to the 16-byte loads: one scalar form
+    });
   });
 }
 
@@ -943,80 +873,41 @@ gemvb_t_lds_kernel(T *__restrict__ res, int64_t ldr, const T *__restrict__ M, in
   }
 }
 
-inline int32_t ensure_scratch(mxlo_ctx *ctx, size_t need, const char *what) {
-  if (ctx->scratch_bytes < need) {            // stream-ordered users only: drain before the buffer is replaced
-    if (ctx->scratch) {
-      MXLO_HIP(hipStreamSynchronize(ctx->stream));
-      MXLO_HIP(hipFree(ctx->scratch));
-    }
-    ctx->scratch = nullptr;
-    ctx->scratch_bytes = 0;
-    hipError_t e = hipMalloc(&ctx->scratch, need);
-    MXLO_REQUIRE(e == hipSuccess, MXLO_ENOMEM, "%s scratch: %s", what, hipGetErrorString(e));
-    ctx->scratch_bytes = need;
-    ++ctx->scratch_generation;     // graphs that recorded the old workspace pointer are stale now
-  }
-  if (ctx->capturing) ctx->scratch_used_in_capture = true;
-  return MXLO_OK;
-}
-
 // one chunk of KB <= 8 columns
 template <typename T, int KB>
 int32_t gemv_block_chunk(mxlo_ctx *ctx, T *res, int64_t ldr, const T *M, int64_t m, int64_t n, int64_t ld, const T *V,
                          int64_t ldv, double alpha, double beta, int32_t mode, int32_t flags) {
+  constexpr int VR = 16 / (int)sizeof(T);
   if (mode == MXLO_OP_N) {
     // Row bands with the block staged in LDS per WORKGROUP (round 6; the round-5 attempt staged it per wave and step and was
     // slower everywhere): taken where the single apply takes its 512- / 256-byte bands, so that every column of the block
     // has the bits of gemv_n on that column.
-    {
-      constexpr int VR = 16 / (int)sizeof(T);
-      // the tallest band that still gives every CU a workgroup (gemv_rows_band's rule without its exceptions for very wide
-      // matrices: those weigh a finish launch that the block form's column-chunk schedule pays KB-fold)
-      const bool vec = (((uintptr_t)M & 15u) == 0) && ld % VR == 0 && m % VR == 0;
-      int rb = 0;
-      if (ctx->tune.gemvb_n_rows && vec && n >= 1024) {
-        if (m >= (int64_t)32 * VR * ctx->num_cu) rb = 32 * VR;
-        else if (m >= (int64_t)16 * VR * ctx->num_cu) rb = 16 * VR;
-        else if (m >= (int64_t)8 * VR * ctx->num_cu) rb = 8 * VR;
-      }
-      if (rb != 0) {
-        const bool nt = (int64_t)sizeof(T) * m * n >= ctx->tune.nt_min_bytes;
-        return dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
-#define BROWS(RB_, NT_)                                                                                                  \
-  hipLaunchKernelGGL((gemvb_n_rows_kernel<T, CA, CB, B0, KB, RB_, NT_>), dim3((unsigned)((m + (RB_) - 1) / (RB_))),      \
-                     dim3(kGemvRowsBlock), 0, ctx->stream, res, ldr, M, m, n, ld, V, ldv, (CA)alpha, (CB)beta)
-          if (rb == 32 * VR) { if (nt) BROWS(32 * VR, true); else BROWS(32 * VR, false); }
-          else if (rb == 16 * VR) { if (nt) BROWS(16 * VR, true); else BROWS(16 * VR, false); }
-          else { if (nt) BROWS(8 * VR, true); else BROWS(8 * VR, false); }
-#undef BROWS
-          MXLO_LAUNCH_CHECK();
-          return MXLO_OK;
+    if (const int rb = gemv_row_band<T>(M, m, n, ld, ctx->num_cu, 0, ctx->tune.gemvb_n_rows != 0, false); rb != 0) {
+      const bool nt = (int64_t)sizeof(T) * m * n >= ctx->tune.nt_min_bytes;
+      return dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
+        return with_int<32 * VR, 16 * VR, 8 * VR>(rb, [&](auto RB) {
+          return with_bool(nt, [&](auto NT) -> int32_t {
+            hipLaunchKernelGGL((gemvb_n_rows_kernel<T, CA, CB, B0, KB, RB.value, NT.value>), dim3((unsigned)((m + RB.value - 1) / RB.value)),
+                               dim3(kGemvRowsBlock), 0, ctx->stream, res, ldr, M, m, n, ld, V, ldv, (CA)alpha, (CB)beta);
+            MXLO_LAUNCH_CHECK();
+            return MXLO_OK;
+          });
         });
-      }
+      });
     }
     const bool pair = m >= 2 && (((uintptr_t)M % (2 * sizeof(T))) == 0) && (ld % 2 == 0);
-    const int64_t rows_per_block = (int64_t)kBlock * (pair ? 2 : 1);
-    const int64_t row_blocks = (m + rows_per_block - 1) / rows_per_block;
-    int64_t nchunks = (n + 63) / 64;
-    const int64_t want = (int64_t)ctx->num_cu * 8 / (row_blocks > 0 ? row_blocks : 1) + 1;
-    if (nchunks > want) nchunks = want;
-    if (nchunks > 65535) nchunks = 65535;
-    if (nchunks < 1) nchunks = 1;
-    const int64_t cpc = (n + nchunks - 1) / nchunks;
-    nchunks = (n + cpc - 1) / cpc;
-    MXLO_TRY(ensure_scratch(ctx, sizeof(double) * (size_t)nchunks * KB * (size_t)m, "block GEMV"));
+    const ColChunks cc = gemv_col_chunks(m, n, (int64_t)kBlock * (pair ? 2 : 1), ctx->num_cu);
+    MXLO_TRY(ensure_scratch(ctx, sizeof(double) * (size_t)cc.nchunks * KB * (size_t)m, "block GEMV"));
     double *part = (double *)ctx->scratch;
-    dim3 grid((unsigned)row_blocks, (unsigned)nchunks);
-    if (pair)
-      hipLaunchKernelGGL((gemvb_n_partial_kernel<T, KB, true>), grid, dim3(kBlock), 0, ctx->stream, part, M, m, n, ld, V,
-                         ldv, cpc);
-    else
-      hipLaunchKernelGGL((gemvb_n_partial_kernel<T, KB, false>), grid, dim3(kBlock), 0, ctx->stream, part, M, m, n, ld,
-                         V, ldv, cpc);
-    MXLO_LAUNCH_CHECK();
+    MXLO_TRY(with_bool(pair, [&](auto PAIR) -> int32_t {
+      hipLaunchKernelGGL((gemvb_n_partial_kernel<T, KB, PAIR.value>), dim3((unsigned)cc.row_blocks, (unsigned)cc.nchunks), dim3(kBlock), 0,
+                         ctx->stream, part, M, m, n, ld, V, ldv, cc.cpc);
+      MXLO_LAUNCH_CHECK();
+      return MXLO_OK;
+    }));
     return dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
       hipLaunchKernelGGL((gemvb_n_finish_kernel<T, CA, CB, B0>), dim3((unsigned)((m + 31) / 32), (unsigned)KB),
-                         dim3(kBlock), 0, ctx->stream, res, ldr, part, m, (int)nchunks, KB, (CA)alpha, (CB)beta);
+                         dim3(kBlock), 0, ctx->stream, res, ldr, part, m, (int)cc.nchunks, KB, (CA)alpha, (CB)beta);
       MXLO_LAUNCH_CHECK();
       return MXLO_OK;
     });
@@ -1025,7 +916,6 @@ int32_t gemv_block_chunk(mxlo_ctx *ctx, T *res, int64_t ldr, const T *M, int64_t
   const int64_t cap = (int64_t)ctx->num_cu * 16;
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
-  constexpr int VR = 16 / (int)sizeof(T);
   const bool pair = m >= VR && (((uintptr_t)M & 15u) == 0) && (ld % VR == 0) && (((uintptr_t)V & 15u) == 0) &&
                     (ldv % VR == 0);
   // >= 4 columns of U on a matrix tall enough for a few row chunks: the LDS-staged form (32 columns of M per workgroup)
@@ -1033,24 +923,22 @@ int32_t gemv_block_chunk(mxlo_ctx *ctx, T *res, int64_t ldr, const T *M, int64_t
   return dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
     if constexpr (KB >= 4) {
       if (lds_form) {
-        if ((n + 31) / 32 >= ctx->num_cu)
-          hipLaunchKernelGGL((gemvb_t_lds_kernel<T, CA, CB, B0, KB, 512>), dim3((unsigned)((n + 31) / 32)), dim3(512), 0, ctx->stream,
-                             res, ldr, M, m, n, ld, V, ldv, (CA)alpha, (CB)beta);
-        else
-          hipLaunchKernelGGL((gemvb_t_lds_kernel<T, CA, CB, B0, KB, 256>), dim3((unsigned)((n + 15) / 16)), dim3(256), 0, ctx->stream,
-                             res, ldr, M, m, n, ld, V, ldv, (CA)alpha, (CB)beta);
-        MXLO_LAUNCH_CHECK();
-        return MXLO_OK;
+        // 32 columns per 512-thread workgroup once that gives every CU one, else 16 columns per 256 threads
+        return with_bool((n + 31) / 32 >= ctx->num_cu, [&](auto WIDE) -> int32_t {
+          constexpr int BLOCK = WIDE.value ? 512 : 256, COLS = BLOCK / 16;
+          hipLaunchKernelGGL((gemvb_t_lds_kernel<T, CA, CB, B0, KB, BLOCK>), dim3((unsigned)((n + COLS - 1) / COLS)), dim3(BLOCK), 0,
+                             ctx->stream, res, ldr, M, m, n, ld, V, ldv, (CA)alpha, (CB)beta);
+          MXLO_LAUNCH_CHECK();
+          return MXLO_OK;
+        });
       }
     }
-    if (pair)
-      hipLaunchKernelGGL((gemvb_t_kernel<T, CA, CB, B0, KB, true>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream,
+    return with_bool(pair, [&](auto PAIR) -> int32_t {
+      hipLaunchKernelGGL((gemvb_t_kernel<T, CA, CB, B0, KB, PAIR.value>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream,
                          res, ldr, M, m, n, ld, V, ldv, (CA)alpha, (CB)beta);
-    else
-      hipLaunchKernelGGL((gemvb_t_kernel<T, CA, CB, B0, KB, false>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream,
-                         res, ldr, M, m, n, ld, V, ldv, (CA)alpha, (CB)beta);
-    MXLO_LAUNCH_CHECK();
-    return MXLO_OK;
+      MXLO_LAUNCH_CHECK();
+      return MXLO_OK;
+    });
   });
 }
 
@@ -1567,57 +1455,33 @@ __global__ void __launch_bounds__(kBlock) herm_slots_fill_kernel(unsigned long l
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += (int64_t)gridDim.x * kBlock) p[i] = kSlotEmpty;
 }
 
-// Cache policy of the strip loads (tune key herm_nt: -1 = this rule, 0 / 1 force): nontemporal, EXCEPT for triangles of about
-// the size of the 256 MiB Infinity Cache — [herm_dp_min_bytes, herm_nt_min_bytes) = [96, 384) MiB — where the next apply of
-// the same operator (a Krylov loop) finds part of a default-policy stream still there. Measured, old vs new library in one
-// run (profiles/r06_herm_policy.txt): f64 n = 6144 29.8 -> 28.2 us, 8192 49.9 -> 47.3; 4096 / 5120 neutral; below (3072) the
-// default policy is 10 % SLOWER, above (16384) 9 % slower.
+// The tile / strip geometry of an n x n operand (launch_plans.h; cache policy of the strip loads: herm_nt_policy there)
 template <typename T>
-inline int herm_nt_policy(const mxlo_ctx *ctx, int64_t n) {
-  if (ctx->tune.herm_nt >= 0) return ctx->tune.herm_nt;
-  const int64_t tri = (int64_t)sizeof(T) * n * (n / 2);
-  return tri >= ctx->tune.herm_dp_min_bytes && tri < ctx->tune.herm_nt_min_bytes ? 0 : 1;
+HermGeom herm_geom_of(const mxlo_ctx *ctx, const T *A, int64_t lda, int64_t n) {
+  using Cfg = HermCfg<T>;
+  const bool aligned = (((uintptr_t)A & 15u) == 0) && (lda % Cfg::RPL == 0);
+  return herm_geom(n, Cfg::HR, Cfg::DT, aligned,
+                   [&](int64_t pairs) { return herm_strip_tiles(ctx, sizeof(T), Cfg::DT, n, pairs); });
 }
-
-// Tiles per strip: 8-tile strips once there are two of them per CU, 2-tile strips with two per CU, else single tiles. Triangles
-// small enough for the single-launch form (herm_small) take 2-tile strips from 1.25 per CU on — measured with the one launch
-// (profiles/r06_herm_policy.txt): f64 n = 4096 14.8 -> 14.4 us, f32 n = 5120 14.1 -> 13.6; f64 n = 3072 (1.03 per CU) 10.1 -> 11.0:
-// stays single tiles. The rule depends on (n, T, CUs) only, so the single launch and the two launches share their partial
-// layout and stay bit-identical.
-template <typename T>
-inline bool herm_small(const mxlo_ctx *ctx, int64_t n) {
-  if (ctx->tune.herm_single_max_n > 0) return n <= ctx->tune.herm_single_max_n;
-  return (int64_t)sizeof(T) * n * (n / 2) <= ctx->tune.herm_single_max_bytes;
-}
-template <typename T>
-inline int herm_strip_tiles(const mxlo_ctx *ctx, int64_t n, int64_t pairs) {
-  constexpr int DT = HermCfg<T>::DT;
-  if (ctx->tune.herm_strip) return ctx->tune.herm_strip;
-  if ((DT / 8) * pairs >= 2 * ctx->num_cu) return 8;
-  if ((DT / 2) * pairs * 4 >= (herm_small<T>(ctx, n) ? 5 : 8) * (int64_t)ctx->num_cu) return 2;
-  return 1;
-}
+constexpr int kHermFinishRows = 32;   // rows per finishing workgroup (8 ... 64 measured alike)
 
 template <typename T>
 int32_t hermitian_t(mxlo_ctx *ctx, T *res, const T *d, const T *A, int64_t lda, const T *v, int64_t n,
                     double alpha, double beta, int32_t flags) {
   if (n == 0) return MXLO_OK;
-  constexpr int HR = HermCfg<T>::HR, DT = HermCfg<T>::DT, RPL = HermCfg<T>::RPL;
-  const int64_t ng = (n + HR - 1) / HR, ngf = n / HR;
-  MXLO_REQUIRE(4 * ng * (ng + 1) < (1LL << 31), MXLO_ESHAPE, "opHermitian: n too large");
-  // tiles per strip: 8-tile strips once there are at least two of them per CU, thinner strips below that
-  const int64_t pairs = ng * (ng - 1) / 2;                       // (row group, strip column block) pairs left of the diagonal
-  const int C = herm_strip_tiles<T>(ctx, n, pairs), Q = DT / C;
-  const int64_t prow_len = herm_row_base<HR, DT>(ng, Q), pcol_len = herm_col_base<HR>(ng, ng);
+  constexpr int HR = HermCfg<T>::HR, DT = HermCfg<T>::DT, FR = kHermFinishRows;
+  const HermGeom g = herm_geom_of<T>(ctx, A, lda, n);
+  MXLO_REQUIRE(!g.too_large, MXLO_ESHAPE, "opHermitian: n too large");
+  const int64_t prow_len = herm_row_base<HR, DT>(g.ng, g.Q), pcol_len = herm_col_base<HR>(g.ng, g.ng);
   const size_t need = sizeof(double) * (size_t)(prow_len + pcol_len);
-  const bool aligned = (((uintptr_t)A & 15u) == 0) && (lda % RPL == 0);
-  const int nt = herm_nt_policy<T>(ctx, n);
+  const bool nt = herm_nt_policy(ctx, sizeof(T), n);
   // ---- the whole apply in ONE launch: full row groups of an aligned matrix, slots in their own (always re-armed) buffer
-  if (ctx->tune.herm_single && aligned && n % HR == 0 && herm_small<T>(ctx, n) && ctx->fault_dev && !ctx->capturing) {
+  if (ctx->tune.herm_single && g.aligned && n % HR == 0 && herm_small(ctx, sizeof(T), n) && ctx->fault_dev && !ctx->capturing) {
     int32_t fst = fused_fault_check(ctx);
     if (fst != MXLO_OK) return fst;
     if (ctx->tune.herm_single) {              // (the fault check switches the single-launch forms off)
-      if (ctx->herm_slots_bytes < need || ctx->herm_slots_layout != (int64_t)n * 64 + C * 2 + (sizeof(T) == 8 ? 1 : 0) || ctx->herm_slots_dirty) {
+      const int64_t layout = (int64_t)n * 64 + g.C * 2 + (sizeof(T) == 8 ? 1 : 0);
+      if (ctx->herm_slots_bytes < need || ctx->herm_slots_layout != layout || ctx->herm_slots_dirty) {
         if (ctx->herm_slots_bytes < need) {
           if (ctx->herm_slots) {
             MXLO_HIP(hipStreamSynchronize(ctx->stream));
@@ -1634,75 +1498,46 @@ int32_t hermitian_t(mxlo_ctx *ctx, T *res, const T *d, const T *A, int64_t lda, 
         hipLaunchKernelGGL(herm_slots_fill_kernel, dim3(ctx->num_cu * 4), dim3(kBlock), 0, ctx->stream,
                            (unsigned long long *)ctx->herm_slots, (int64_t)(ctx->herm_slots_bytes / 8));
         MXLO_LAUNCH_CHECK();
-        ctx->herm_slots_layout = (int64_t)n * 64 + C * 2 + (sizeof(T) == 8 ? 1 : 0);
+        ctx->herm_slots_layout = layout;
         ctx->herm_slots_dirty = false;
       }
       double *Sr = ctx->herm_slots, *Sc = Sr + prow_len;
-      const int64_t n_int1 = ngf > 1 ? Q * ngf * (ngf - 1) / 2 : 0, n_light1 = n_int1 + (int64_t)DT * ngf;
-      constexpr int FR1 = 32;
-      const int64_t grid1 = n_light1 + (n + FR1 - 1) / FR1;
-      bool fits = true;
-      const int32_t st1 = dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
-        auto go = [&]<int C_>() -> int32_t {
-          // (no co-residency requirement: the strip workgroups wait for nobody, and the finishers — the last workgroups of the
-          //  1-D grid — are dispatched after all of them)
-          hipLaunchKernelGGL((herm_single_kernel<T, C_, CA, CB, B0, FR1>), dim3((unsigned)grid1), dim3(kBlock), 0, ctx->stream, res, d, A,
-                             lda, v, n, Sr, Sc, ng, Q, n_int1, n_light1, (CA)alpha, (CB)beta, fused_timeout_ticks(ctx), ctx->fault_dev,
-                             ctx->tune.herm_order && n > 2048 ? (int)ngf : 0, ctx->tune.herm_poll_sleep);
+      // every row group is full and unmasked here: the strips and diagonal tiles are g.n_light workgroups, the finishers follow
+      // (no co-residency requirement: the strip workgroups wait for nobody, and the finishers — the last workgroups of the
+      //  1-D grid — are dispatched after all of them)
+      const int64_t grid1 = g.n_light + (n + FR - 1) / FR;
+      return dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
+        return with_int<8, 2, 1>(g.C, [&](auto C_) -> int32_t {
+          hipLaunchKernelGGL((herm_single_kernel<T, C_.value, CA, CB, B0, FR>), dim3((unsigned)grid1), dim3(kBlock), 0, ctx->stream, res, d, A,
+                             lda, v, n, Sr, Sc, g.ng, g.Q, g.n_int, g.n_light, (CA)alpha, (CB)beta, fused_timeout_ticks(ctx), ctx->fault_dev,
+                             ctx->tune.herm_order && n > 2048 ? (int)g.ngf : 0, ctx->tune.herm_poll_sleep);
           MXLO_LAUNCH_CHECK();
           return MXLO_OK;
-        };
-        return C == 8 ? go.template operator()<8>() : (C == 2 ? go.template operator()<2>() : go.template operator()<1>());
+        });
       });
-      if (st1 != MXLO_OK || fits) return st1;
     }
   }
-  if (ctx->scratch_bytes < need) {            // stream-ordered users only: drain before the buffer is replaced
-    if (ctx->scratch) {
-      MXLO_HIP(hipStreamSynchronize(ctx->stream));
-      MXLO_HIP(hipFree(ctx->scratch));
-    }
-    ctx->scratch = nullptr;
-    ctx->scratch_bytes = 0;
-    hipError_t e = hipMalloc(&ctx->scratch, need);
-    MXLO_REQUIRE(e == hipSuccess, MXLO_ENOMEM, "opHermitian scratch: %s", hipGetErrorString(e));
-    ctx->scratch_bytes = need;
-    ++ctx->scratch_generation;     // graphs that recorded the old workspace pointer are stale now
-  }
-  if (ctx->capturing) ctx->scratch_used_in_capture = true;
+  MXLO_TRY(ensure_scratch(ctx, need, "opHermitian"));
   double *Prow = (double *)ctx->scratch, *Pcol = Prow + prow_len;
   // full row groups (aligned A): interior strips + diagonal tiles in the unmasked launch; everything else is masked
-  const int64_t gi = aligned ? ngf : 0;
-  const int64_t n_int = gi > 1 ? Q * gi * (gi - 1) / 2 : 0;
-  const int64_t n_dsel = (int64_t)DT * gi;
-  const int64_t n_all = !aligned && ng > 1 ? Q * ng * (ng - 1) / 2 : 0;       // mode 0, masked
-  const int64_t n_last = aligned && ng > ngf ? Q * (ng - 1) : 0;               // mode 1
-  const int64_t n_diag = (int64_t)DT * (ng - gi);                              // mode 2, row groups gi .. ng-1
-  const int64_t n_light = n_int + n_dsel, n_edge = n_all + n_last + n_diag;
-  MXLO_REQUIRE(n_light < (1LL << 31) && n_edge < (1LL << 31), MXLO_ESHAPE, "opHermitian: n too large");
-#define HERM_LAUNCH(C_)                                                                                          \
-  {                                                                                                              \
-    if (n_light > 0) {                                                                                           \
-      if (nt)                                                                                                    \
-        hipLaunchKernelGGL((herm_pass_kernel<T, C_, true>), dim3((unsigned)n_light), dim3(kBlock), (size_t)ctx->tune.herm_lds_pad, ctx->stream, A, lda, v, \
-                           n, Prow, Pcol, ng, Q, n_int, ctx->tune.herm_order ? (int)gi : 0);                     \
-      else                                                                                                       \
-        hipLaunchKernelGGL((herm_pass_kernel<T, C_, false>), dim3((unsigned)n_light), dim3(kBlock), (size_t)ctx->tune.herm_lds_pad, ctx->stream, A, lda, v, \
-                           n, Prow, Pcol, ng, Q, n_int, ctx->tune.herm_order ? (int)gi : 0);                     \
-      MXLO_LAUNCH_CHECK();                                                                                       \
-    }                                                                                                            \
-    if (n_edge > 0) {                                                                                            \
-      hipLaunchKernelGGL((herm_edge_kernel<T, C_>), dim3((unsigned)n_edge), dim3(kBlock), 0, ctx->stream, A, lda, v,  \
-                         n, Prow, Pcol, ng, Q, n_all, n_last, gi);                                               \
-      MXLO_LAUNCH_CHECK();                                                                                       \
-    }                                                                                                            \
-  }
-  if (C == 8) HERM_LAUNCH(8) else if (C == 2) HERM_LAUNCH(2) else HERM_LAUNCH(1)
-#undef HERM_LAUNCH
-  constexpr int FR = 32;                       // rows per finishing workgroup (8 ... 64 measured alike)
+  MXLO_TRY((with_int<8, 2, 1>(g.C, [&](auto C_) -> int32_t {
+    if (g.n_light > 0)
+      MXLO_TRY(with_bool(nt, [&](auto NT) -> int32_t {
+        hipLaunchKernelGGL((herm_pass_kernel<T, C_.value, NT.value>), dim3((unsigned)g.n_light), dim3(kBlock), (size_t)ctx->tune.herm_lds_pad,
+                           ctx->stream, A, lda, v, n, Prow, Pcol, g.ng, g.Q, g.n_int, ctx->tune.herm_order ? (int)g.gi : 0);
+        MXLO_LAUNCH_CHECK();
+        return MXLO_OK;
+      }));
+    if (g.n_edge > 0) {
+      hipLaunchKernelGGL((herm_edge_kernel<T, C_.value>), dim3((unsigned)g.n_edge), dim3(kBlock), 0, ctx->stream, A, lda, v,
+                         n, Prow, Pcol, g.ng, g.Q, g.n_all, g.n_last, g.gi);
+      MXLO_LAUNCH_CHECK();
+    }
+    return MXLO_OK;
+  })));
   return dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
     hipLaunchKernelGGL((herm_finish_kernel<T, CA, CB, B0, FR>), dim3((unsigned)((n + FR - 1) / FR)), dim3(kBlock), 0,
-                       ctx->stream, res, d, v, Prow, Pcol, n, (int)ng, Q, (CA)alpha, (CB)beta);
+                       ctx->stream, res, d, v, Prow, Pcol, n, (int)g.ng, g.Q, (CA)alpha, (CB)beta);
     MXLO_LAUNCH_CHECK();
     return MXLO_OK;
   });
@@ -1710,31 +1545,21 @@ int32_t hermitian_t(mxlo_ctx *ctx, T *res, const T *d, const T *A, int64_t lda, 
 
 // res[:, c] = alpha * ((d .* V[:, c] + L V[:, c]) + L' V[:, c]) + beta * res[:, c], c < k — mulHermitian! (src/linalg.jl:97-103)
 // applied to the columns of a matrix (src/operations.jl:34-36), the strict lower triangle read ONCE per chunk of up to 4
-// columns instead of once per column. Same launch geometry, partial layout and summation order as hermitian_t per column.
+// columns instead of once per column. Same launch geometry (one HermGeom), partial layout and summation order as hermitian_t
+// per column.
 template <typename T>
 int32_t hermitian_block_t(mxlo_ctx *ctx, T *res, int64_t ldr, const T *d, const T *A, int64_t lda, const T *V, int64_t ldv,
                           int64_t n, int64_t k, double alpha, double beta, int32_t flags) {
   if (n == 0 || k == 0) return MXLO_OK;
-  constexpr int HR = HermCfg<T>::HR, DT = HermCfg<T>::DT, RPL = HermCfg<T>::RPL;
-  const int64_t ng = (n + HR - 1) / HR, ngf = n / HR;
-  MXLO_REQUIRE(4 * ng * (ng + 1) < (1LL << 31), MXLO_ESHAPE, "opHermitian: n too large");
-  const int64_t pairs = ng * (ng - 1) / 2;
-  const int C = herm_strip_tiles<T>(ctx, n, pairs), Q = DT / C;
-  const int64_t prow_len = herm_row_base<HR, DT>(ng, Q), pcol_len = herm_col_base<HR>(ng, ng);
+  constexpr int HR = HermCfg<T>::HR, DT = HermCfg<T>::DT, FR = kHermFinishRows;
+  const HermGeom g = herm_geom_of<T>(ctx, A, lda, n);
+  MXLO_REQUIRE(!g.too_large, MXLO_ESHAPE, "opHermitian: n too large");
+  const int64_t prow_len = herm_row_base<HR, DT>(g.ng, g.Q), pcol_len = herm_col_base<HR>(g.ng, g.ng);
   const int64_t pstride = prow_len + pcol_len;
   constexpr int KVMAX = 4;
   MXLO_TRY(ensure_scratch(ctx, sizeof(double) * (size_t)pstride * KVMAX, "opHermitian block"));
   double *Prow = (double *)ctx->scratch, *Pcol = Prow + prow_len;
-  const bool aligned = (((uintptr_t)A & 15u) == 0) && (lda % RPL == 0);
-  const int nt = herm_nt_policy<T>(ctx, n);
-  const int64_t gi = aligned ? ngf : 0;
-  const int64_t n_int = gi > 1 ? Q * gi * (gi - 1) / 2 : 0;
-  const int64_t n_dsel = (int64_t)DT * gi;
-  const int64_t n_all = !aligned && ng > 1 ? Q * ng * (ng - 1) / 2 : 0;
-  const int64_t n_last = aligned && ng > ngf ? Q * (ng - 1) : 0;
-  const int64_t n_diag = (int64_t)DT * (ng - gi);
-  const int64_t n_light = n_int + n_dsel, n_edge = n_all + n_last + n_diag;
-  MXLO_REQUIRE(n_light < (1LL << 31) && n_edge < (1LL << 31), MXLO_ESHAPE, "opHermitian: n too large");
+  const bool nt = herm_nt_policy(ctx, sizeof(T), n);
   int64_t done = 0;
   while (done < k) {
     const int64_t left = k - done;
@@ -1748,31 +1573,27 @@ int32_t hermitian_block_t(mxlo_ctx *ctx, T *res, int64_t ldr, const T *d, const 
       done += 1;
       continue;
     }
-    auto launch = [&]<int C_, int KV_>() -> int32_t {
-      if (n_light > 0) {
-        if (nt)
-          hipLaunchKernelGGL((herm_pass_block_kernel<T, C_, KV_, true>), dim3((unsigned)n_light), dim3(kBlock), (size_t)ctx->tune.herm_lds_pad, ctx->stream, A, lda, v, ldv, n,
-                             Prow, Pcol, pstride, ng, Q, n_int, ctx->tune.herm_order ? (int)gi : 0);
-        else
-          hipLaunchKernelGGL((herm_pass_block_kernel<T, C_, KV_, false>), dim3((unsigned)n_light), dim3(kBlock), (size_t)ctx->tune.herm_lds_pad, ctx->stream, A, lda, v, ldv, n,
-                             Prow, Pcol, pstride, ng, Q, n_int, ctx->tune.herm_order ? (int)gi : 0);
-        MXLO_LAUNCH_CHECK();
-      }
-      if (n_edge > 0) {
-        hipLaunchKernelGGL((herm_edge_block_kernel<T, C_, KV_>), dim3((unsigned)n_edge), dim3(kBlock), 0, ctx->stream, A, lda, v, ldv, n,
-                           Prow, Pcol, pstride, ng, Q, n_all, n_last, gi);
-        MXLO_LAUNCH_CHECK();
-      }
-      return MXLO_OK;
-    };
-    auto by_c = [&]<int KV_>() -> int32_t {
-      return C == 8 ? launch.template operator()<8, KV_>() : (C == 2 ? launch.template operator()<2, KV_>() : launch.template operator()<1, KV_>());
-    };
-    MXLO_TRY(kv == 4 ? by_c.template operator()<4>() : by_c.template operator()<2>());
-    constexpr int FR = 32;
+    MXLO_TRY((with_int<4, 2>(kv, [&](auto KV) {
+      return with_int<8, 2, 1>(g.C, [&](auto C_) -> int32_t {
+        if (g.n_light > 0)
+          MXLO_TRY(with_bool(nt, [&](auto NT) -> int32_t {
+            hipLaunchKernelGGL((herm_pass_block_kernel<T, C_.value, KV.value, NT.value>), dim3((unsigned)g.n_light), dim3(kBlock),
+                               (size_t)ctx->tune.herm_lds_pad, ctx->stream, A, lda, v, ldv, n, Prow, Pcol, pstride, g.ng, g.Q, g.n_int,
+                               ctx->tune.herm_order ? (int)g.gi : 0);
+            MXLO_LAUNCH_CHECK();
+            return MXLO_OK;
+          }));
+        if (g.n_edge > 0) {
+          hipLaunchKernelGGL((herm_edge_block_kernel<T, C_.value, KV.value>), dim3((unsigned)g.n_edge), dim3(kBlock), 0, ctx->stream, A, lda,
+                             v, ldv, n, Prow, Pcol, pstride, g.ng, g.Q, g.n_all, g.n_last, g.gi);
+          MXLO_LAUNCH_CHECK();
+        }
+        return MXLO_OK;
+      });
+    })));
     MXLO_TRY((dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
       hipLaunchKernelGGL((herm_finish_block_kernel<T, CA, CB, B0, FR>), dim3((unsigned)((n + FR - 1) / FR), (unsigned)kv), dim3(kBlock), 0,
-                         ctx->stream, r, ldr, d, v, ldv, Prow, Pcol, pstride, n, (int)ng, Q, (CA)alpha, (CB)beta);
+                         ctx->stream, r, ldr, d, v, ldv, Prow, Pcol, pstride, n, (int)g.ng, g.Q, (CA)alpha, (CB)beta);
       MXLO_LAUNCH_CHECK();
       return MXLO_OK;
     })));
@@ -1830,7 +1651,7 @@ int32_t kron_t(mxlo_ctx *ctx, T *res, const T *A, int64_t am, int64_t an, int64_
   const int64_t m = trans_a ? an : am, n = trans_a ? am : an;
   const int64_t p = trans_b ? bq : bp, q = trans_b ? bp : bq;
   // ---- both products in ONE launch with an XCD-local dependency (gemm_glds.h: kron_fused_kernel; tune key kron_fuse):
-  // same tile class for both (the one gemm() would pick for each), the same A layout, every tile of both products on its
+  // same tile class for both (gemm_tile_class, the one gemm() picks for each), the same A layout, every tile of both products on its
   // own CU (grid <= #CU and co-resident), DMA preconditions as gemm().
   // (inside a graph capture only once a warm-up apply has probed the XCD map and allocated the counters: neither can happen there)
   // Not when res overlaps x (mul!(x, K, x) of a square kron, src/kron.jl:14-40 materialises B*X*A' before res .=): the
@@ -1841,12 +1662,7 @@ int32_t kron_t(mxlo_ctx *ctx, T *res, const T *A, int64_t am, int64_t an, int64_
       m < (1LL << 31) && n < (1LL << 31) && p < (1LL << 31) && q < (1LL << 31) && lda < (1LL << 22) && ldb < (1LL << 22) &&
       m < (1LL << 22) && q < (1LL << 22) && gemm_glds_ok<T>(A, lda, trans_a, x, q, m, q, n) &&
       gemm_glds_ok<T>(B, ldb, trans_b, work, m, p, m, q)) {
-    auto tile_of = [&](int64_t M, int64_t N) {
-      auto tiles = [&](int tm, int tn) { return ((M + tm - 1) / tm) * ((N + tn - 1) / tn); };
-      if (tiles(128, 128) >= ctx->num_cu) return 128;
-      return tiles(64, 64) * 5 >= (int64_t)ctx->num_cu * 3 ? 64 : 32;
-    };
-    const int t1 = tile_of(m, q), t2 = tile_of(p, m);
+    const int t1 = gemm_tile_class(m, q, ctx->num_cu), t2 = gemm_tile_class(p, m, ctx->num_cu);
     if (t1 == t2 && t1 != 128) {
       const int tile = t1;
       const int64_t nrb = (m + tile - 1) / tile, gy1 = (q + tile - 1) / tile, gx2 = (p + tile - 1) / tile;
@@ -1864,31 +1680,22 @@ int32_t kron_t(mxlo_ctx *ctx, T *res, const T *A, int64_t am, int64_t an, int64_
           MXLO_HIP(hipMemsetAsync(ctx->kron_cnt, 0, sizeof(unsigned) * 2 * 64 * kGlFuseStride, ctx->stream));
           ctx->kron_cnt_n = 2 * 64 * kGlFuseStride;
         }
-        bool fits = true;
+        bool fits = true;   // false: the grid is not co-resident for this instantiation — nothing launched, the two launches below run
         const int32_t st = dispatch_ab<T>(beta, flags, [&]<typename CA, typename CB, bool B0>() -> int32_t {
           GlFuse F{ctx->kron_cnt, (int)nrb, (int)gy1, (int)gx2, (int)per_xcd, ctx->tune.kron_fuse == 2 ? 0ull : fused_timeout_ticks(ctx), ctx->fault_dev, kFaultKron,
                    ctx->tune.fused_debug_drop};
-#define KFUSE(AK_, TM_, WM_, WN_, BK_, NST_, PAIR_, PFD_, UNR_)                                                                \
-  {                                                                                                                        \
-    GlShape S1{(int)m, (int)q, (int)n, (int)nrb, (int)gy1}, S2{(int)p, (int)m, (int)q, (int)gx2, (int)nrb};               \
-    if ((fits = coresident<kron_fused_kernel<T, CA, CB, B0, AK_, TM_, TM_, WM_, WN_, BK_, NST_, PAIR_, PFD_, UNR_>, WM_ * WN_ * 64>(ctx, grid))) \
-      hipLaunchKernelGGL((kron_fused_kernel<T, CA, CB, B0, AK_, TM_, TM_, WM_, WN_, BK_, NST_, PAIR_, PFD_, UNR_>), dim3((unsigned)grid), \
-                         dim3(WM_ * WN_ * 64), 0, ctx->stream, res, p, B, ldb, work, m, A, lda, x, q, S1, S2, (CA)alpha, (CB)beta, F); \
-  }
-#define KFUSE_BY_A(TM_, WM_, WN_, BK_, NST_, PAIR_, PFD_, UNR_AM_)                                                         \
-  if (trans_a) KFUSE(true, TM_, WM_, WN_, BK_, NST_, PAIR_, PFD_, true) else KFUSE(false, TM_, WM_, WN_, BK_, NST_, PAIR_, PFD_, UNR_AM_)
-          if constexpr (sizeof(T) == 8) {
-            if (tile == 64) KFUSE_BY_A(64, 4, 2, 32, 3, true, 1, true)
-            else KFUSE_BY_A(32, 2, 2, 32, 4, false, 2, true)
-          } else {
-            if (tile == 64) KFUSE_BY_A(64, 4, 2, 64, 3, true, 1, false)
-            else KFUSE_BY_A(32, 2, 2, 64, 4, false, 2, true)
-          }
-#undef KFUSE_BY_A
-#undef KFUSE
-          if (!fits) return MXLO_OK;
-          MXLO_LAUNCH_CHECK();
-          return MXLO_OK;
+          GlShape S1{(int)m, (int)q, (int)n, (int)nrb, (int)gy1}, S2{(int)p, (int)m, (int)q, (int)gx2, (int)nrb};
+          return with_bool(trans_a, [&](auto AK) {
+            return with_int<64, 32>(tile, [&](auto TILE) -> int32_t {           // (no 128-tiles: t1 != 128 above)
+              constexpr GemmTile P = gemm_tile_params(sizeof(T), AK.value, TILE.value);
+              fits = coresident<kron_fused_kernel<T, CA, CB, B0, AK.value, P.TM, P.TM, P.WM, P.WN, P.BK, P.NST, P.PAIR, P.PFD, P.UNR>, P.WM * P.WN * 64>(ctx, grid);
+              if (!fits) return MXLO_OK;
+              hipLaunchKernelGGL((kron_fused_kernel<T, CA, CB, B0, AK.value, P.TM, P.TM, P.WM, P.WN, P.BK, P.NST, P.PAIR, P.PFD, P.UNR>), dim3((unsigned)grid),
+                                 dim3(P.WM * P.WN * 64), 0, ctx->stream, res, p, B, ldb, work, m, A, lda, x, q, S1, S2, (CA)alpha, (CB)beta, F);
+              MXLO_LAUNCH_CHECK();
+              return MXLO_OK;
+            });
+          });
         });
         if (st != MXLO_OK || fits) return st;
       }

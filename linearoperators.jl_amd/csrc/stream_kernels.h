@@ -320,6 +320,25 @@ int32_t dispatch_ab(double beta, int32_t flags, F &&f) {
   }
 }
 
+// A run-time value as a template argument: f is called with a std::bool_constant / std::integral_constant, so a launch site
+// is one generic lambda, [&](auto NT, auto RB) { hipLaunchKernelGGL((kernel<..., RB.value, NT.value>), ...); }. Exactly the
+// listed values are instantiated; where a combination must not exist, the lambda says so with `if constexpr`.
+template <typename F>
+int32_t with_bool(bool flag, F &&f) {
+  return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+// A value outside the list is a defect of the caller (the rules of launch_plans.h return listed values only): no kernel
+// stands in for it.
+template <int... Vs, typename F>
+int32_t with_int(int value, F &&f) {
+  int32_t st = MXLO_OK;
+  if (!((value == Vs && ((st = f(std::integral_constant<int, Vs>{})), true)) || ...)) {
+    fprintf(stderr, "[mxlo] with_int: %d is not one of the dispatched values\n", value);
+    abort();
+  }
+  return st;
+}
+
 // Round caller scalars to the types the flags say they have (a Float32 scalar arrives widened to double).
 inline void eff_scalars(size_t elt, int32_t flags, double &alpha, double &beta) {
   if (!alpha_is_f64(elt, flags)) alpha = (double)(float)alpha;

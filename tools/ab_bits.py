@@ -149,7 +149,46 @@ def cases_linalg(lo, torch, dev):
                 yield from applies(f"opPinv {tag}", lo.opPinv(Ad), dt, g)
 
 
-SECTIONS = {"herm": cases_herm, "dense": cases_dense, "qn": cases_qn, "persist": cases_persist, "linalg": cases_linalg}
+def cases_complex(lo, torch, dev):
+    """complex.hip's dense leaves on ComplexF64 / ComplexF32: the GEMV in modes N, T, C and through the row-major alias at 1000x700,
+    4096x1100 (row bands) and a view of 4096 rows at an odd offset and leading dimension (ComplexF32: column chunks); opHermitian with a
+    real and a complex d under both cherm_two_pass values; beta = 0 and beta != 0 with res pre-filled"""
+    ctx = lo.get_ctx(dev)
+    scal = (("b0", complex(1), complex(0)), ("ab", 0.7 - 0.5j, -1.3 + 0.25j))
+
+    def crand(g, rdt, *shape):
+        return torch.complex(torch.rand(*shape, dtype=rdt, generator=g) - 0.5, torch.rand(*shape, dtype=rdt, generator=g) - 0.5)
+
+    for dt, rdt in ((torch.complex128, torch.float64), (torch.complex64, torch.float32)):
+        for tag, m, n, off in (("1000x700", 1000, 700, 0), ("4096x1100", 4096, 1100, 0), ("view 4096x1100", 4096, 1100, 1)):
+            g = torch.Generator(device="cpu").manual_seed(m * 7 + n + off)
+            big = crand(g, rdt, n, m + 3 * off).to(dev).t()                      # column-major, leading dimension m + 3 * off
+            M = big[off:off + m, :]
+            x, u, rm, rn = (crand(g, rdt, k).to(dev) for k in (n, m, m, n))
+            ops = (("N", lo.LinearOperatorFromMatrix(M), x, rm), ("T", lo.LinearOperatorFromMatrix(M).T, u, rn),
+                   ("C", lo.LinearOperatorFromMatrix(M).H, u, rn),
+                   ("rowmajor N", lo.LinearOperatorFromMatrix(M.t()), u, rn), ("rowmajor C", lo.LinearOperatorFromMatrix(M.t()).H, x, rm))
+            for mode, op, v, r0 in ops:
+                for name, a, b in scal:
+                    r = r0.clone()
+                    lo.mul(r, op, v, a, b)
+                    yield f"complex gemv {str(dt)[6:]} {tag} {mode} {name}", r
+        for n in (100, 256, 1000, 1024, 3000):
+            g = torch.Generator(device="cpu").manual_seed(n)
+            A = crand(g, rdt, n, n).to(dev).t()
+            x, y = crand(g, rdt, n).to(dev), crand(g, rdt, n).to(dev)
+            for dname, d in (("real d", (torch.rand(n, dtype=rdt, generator=g) - 0.5).to(dev)), ("complex d", crand(g, rdt, n).to(dev))):
+                H = lo.opHermitian(d, A)
+                for two_pass in (0, 1):
+                    with ctx.tuned(cherm_two_pass=two_pass):
+                        for name, a, b in scal:
+                            r = y.clone()
+                            lo.mul(r, H, x, a, b)
+                            yield f"complex herm {str(dt)[6:]} n={n} {dname} two_pass={two_pass} {name}", r
+
+
+SECTIONS = {"herm": cases_herm, "dense": cases_dense, "qn": cases_qn, "persist": cases_persist, "linalg": cases_linalg,
+            "complex": cases_complex}
 
 
 def run(sections):
